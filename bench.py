@@ -15,16 +15,22 @@ in cache.  Extra objects of the line (N = 1): `end_to_end` = the same pass for a
 (host buffers in, host-visible results out; pageable and pinned, H2D / kernel / D2H split) and `cpu_baseline` =
 scipy.optimize.linprog called as polytope/solvers.py:152-154 calls it, on the host cores (count stated).
 
-Launch:  python bench.py [--gpus N --steps K --warmup W].  For N > 1 either under a launcher,
+Launch:  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full].  For N > 1 either under a launcher,
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 or plainly as `python bench.py --gpus N`: without WORLD_SIZE in the environment it starts its N ranks itself.
 One rank per GPU; `value` = weak scaling (every rank reduces its own 100k-polytope batches, the packed results
--- 24 B per polytope -- are all-gathered over RCCL, coalesced and overlapped); the same run also measures ONE
-100k-polytope batch partitioned over the ranks (north_star) and reports it as the object `strong`.
+-- 24 B per polytope -- are all-gathered over RCCL, coalesced and overlapped); with `--full` the same run also measures
+ONE 100k-polytope batch partitioned over the ranks (north_star) and reports it as the object `strong`.
 
-Timing: a region = the K steps repeated until it lasts >= 50 ms, between barrier + synchronize on both sides, max over
-ranks; five regions, the median is reported (`--steps 20` alone would be a 4 ms window).  After the clocks every
-polytope of every batch is reduced again by the CPU oracle on the host cores and compared (`parity_checked`).
+Timing: after W warm-up steps (continued to >= 100 ms), ONE region of exactly K steps, between barrier + synchronize on both sides, max over
+ranks; `ms_per_step` = the region / K.  `--dump-outputs DIR` then writes what the last timed step returned (keep, flags,
+r, xc, nlp of its batch, as float64 .npy files; the inputs are seeded, so two runs with the same arguments compare
+output for output).
+
+A plain run does nothing else.  `--full` adds, after the headline: the K steps repeated until a region lasts >= 50 ms,
+five regions, the median (object `repeated`); `end_to_end`, `cpu_baseline` and `secondary` (N = 1); the partitioned
+batch and the cost of one exchange (N > 1); and every polytope of every batch reduced again by the CPU oracle on the
+host cores and compared (`parity_checked`).
 
 Prints ONE JSON line on rank 0.
 """
@@ -43,16 +49,38 @@ HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 SIMD_CLOCK_HZ = 2.4e9  # MI355X_MICROARCH.md: peak engine clock
 
 
-def cpu_baseline(A, b, nlp_gpu):
+def _host_cpus():
+    """The CPUs this job may use: its affinity mask, capped by a cgroup CPU quota and by OMP_NUM_THREADS where a
+    scheduler sets them (os.cpu_count() is the whole host's)."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    try:
+        with open("/sys/fs/cgroup/cpu.max") as f:
+            quota, period = f.read().split()[:2]
+        if quota != "max":
+            n = min(n, max(1, int(int(quota) // int(period))))
+    except (OSError, ValueError):
+        pass
+    omp = os.environ.get("OMP_NUM_THREADS", "")
+    if omp.isdigit() and int(omp) > 0:
+        n = min(n, int(omp))
+    return max(1, n)
+
+
+HOST_CPUS = _host_cpus()   # at import: cpu_baseline() sets OMP_NUM_THREADS=1 for its workers
+
+
+def cpu_baseline(A, b, nlp_gpu, seed, stream):
     """Rank 0, N=1 only, bounded samples of batch 0.  `value` = the reference's own LP path on this host:
     scipy.optimize.linprog called exactly as polytope/solvers.py:152-154 calls it (the only backend the reference
     finds installed here), on the redundancy LPs (F2) of a sample, one process per host core; the one-process
     figure and the C restatement (oracle/plp_oracle.c, 'port') on one core / all cores ride along as side keys.
+    (A, b) = random_hpolytopes(B_PER_GPU, M_ROWS, DIM, seed=seed, stream=stream): the all-cores port regenerates it.
     The oracle leg doubles as a check: the LP count the GPU reported for the sample must equal the oracle's."""
     from oracle import oracle as O
     O.build()
     out = {"value": None, "unit": "LP/s", "cores": None, "kind": "reference", "sample": ""}
-    ncpu = os.cpu_count() or 1
+    ncpu = HOST_CPUS
+    # the workers are spawned, not forked: a fork of this process would carry its open GPU device into every worker
     try:
         from scipy.optimize import linprog
         import multiprocessing as mp
@@ -75,7 +103,7 @@ def cpu_baseline(A, b, nlp_gpu):
         per_task = 4
         avail = (A.shape[0] - ns) // per_task
         mk = lambda lo, hi: [[(A[k], b[k]) for k in range(ns + t * per_task, ns + (t + 1) * per_task)] for t in range(lo, hi)]
-        with mp.get_context("fork").Pool(ncpu) as pool:
+        with mp.get_context("spawn").Pool(ncpu) as pool:
             pool.map(_scipy_chunk, mk(0, min(ncpu, avail)), chunksize=1)  # start the workers, import scipy: not timed
             t0 = time.perf_counter()
             pilot = pool.map(_scipy_chunk, mk(0, min(2 * ncpu, avail)), chunksize=1)
@@ -109,12 +137,10 @@ def cpu_baseline(A, b, nlp_gpu):
     out["sample"] += "; port: oracle/plp_oracle.c reduce() on the first %d polytopes (%d LPs, %.1f s)" % (n, lps, t_or)
     try:  # the same C port on every host core: what a competent CPU code does with the box
         import multiprocessing as mp
-        global _ORACLE_AB
-        _ORACLE_AB = (A, b)
         per = 2000
-        tasks = [((t * per) % A.shape[0], per) for t in range(4 * ncpu)]
-        with mp.get_context("fork").Pool(ncpu) as pool:
-            pool.map(_oracle_chunk, tasks[:ncpu], chunksize=1)  # start the workers, load the library
+        tasks = [(seed, stream, (t * per) % A.shape[0], per) for t in range(4 * ncpu)]
+        with mp.get_context("spawn").Pool(ncpu) as pool:
+            pool.map(_oracle_chunk, tasks[:ncpu], chunksize=1)  # start the workers, load the library, make the batch
             t0 = time.perf_counter()
             res = pool.map(_oracle_chunk, tasks, chunksize=1)
             t_all = time.perf_counter() - t0
@@ -201,10 +227,6 @@ def end_to_end(torch, pa, A, b, dev, reps=10):
                      "note": "upload in %d chunks on a copy stream, the kernel of a chunk starts when it has landed" % len(bounds)}
     out["pageable"]["pcie_frac_of_64GBs"] = (out["pageable"]["h2d_bytes"] + out["pageable"]["d2h_bytes"]) / t / 64e9
     return out
-
-
-_ORACLE_AB = None
-
 
 
 def secondary(torch, pa, dev):
@@ -326,8 +348,8 @@ def secondary(torch, pa, dev):
 
 def _oracle_chunk(args):
     from oracle import oracle as O
-    lo, cnt = args
-    A, b = _ORACLE_AB
+    seed, stream, lo, cnt = args
+    A, b = _batch(seed, stream)
     lps = 0
     for k in range(lo, min(lo + cnt, A.shape[0])):
         lps += O.reduce(A[k], b[k])["nlp"]
@@ -358,11 +380,9 @@ def _scipy_chunk(args):
 _PAR = {}
 
 
-def _parity_task(args):
-    """Pool worker (forked before HIP / RCCL exist in the parent): regenerates batch (seed, stream) -- Philox is
-    counter-based, so this is the rank's own data -- and runs the oracle's reduce() on polytopes [lo, hi)."""
+def _batch(seed, stream):
+    """In a pool worker: batch (seed, stream) regenerated -- Philox is counter-based, so this is the rank's own data."""
     import importlib.util
-    seed, stream, lo, hi = args
     if _PAR.get("key") != (seed, stream):
         if "synth" not in _PAR:   # by path: importing the package would load libplp_hip.so into every worker
             spec = importlib.util.spec_from_file_location("_plp_synth", os.path.join(ROOT, "polytope_amd", "synth.py"))
@@ -370,8 +390,15 @@ def _parity_task(args):
             spec.loader.exec_module(_PAR["synth"])
         _PAR["AB"] = _PAR["synth"].random_hpolytopes(B_PER_GPU, M_ROWS, DIM, seed=seed, stream=stream)
         _PAR["key"] = (seed, stream)
+    return _PAR["AB"]
+
+
+def _parity_task(args):
+    """Pool worker (forked before HIP / RCCL exist in the parent): regenerates batch (seed, stream) and runs the
+    oracle's reduce() on polytopes [lo, hi)."""
+    seed, stream, lo, hi = args
     from oracle import oracle as O
-    A, b = _PAR["AB"]
+    A, b = _batch(seed, stream)
     R = O.reduce_batch(A[lo:hi], b[lo:hi])
     return seed, lo, hi, R["keep"], R["flags"], R["nlp"], R["r"]
 
@@ -443,6 +470,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)  # 0.2 ms each
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--warmup-min-ms", type=float, default=100.0, help="the warm-up runs W steps and goes on until it has "
+                    "lasted at least this long (a few warm-up steps leave the GPU's clocks short of their steady state)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one "
+                    "returned (keep, flags, r, xc, nlp) to DIR/<name>.npy as float64")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: repeated regions, end_to_end, "
+                    "cpu_baseline, secondary (N = 1), the partitioned batch and the exchange cost (N > 1), full-batch parity "
+                    "against the oracle; the --no-* options below switch single parts of it off")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-end-to-end", action="store_true")
     ap.add_argument("--no-parity", action="store_true", help="skip the full-batch parity check against the oracle")
@@ -450,10 +484,10 @@ def main():
                     "(64,16) fused reduce, about three seconds)")
     ap.add_argument("--batches", type=int, default=6, help="distinct 100k-polytope batches the steps rotate over "
                     "(6 x 52.4 MB > 256 MiB Infinity Cache: every step reads its input from HBM)")
-    ap.add_argument("--regions", type=int, default=5, help="timed regions (each: barrier + synchronize, the steps, "
-                    "synchronize + barrier; max over ranks); the line reports the median region")
-    ap.add_argument("--min-region-ms", type=float, default=50.0, help="a region is the K steps repeated until it lasts "
-                    "at least this long (a 20-step region is 4 ms: the figure would move with the box's noise)")
+    ap.add_argument("--regions", type=int, default=5, help="--full: timed regions of the object `repeated` (each: barrier + "
+                    "synchronize, the steps, synchronize + barrier; max over ranks); it reports the median region")
+    ap.add_argument("--min-region-ms", type=float, default=50.0, help="--full: a region of `repeated` is the K steps repeated "
+                    "until it lasts at least this long (a 20-step region is 4 ms: the figure would move with the box's noise)")
     ap.add_argument("--force-dist", action="store_true", help="take the N > 1 code path (process group, exchange "
                     "buffers, overlapped all-gather) even at world size 1: a plumbing check of the RCCL path on a 1-GPU box")
     ap.add_argument("--pipelined", action="store_true", help="N = 1: after the timed regions run the same steps again "
@@ -489,11 +523,11 @@ def main():
     # The parity pool is forked NOW, before HIP and RCCL exist in this process (forking a process that holds a HIP
     # context and RCCL's threads is asking for trouble); it idles until the timed regions are over.
     pool, pool_n = None, 0
-    if not args.no_parity:
+    if args.full and not args.no_parity:
         import multiprocessing as mp
         from oracle import oracle as O
         O.build()   # once, here: the workers only load it
-        pool_n = max(1, (os.cpu_count() or 1) // world)
+        pool_n = max(1, HOST_CPUS // world)
         pool = mp.get_context("fork").Pool(pool_n)
 
     import torch
@@ -590,9 +624,10 @@ def main():
         first = [pa.reduce_batch(At_, bt_) for At_, bt_ in dev_batches]
         nlp_of = [int(v["nlp"].sum().item()) for v in first]
 
-        def region(nsteps):
+        def region(nsteps, keep_last=False):
             """barrier + synchronize | nsteps steps (+ the drain of the exchange) | synchronize + barrier; the wall time
-            is the max over ranks.  One HIP event pair sits around the launches on the stream they are issued on."""
+            is the max over ranks.  One HIP event pair sits around the launches on the stream they are issued on.
+            keep_last: also return the last step's results as host arrays (copied after the clock has stopped)."""
             nissued[0] = 0
             if ex is not None:
                 ex.k = 0
@@ -627,33 +662,51 @@ def main():
             assert int(res["nlp"].sum().item()) == nlp_of[(nsteps - 1) % NB]   # the last step's own output
             if multi:
                 assert gathered.numel() == world * G * nb
+            last = {k_: v_.cpu().numpy() for k_, v_ in res.items()} if keep_last else None
             return {"elapsed": el, "kern_ms": ev0.elapsed_time(ev1) / n_on_evs, "simplex": simplex, "steps": nsteps,
-                    "gathered": gathered}
+                    "gathered": gathered, "last": last}
 
-        for _ in range(args.warmup):
-            step()
-        if ex is not None:
-            drain()
-        cal = region(K)["elapsed"]
-        # (the calibration region is the first region of a mode and runs a few percent slower than the ones that follow: 15 % on top)
-        rep = max(1, int(-(-1.15 * args.min_region_ms * 1e-3 // cal))) if cal > 0 else 1
-        S = K * rep
-        regs = [region(S) for _ in range(max(1, args.regions))]
-        order = sorted(range(len(regs)), key=lambda i: regs[i]["elapsed"])
-        med = regs[order[len(order) // 2]]
-        lps_local = sum(nlp_of[k % NB] for k in range(S))
-        lps = int(allred(lps_local, torch.int64))
-        simplex = med["simplex"]
-        if simplex is not None:
-            simplex = int(allred(simplex, torch.int64))
-        return {"ex": ex, "first": first, "nlp_of": nlp_of, "S": S, "rep": rep, "regs": regs, "med": med, "lps": lps,
-                "lps_local": lps_local, "simplex": simplex, "B_LOCAL": B_LOCAL, "last_gathered": regs[-1]["gathered"],
-                "region_ms": [r_["elapsed"] * 1e3 for r_ in regs]}
+        def summary(regs, S):
+            order = sorted(range(len(regs)), key=lambda i: regs[i]["elapsed"])
+            med = regs[order[len(order) // 2]]
+            lps_local = sum(nlp_of[k % NB] for k in range(S))
+            lps = int(allred(lps_local, torch.int64))
+            simplex = med["simplex"]
+            if simplex is not None:
+                simplex = int(allred(simplex, torch.int64))
+            return {"S": S, "regs": regs, "med": med, "lps": lps, "lps_local": lps_local, "simplex": simplex,
+                    "last_gathered": regs[-1]["gathered"], "region_ms": [r_["elapsed"] * 1e3 for r_ in regs]}
+
+        t_warm = time.perf_counter()
+        nwarm = args.warmup
+        while True:
+            for _ in range(nwarm):
+                step()
+            if ex is not None:
+                drain()
+            torch.cuda.synchronize()
+            more = (time.perf_counter() - t_warm) * 1e3 < args.warmup_min_ms
+            if not allred(1 if more else 0, torch.int64, dist.ReduceOp.MAX if multi else None):   # every rank alike
+                break
+            nwarm = NB
+        # the headline: ONE region of exactly K steps
+        mode = summary([region(K, keep_last=args.dump_outputs is not None)], K)
+        mode.update(ex=ex, first=first, nlp_of=nlp_of, B_LOCAL=B_LOCAL, rep=1, repeated=None)
+        if args.full:
+            # `repeated`: the K steps repeated until a region lasts >= --min-region-ms, --regions regions, the median
+            # (the first region of a mode runs a few percent slower than the ones that follow: 15 % on top)
+            cal = mode["med"]["elapsed"]
+            rep = max(1, int(-(-1.15 * args.min_region_ms * 1e-3 // cal))) if cal > 0 else 1
+            S = K * rep
+            mode["repeated"] = summary([region(S) for _ in range(max(1, args.regions))], S)
+            mode["repeated"]["rep"] = rep
+            mode["last_gathered"] = mode["repeated"]["last_gathered"]
+        return mode
 
     def verify_exchange(mode, strong):
         # the last gathered group holds the slots of the steps of the (possibly partly filled) last group; rank q's part
         # must be what a reduce of rank q's batch of that step returns -- recomputed here, on this rank's GPU
-        ex, S = mode["ex"], mode["S"]
+        ex, S = mode["ex"], (mode["repeated"] or mode)["S"]   # the steps of the last region that ran
         gcpu = mode["last_gathered"].cpu()
         first = (S - 1) // G * G
         ok, nslots = True, 0
@@ -694,7 +747,7 @@ def main():
 
     # ---- the batches: NB distinct ones per mode, resident in HBM before any clock starts ---------------------------------
     want_weak = args.scaling == "weak"
-    want_strong = args.scaling == "strong" or (multi and want_weak)
+    want_strong = args.scaling == "strong" or (multi and want_weak and args.full)
     weak = strong = None
     host_batches = None
     if want_weak:
@@ -712,9 +765,17 @@ def main():
             host_batches = glob
         dev_s = [(torch.as_tensor(A_[lo:hi]).to(dev), torch.as_tensor(b_[lo:hi]).to(dev)) for A_, b_ in glob]
         strong = run_mode(dev_s, hi - lo)
-        strong["shard_alone_ms"] = shard_alone(dev_s)
+        strong["shard_alone_ms"] = shard_alone(dev_s) if args.full else None
     head = weak if want_weak else strong      # the mode `value` is quoted on
     A, b = host_batches[0]
+    if args.dump_outputs is not None and rank == 0:
+        # what the last timed step returned, for comparing two builds output for output: keep, flags, r, xc, nlp of
+        # (at most) 100 000 polytopes, 5.6 MB; float64 holds every value exactly (keep: a 16-bit row mask, flags / nlp:
+        # small integers)
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in head["med"]["last"].items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
 
     # ---- after the clocks: self-check of the collective layer, exchange verification, full-batch parity -------------------
     ranks_seen, exchange_ms = None, None
@@ -723,6 +784,7 @@ def main():
         if ranks_seen != world:   # a collective layer that does not see every rank measures something else: refuse the number
             raise SystemExit("bench.py: the all-reduce over the process group counted %d ranks, %d were launched (backend %s)"
                              % (ranks_seen, world, args.backend))
+    if multi and args.full:
         # what ONE exchange of a group costs on its own (all-gather of G x 24 B x polytopes per rank, nothing overlapping it)
         src = head["ex"].big[0]
         src = src.cpu() if args.backend == "gloo" else src
@@ -804,9 +866,9 @@ def main():
                                    "batches resident in HBM, one per step in rotation (%.0f MB > 256 MiB Infinity Cache)"
                                    % (B_PER_GPU, DIM, M_ROWS, NB, NB * B_PER_GPU * 8 * M_ROWS * (DIM + 1) / 1e6),
                        "lps_per_step": head["lps"] / S, "batches": NB, "polytopes_per_gpu": B_LOCAL, "streams": args.streams,
-                       "timing": "`--steps` K = %d; a timed region = K x %d = %d steps (>= %.0f ms), bracketed by barrier + "
-                                 "synchronize, max over ranks; %d regions, the line reports the median one"
-                                 % (K, head["rep"], S, args.min_region_ms, len(head["regs"])),
+                       "timing": "`--steps` K = %d: ONE timed region of exactly K steps after %d warm-up steps (continued "
+                                 "to >= %.0f ms), bracketed by barrier + synchronize, max over ranks"
+                                 % (K, args.warmup, args.warmup_min_ms),
                        "timed_steps_per_region": S, "regions": len(head["regs"]), "region_ms": head["region_ms"],
                        "lp_accounting": "`value` counts the LPs the reference issues on these polytopes (kernel output nlp, checked "
                                         "against the oracle's count); `lps_simplex_per_step` of them ran the simplex in the timed "
@@ -823,6 +885,16 @@ def main():
                          "note": "VALU-issue bound (valu_busy_frac_measured), not HBM bound: %.3g LP/s inside the kernel" % (
                              head["lps_local"] / S / (kern_ms * 1e-3))},
         }
+        def repeated_obj(mode):
+            r_ = mode["repeated"]
+            return {"what": "the K steps repeated until a region lasts >= %.0f ms (K x %d = %d steps), %d regions, the "
+                            "median one; not the headline" % (args.min_region_ms, r_["rep"], r_["S"], len(r_["regs"])),
+                    "value": r_["lps"] / r_["med"]["elapsed"], "unit": "LP/s", "ms_per_step": r_["med"]["elapsed"] / r_["S"] * 1e3,
+                    "lps_per_step": r_["lps"] / r_["S"], "kernel_ms": r_["med"]["kern_ms"], "timed_steps_per_region": r_["S"],
+                    "regions": len(r_["regs"]), "region_ms": r_["region_ms"]}
+
+        if head["repeated"] is not None:
+            line["repeated"] = repeated_obj(head)
         if parity is not None:
             line["parity_checked"] = parity["checked_all_ranks"]
             line["parity_ok"] = parity["ok_all_ranks"]
@@ -844,6 +916,8 @@ def main():
                     "polytopes_per_s": B_PER_GPU * strong["S"] / sm["elapsed"], "lps_per_step": strong["lps"] / strong["S"],
                     "timed_steps_per_region": strong["S"], "region_ms": strong["region_ms"],
                     "kernel_ms": sm["kern_ms"], "strong_floor": floor}
+            if strong["repeated"] is not None:
+                sobj["repeated"] = repeated_obj(strong)
             if want_weak:
                 line["strong"] = sobj
             line["config"]["strong_floor"] = floor
@@ -880,11 +954,11 @@ def main():
             line["pipelined"] = {"streams": 2, "value": head["lps_local"] / tp, "unit": "LP/s",
                                  "ms_per_step": tp / S * 1e3,
                                  "note": "two batches in flight; not the headline, see DESIGN.md section 6"}
-        if not multi and not args.no_end_to_end:
+        if args.full and not multi and not args.no_end_to_end:
             line["end_to_end"] = end_to_end(torch, pa, A, b, dev)
-        if not multi and not args.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline(A, b, head["first"][0]["nlp"].cpu().numpy())
-        if not multi and not args.no_secondary:
+        if args.full and not multi and not args.no_cpu_baseline:
+            line["cpu_baseline"] = cpu_baseline(A, b, head["first"][0]["nlp"].cpu().numpy(), 0, rank if want_weak else 0)
+        if args.full and not multi and not args.no_secondary:
             t_sec = time.perf_counter()
             line["secondary"] = secondary(torch, pa, dev)
             line["secondary"]["seconds"] = time.perf_counter() - t_sec

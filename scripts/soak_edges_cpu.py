@@ -2,7 +2,9 @@
 """CPU: EDGE inputs through the host layer against the reference itself (both on the scipy backend; build container only, the
 reference is imported in place): empty polytopes, half-spaces, slabs, flat (lower-dimensional) sets, open cones, tiny boxes,
 duplicated and zero rows, one-member and empty Regions -- every pair of a menu through the light operations; results (pieces in
-order, rows 1e-9, booleans, boxes) or the exception CLASS must agree.      python scripts/soak_edges_cpu.py [d ...]"""
+order, rows 1e-9, booleans, boxes) or the exception CLASS must agree.
+    python scripts/soak_edges_cpu.py [--record FILE | --against FILE] [d ...]
+The reference, --record and --against: as in scripts/soak_objects_cpu.py."""
 import itertools
 import os
 import sys
@@ -14,12 +16,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.dont_write_bytecode = True
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "scripts"))
-sys.path.insert(0, "/root/reference")
 import logging  # noqa: E402
 logging.disable(logging.CRITICAL)
-import polytope as ref  # noqa: E402
 import polytope_amd as mine  # noqa: E402
-from soak_objects_cpu import same  # noqa: E402
+from soak_objects_cpu import Reference, same  # noqa: E402
 
 
 def menu(d):
@@ -45,6 +45,7 @@ def menu(d):
 
 
 def main():
+    reference = Reference(sys.argv)
     dims = [int(a) for a in sys.argv[1:]] or [1, 2, 3]
     bad = nops = 0
     t0 = time.time()
@@ -88,14 +89,15 @@ def main():
         def run(what, fn, cmp, names):
             nonlocal bad, nops
             nops += 1
-            out = []
-            for mod in (ref, mine):
+
+            def outcome(mod):
                 args = [mod.Polytope(items[n][0].copy(), items[n][1].copy()) for n in names]
                 try:
                     np.random.seed(0)
-                    out.append(("ok", fn(mod, *args)))
+                    return ("ok", fn(mod, *args))
                 except Exception as e:
-                    out.append(("exc", type(e).__name__))
+                    return ("exc", type(e).__name__)
+            out = [reference.outcome("%d %s %s" % (d, what, "/".join(names)), outcome), outcome(mine)]
             err = None
             if out[0][0] != out[1][0] or (out[0][0] == "exc" and out[0][1] != out[1][1]):
                 err = "reference %s, package %s" % (out[0] if out[0][0] == "exc" else "ok", out[1] if out[1][0] == "exc" else "ok")
@@ -115,6 +117,7 @@ def main():
             for what, fn, cmp in ops2:
                 run(what, fn, cmp, [n1, n2])
         print("d=%d done: %d operations so far, %d differences, %.0f s" % (d, nops, bad, time.time() - t0), flush=True)
+    reference.save()
     print("EDGE SOAK (cpu, scipy backend on both sides) %s: %d operations, %d differences" % ("FAILED" if bad else "OK", nops, bad))
     return 1 if bad else 0
 

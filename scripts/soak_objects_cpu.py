@@ -3,7 +3,13 @@
 backend, in the build container only (/root/reference is imported in place; nothing of it is copied): random and structured
 polytope pairs / small regions in d = 1..4 through reduce, intersect, union(check_convex), mldivide, envelope, is_convex,
 is_adjacent, is_subset, ==, bounding_box, extreme, Region.intersect, Region diff, find_adjacent_regions -- same pieces in the
-same order, rows within 1e-9, booleans equal.    python scripts/soak_objects_cpu.py [trials] [seed]"""
+same order, rows within 1e-9, booleans equal.    python scripts/soak_objects_cpu.py [--record FILE | --against FILE] [trials] [seed]
+
+The reference is the package `polytope` as Python finds it, or the checkout that POLYTOPE_REFERENCE names.
+--record FILE also stores what the reference returned (gzip'd JSON); --against FILE compares with such a file instead
+of the reference, which then need not be there (tests/test_against_reference.py)."""
+import gzip
+import json
 import os
 import sys
 import time
@@ -13,18 +19,101 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.dont_write_bytecode = True
 sys.path.insert(0, ROOT)
-sys.path.insert(0, "/root/reference")
 import logging  # noqa: E402
 logging.disable(logging.CRITICAL)
-import polytope as ref  # noqa: E402  (the reference, read in place)
 import polytope_amd as mine  # noqa: E402
 assert mine.solvers.default_solver != "hip"
+ref = None   # the reference package, when it is run (Reference below)
+
+
+class Piece:
+    """A recorded piece of a result: what `same` reads of a Polytope."""
+    def __init__(self, A, b):
+        self.A, self.b = A, b
 
 
 def pieces(X):
-    if isinstance(X, (ref.Region, mine.Region)):
+    if isinstance(X, list):   # recorded
+        return X
+    if isinstance(X, mine.Region) or (ref is not None and isinstance(X, ref.Region)):
         return list(X.list_poly)
     return [X] if X.A.size else []
+
+
+def _arr(a):
+    a = np.asarray(a)
+    return {"array": a.tolist(), "shape": list(a.shape), "dtype": str(a.dtype)}
+
+
+def encode(v):
+    """A result of an operation as JSON (floats round-trip exactly)."""
+    if isinstance(v, (mine.Polytope, mine.Region)) or (ref is not None and isinstance(v, (ref.Polytope, ref.Region))):
+        return {"pieces": [[_arr(p.A), _arr(p.b)] for p in pieces(v)]}
+    if isinstance(v, np.ndarray):
+        return _arr(v)
+    if isinstance(v, (tuple, list)):
+        return [encode(u) for u in v]
+    if isinstance(v, (bool, np.bool_)):
+        return bool(v)
+    if isinstance(v, (int, np.integer)):
+        return int(v)
+    if isinstance(v, (float, np.floating)):
+        return float(v)
+    if v is None:
+        return None
+    raise TypeError("cannot record a %s" % type(v).__name__)
+
+
+def decode(v):
+    if isinstance(v, dict):
+        if "pieces" in v:
+            return [Piece(decode(A), decode(b)) for A, b in v["pieces"]]
+        return np.array(v["array"], dtype=v["dtype"]).reshape(v["shape"])
+    if isinstance(v, list):
+        return tuple(decode(u) for u in v)
+    return v
+
+
+class Reference:
+    """The reference side of a soak: the reference itself (recording what it returned with --record FILE), or the
+    outcomes such a file stored (--against FILE).  Takes its option out of argv."""
+
+    def __init__(self, argv):
+        global ref
+        self.mode, self.path, self.store = None, None, {}
+        for opt in ("--record", "--against"):
+            if opt in argv:
+                i = argv.index(opt)
+                self.mode, self.path = opt[2:], argv[i + 1]
+                del argv[i:i + 2]
+        self.args = argv[1:]
+        if self.mode == "against":
+            with gzip.open(self.path, "rt") as f:
+                rec = json.load(f)
+            if rec["args"] != self.args:
+                raise SystemExit("%s was recorded with the arguments %s, not %s" % (self.path, rec["args"], self.args))
+            self.store = rec["outcomes"]
+        else:
+            if os.environ.get("POLYTOPE_REFERENCE"):
+                sys.path.insert(0, os.environ["POLYTOPE_REFERENCE"])
+            import polytope
+            ref = polytope
+
+    def outcome(self, key, run):
+        """run(module) -> ("ok", value) or ("exc", exception class name)"""
+        if self.mode == "against":
+            kind, v = self.store[key]
+            return (kind, decode(v)) if kind == "ok" else (kind, v)
+        out = run(ref)
+        if self.mode == "record":
+            self.store[key] = [out[0], encode(out[1]) if out[0] == "ok" else out[1]]
+        return out
+
+    def save(self):
+        if self.mode == "record":
+            with gzip.GzipFile(self.path, "wb", mtime=0) as f:
+                f.write(json.dumps({"script": os.path.basename(sys.argv[0]), "args": self.args,
+                                    "outcomes": self.store}, sort_keys=True).encode())
 
 
 def same(X, Y, what, tol=1e-9):
@@ -56,6 +145,7 @@ def rand_poly(rng, d, kind):
 
 
 def main():
+    reference = Reference(sys.argv)
     trials = int(sys.argv[1]) if len(sys.argv) > 1 else 200
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
     rng = np.random.default_rng(seed)
@@ -80,17 +170,19 @@ def main():
         def both(fn, what, cmp=same):
             nonlocal nops
             nops += 1
-            out = []
-            for mod in (ref, mine):
+
+            def run(mod):
                 t1 = time.time()
                 P = [mod.Polytope(A.copy(), b.copy()) for A, b in data]
                 try:
                     np.random.seed(trial)
-                    out.append(("ok", fn(mod, P)))
+                    o = ("ok", fn(mod, P))
                 except Exception as e:   # the same exception class on both sides is parity too
-                    out.append(("exc", type(e).__name__))
+                    o = ("exc", type(e).__name__)
                 if only is not None:
                     print("   %-22s %-10s %.2f s" % (what, mod.__name__, time.time() - t1), flush=True)
+                return o
+            out = [reference.outcome("%d %s" % (trial, what), run), run(mine)]
             if out[0][0] != out[1][0]:
                 errs.append("%s: reference %s, package %s" % (what, out[0], out[1]))
             elif out[0][0] == "exc":
@@ -136,6 +228,7 @@ def main():
             print("trial %d  d %d %s:" % (trial, d, kinds), "; ".join(errs[:4]), flush=True)
         elif os.environ.get("SOAK_VERBOSE"):
             print("trial %d  d %d %s ok  %.0f s" % (trial, d, kinds, time.time() - t0), flush=True)
+    reference.save()
     print("OBJECT SOAK (cpu, scipy backend on both sides) %s: %d trials, %d operations, %d trials with a difference, %.0f s" % (
         "FAILED" if bad else "OK", trials, nops, bad, time.time() - t0), flush=True)
     return 1 if bad else 0

@@ -53,11 +53,11 @@ def _nlp_of(seed, stream):
 def test_bench_starts_its_own_ranks():
     """`python3 bench.py --gpus 2 ...` with NO launcher and no WORLD_SIZE in the environment (the form the driver
     uses): bench.py starts its two ranks itself (both on cuda:0, gloo, since the box has one GPU).  One line, from rank
-    0: weak figure as `value`, the partitioned batch as the object `strong`, both exchanges verified slot by slot, every
-    polytope of both ranks' batches checked against the oracle."""
+    0 (--full): weak figure as `value`, the partitioned batch as the object `strong`, both exchanges verified slot by
+    slot, every polytope of both ranks' batches checked against the oracle."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "20",
-           "--warmup", "5", "--verify-exchange", "--batches", "2"]
+           "--warmup", "5", "--full", "--verify-exchange", "--batches", "2"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -65,17 +65,21 @@ def test_bench_starts_its_own_ranks():
     line = json.loads(lines[0])
     assert line["n_gpus"] == 2 and line["scaling"] == "weak" and line["steps"] == 20 and line["warmup"] == 5
     cfg = line["config"]
-    assert cfg["rccl_ranks_seen"] == 2 and cfg["polytopes_per_gpu"] == 100000 and cfg["regions"] >= 5
+    assert cfg["rccl_ranks_seen"] == 2 and cfg["polytopes_per_gpu"] == 100000 and line["repeated"]["regions"] >= 5
+    assert cfg["timed_steps_per_region"] == 20 and cfg["exchange_ms_per_group"] > 0
     assert line["exchange_verified"]["ok"] is True and line["exchange_verified"]["ranks"] == 2
     assert line["exchange_verified"]["strong"]["ok"] is True
     assert line["parity_ok"] is True and line["parity_checked"] == 2 * 2 * 100000
-    S = cfg["timed_steps_per_region"]
-    assert S % 20 == 0 and min(cfg["region_ms"]) >= 0.8 * 50.0
-    want = sum(_rot_mean([_nlp_of(0, r), _nlp_of(1, r)], S) for r in range(2))
-    assert abs(cfg["lps_per_step"] - want) < 1e-6
+    nlp = {r: [_nlp_of(0, r), _nlp_of(1, r)] for r in range(2)}
+    assert abs(cfg["lps_per_step"] - sum(_rot_mean(nlp[r], 20) for r in range(2))) < 1e-6
+    S = line["repeated"]["timed_steps_per_region"]
+    assert S % 20 == 0 and min(line["repeated"]["region_ms"]) >= 0.8 * 50.0
+    want = sum(_rot_mean(nlp[r], S) for r in range(2))
+    assert abs(line["repeated"]["lps_per_step"] - want) < 1e-6
     st = line["strong"]
     assert st["strong_floor"]["shard_polytopes"] == 50000 and st["strong_floor"]["shard_kernel_ms_alone"] > 0
-    assert abs(st["lps_per_step"] - _rot_mean([_nlp_of(0, 0), _nlp_of(1, 0)], st["timed_steps_per_region"])) < 1e-6
+    assert abs(st["lps_per_step"] - _rot_mean(nlp[0], st["timed_steps_per_region"])) < 1e-6
+    assert abs(st["repeated"]["lps_per_step"] - _rot_mean(nlp[0], st["repeated"]["timed_steps_per_region"])) < 1e-6
     assert st["value"] > 0 and st["ms_per_step"] > 0
 
 
@@ -83,11 +87,14 @@ def test_bench_two_ranks_under_a_launcher_strong_only():
     """The launcher route (torch.distributed.run, as the contract describes it) with --scaling strong: `value` is the
     partitioned batch, the reassembled global batch is compared in batch order."""
     p = _torchrun(2, [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "9", "--warmup", "2", "--batches", "2",
-                      "--backend", "gloo", "--scaling", "strong", "--verify-exchange", "--no-parity"])
+                      "--backend", "gloo", "--scaling", "strong", "--full", "--verify-exchange", "--no-parity"])
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
     line = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["scaling"] == "strong" and line["steps"] == 9 and "strong" not in line
     assert line["exchange_verified"]["ok"] is True and line["exchange_verified"]["slots_checked"] >= 1
     assert line["config"]["polytopes_per_gpu"] == 50000 and line["config"]["strong_floor"]["shard_polytopes"] == 50000
-    S = line["config"]["timed_steps_per_region"]
-    assert abs(line["config"]["lps_per_step"] - _rot_mean([_nlp_of(0, 0), _nlp_of(1, 0)], S)) < 1e-6
+    nlp = [_nlp_of(0, 0), _nlp_of(1, 0)]
+    assert line["config"]["timed_steps_per_region"] == 9
+    assert abs(line["config"]["lps_per_step"] - _rot_mean(nlp, 9)) < 1e-6
+    S = line["repeated"]["timed_steps_per_region"]
+    assert abs(line["repeated"]["lps_per_step"] - _rot_mean(nlp, S)) < 1e-6

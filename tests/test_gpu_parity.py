@@ -1730,8 +1730,8 @@ def test_assign_full_config(pa, oracle):
 @pytest.mark.parametrize("scaling", ["weak", "strong"])
 def test_bench_force_dist_rccl_path(pa, scaling):
     """bench.py's N > 1 code path (process group on RCCL, exchange buffers, coalesced overlapped all-gather) driven
-    at world size 1 with --force-dist, in both scaling modes: the line must carry the contract's fields and the
-    LP count of the unsharded run."""
+    at world size 1 with --force-dist, in both scaling modes (--full: the repeated regions, the partitioned batch and
+    the full-batch parity too): the line must carry the contract's fields and the LP count of the unsharded run."""
     import json
     import os
     import socket
@@ -1743,7 +1743,7 @@ def test_bench_force_dist_rccl_path(pa, scaling):
     port = s.getsockname()[1]
     s.close()
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "9", "--warmup", "2", "--no-cpu-baseline",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "9", "--warmup", "2", "--full", "--no-cpu-baseline",
            "--no-end-to-end", "--force-dist", "--scaling", scaling, "--batches", "2"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
@@ -1757,8 +1757,10 @@ def test_bench_force_dist_rccl_path(pa, scaling):
     for i in range(2):
         A, b = random_hpolytopes(100000, 16, 3, seed=i, stream=0)
         n.append(int(pa.reduce_batch(torch.as_tensor(A).cuda(), torch.as_tensor(b).cuda())["nlp"].sum().item()))
-    S = line["config"]["timed_steps_per_region"]   # the 9 steps repeated until a region lasts 50 ms
-    assert S % 9 == 0 and abs(line["config"]["lps_per_step"] - sum(n[k % 2] for k in range(S)) / S) < 1e-6
+    assert line["config"]["timed_steps_per_region"] == 9 and line["config"]["regions"] == 1   # the headline: exactly 9 steps
+    assert abs(line["config"]["lps_per_step"] - sum(n[k % 2] for k in range(9)) / 9) < 1e-6
+    S = line["repeated"]["timed_steps_per_region"]   # the 9 steps repeated until a region lasts 50 ms
+    assert S % 9 == 0 and abs(line["repeated"]["lps_per_step"] - sum(n[k % 2] for k in range(S)) / S) < 1e-6
     assert line["parity_ok"] is True and line["parity_checked"] == 200000
     if scaling == "weak":   # the same run carries the partitioned batch as `strong` (at world size 1: the whole batch)
         assert line["strong"]["strong_floor"]["shard_polytopes"] == 100000 and line["strong"]["value"] > 1e9
