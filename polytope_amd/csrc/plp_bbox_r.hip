@@ -44,7 +44,7 @@ int launch_bbox(long long B, int m_max, int d, const double* A, const double* b,
                 double* ub, int* status, hipStream_t st, BoxHandover* ho) {
     if (ho) ho->mode = 0;
     if (m_max < 1 || m_max > MAX_M || B < 1) return 1;
-    // up to 32 rows in d <= 3: the 2 d box LPs one LP per lane (plp_reduce_lane.hip, bbox_lane_kernel); PLP_BBOX_LANE=0: never (A/B)
+    // up to 32 rows in d <= 3: the 2 d box LPs one LP per lane (bbox_lane_kernel, plp_bbox_lane.hip); PLP_BBOX_LANE=0: never (A/B)
     {
         const char* bl = getenv("PLP_BBOX_LANE");
         // (d = 4 through walk4, measured and not enabled: 20-30 % ahead of the lane-group kernels from 2 000 polytopes on --

@@ -764,7 +764,6 @@ int plp_reduce_batch_dev(plp_ctx* ctx, void* stream, int64_t B, int m_max, int d
     if (m_max > plp::MAX_M || d > plp::MAX_D)
         return fail(PLP_EUNSUPPORTED, "m_max=%d d=%d outside envelope (m<=64, d<=16)", m_max, d);
     hipStream_t st = (hipStream_t)stream;  // NULL = the HIP default stream
-    plp::t_reduce_ctr = ctx->reduce_ctr;
     if (!ctx->retry_ring) {
         if (hipMalloc(reinterpret_cast<void**>(&ctx->retry_ring), 64 * 8) == hipSuccess) {
             if (hipMemset(ctx->retry_ring, 0, 64 * 8) != hipSuccess) { (void)hipFree(ctx->retry_ring); ctx->retry_ring = nullptr; }
@@ -774,12 +773,10 @@ int plp_reduce_batch_dev(plp_ctx* ctx, void* stream, int64_t B, int m_max, int d
         (void)hipGetLastError();
     }
     ctx->reduce_epoch += 1;
-    plp::t_reduce_retry = ctx->retry_ring ? ctx->retry_ring + (ctx->reduce_epoch & 63ull) : nullptr;
-    plp::t_reduce_epoch = ctx->reduce_epoch;
-    const int lrc = plp::launch_reduce(B, m_max, d, A, b, m, abs_tol, reinterpret_cast<unsigned long long*>(keep), flags, r,
-                                       xc, nlp, st);
-    plp::t_reduce_ctr = nullptr;
-    plp::t_reduce_retry = nullptr;
+    const plp::ReduceArgs args{B, m_max, A, b, m, abs_tol, reinterpret_cast<unsigned long long*>(keep), flags, r, xc, nlp,
+                               ctx->reduce_ctr, ctx->retry_ring ? ctx->retry_ring + (ctx->reduce_epoch & 63ull) : nullptr,
+                               ctx->reduce_epoch};
+    const int lrc = plp::launch_reduce(d, args, 0, st);
     if (lrc) return fail(PLP_EUNSUPPORTED, "reduce kernel: unsupported size");
     return check_launch("reduce_kernel");
 }
@@ -838,6 +835,9 @@ int plp_reduce_batch(plp_ctx* ctx, int64_t B, int m_max, int d, const double* A,
                     &staged);
     if (rc) return rc;
     bool two_step = false;
+    // (the two-step path counts no simplex runs and uses no retry word: null counter and word)
+    const plp::ReduceArgs args{B, m_max, dA, db, m ? dm : nullptr, abs_tol, reinterpret_cast<unsigned long long*>(dkeep), dfl, dr,
+                               dxc, dnlp, nullptr, nullptr, 0ull};
     if (!staged) {
         rc = finite_or_fail(ctx, {{A, nA}, {b, nb}});
         if (rc) return rc;
@@ -847,8 +847,7 @@ int plp_reduce_batch(plp_ctx* ctx, int64_t B, int m_max, int d, const double* A,
         // when the flags, host-visible below anyway, ask for it (it is a launch that normally finds nothing to do)
         two_step = B <= 16384 && m_max <= plp::MAX_M && d <= plp::MAX_D;
         if (two_step) {
-            if (plp::launch_reduce_phase(B, m_max, d, dA, db, m ? dm : nullptr, abs_tol,
-                                         reinterpret_cast<unsigned long long*>(dkeep), dfl, dr, dxc, dnlp, st, 1))
+            if (plp::launch_reduce(d, args, 1, st))
                 return fail(PLP_EUNSUPPORTED, "reduce kernel: unsupported size");
             rc = check_launch("reduce_kernel");
         } else {
@@ -863,8 +862,7 @@ int plp_reduce_batch(plp_ctx* ctx, int64_t B, int m_max, int d, const double* A,
     bool again = false;
     for (int64_t k = 0; k < B && !again; ++k) again = (flags[k] & plp::RF_RETRY) != 0;
     if (!again) return PLP_OK;
-    if (plp::launch_reduce_phase(B, m_max, d, dA, db, m ? dm : nullptr, abs_tol, reinterpret_cast<unsigned long long*>(dkeep),
-                                 dfl, dr, dxc, dnlp, st, 2))
+    if (plp::launch_reduce(d, args, 2, st))
         return fail(PLP_EUNSUPPORTED, "reduce kernel: unsupported size");
     rc = check_launch("reduce_kernel");
     if (rc) return rc;

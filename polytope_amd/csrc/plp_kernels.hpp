@@ -99,24 +99,28 @@ int launch_adjacent_w(int n, int m_max, int d, const double* A, const double* b,
                       double thresh, unsigned char* adj, long long p_lo, long long p_hi, unsigned char* compact,
                       hipStream_t st, int cross_n1 = 0);
 
-// Device counter (or nullptr) the fused reduce kernels of the calling thread add their simplex-run count to: set by
-// plp_reduce_batch_dev from the context around the launch (plp_reduce_counters reads it back)
-extern thread_local unsigned long long* t_reduce_ctr;
-// Device word (or nullptr) and the value the fast kernels raise it to when they hand a polytope to the general kernel
-// (RF_RETRY): the second pass of launch_reduce leaves at once when the word does not hold the call's value
-extern thread_local unsigned long long* t_reduce_retry;
-extern thread_local unsigned long long t_reduce_epoch;
-
-int launch_reduce(long long B, int m_max, int d, const double* A, const double* b, const int* mrows,
-                  double abs_tol, unsigned long long* keep, int* flags, double* r, double* xc, int* nlp,
-                  hipStream_t st);
-int launch_reduce_phase(long long B, int m_max, int d, const double* A, const double* b, const int* mrows, double abs_tol,
-                        unsigned long long* keep, int* flags, double* r, double* xc, int* nlp, hipStream_t st, int phase);
-
-// four dictionary rows per lane (d <= 8); returns 1 when it does not apply
-int launch_reduce_r(long long B, int m_max, int d, const double* A, const double* b, const int* mrows,
-                    double abs_tol, unsigned long long* keep, int* flags, double* r, double* xc, int* nlp,
-                    hipStream_t st);
+// Fused reduce() of up to 64 rows (plp_reduce.hip).  The batch, the outputs, and what the fast kernels report besides:
+struct ReduceArgs {
+    long long B;
+    int m_max;
+    const double* A;
+    const double* b;
+    const int* mrows;
+    double abs_tol;
+    unsigned long long* keep;
+    int* flags;
+    double* r;
+    double* xc;
+    int* nlp;
+    unsigned long long* ctr;          // the context's counter of simplex runs (plp_reduce_counters), or nullptr
+    unsigned long long* retry_word;   // the call's word of the context's ring, or nullptr: the fast kernels raise it to
+    unsigned long long epoch;         // `epoch` when they hand a polytope back (RF_RETRY), and the second pass leaves at once
+                                      // when it does not hold that value
+};
+// phase 0: everything (the plan's first launch, then -- when the plan asks for it -- the general kernel's second pass that
+// redoes what the first flagged RF_RETRY);  phase 1: the first launch only -- the caller looks at the flags itself and asks
+// for phase 2 (that second pass) when it finds RF_RETRY.  Returns 0, or 2 for an unsupported size.
+int launch_reduce(int d, const ReduceArgs& a, int phase, hipStream_t st);
 
 // `scratch` (contains_scratch_bytes(P, m_max) bytes of device memory, or nullptr): the per-row thresholds of the
 // comparison form (plp_points.hip); without it the subtraction stays in the kernel

@@ -102,7 +102,7 @@ constexpr double LANE_PAIR_SIN2 = 1e-10;
 // RATIO(d0, d1, d2, x0, x1, x2, tolp, bs, bd, bi): the ratio test -- over the rows with a.d > tolp the one with the smallest
 // (beta_i - a_i.x)+ / a_i.d, the FIRST such row on ties; bs / bd its slack and a.d, bi its index (-1: none).  The caller
 // owns the loop: the host build and the plain device form walk all rows in one lane (ratio_rows below), the device
-// may split the rows of one LP over two or four lanes and combine (plp_reduce_lane.hip).
+// may split the rows of one LP over two or four lanes and combine (plp_reduce_lane.hpp).
 // ANY(pred): true while any lane of the wavefront still runs (device: __any; host: the predicate itself).
 // RATIO0(d0, d1, d2, tolp, bs, bd, bi): the same test from x' = 0, where every slack is its beta_i (the first pass of every
 // walk: no a_i.x to form; the values are the ones RATIO would find, bit for bit).

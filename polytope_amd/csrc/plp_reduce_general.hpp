@@ -1,6 +1,31 @@
-// plp_reduce_general.hpp -- one tile of the general fused reduce (one dictionary row per lane, Bland's rule inside the
-// simplex: plp_simplex.hpp): the body of reduce_kernel<D> (plp_reduce.hip), as a device function so that the fast kernels
-// can redo the polytopes they hand back (RF_RETRY) in place instead of leaving them to a second launch.
+// plp_reduce_general.hpp -- the general fused reduce, reduce_kernel<D>: one dictionary row per lane, Bland's rule inside
+// the simplex (plp_simplex.hpp).  It serves what no fast kernel takes and the second pass that redoes what they hand back
+// (RF_RETRY); its tile, reduce_general_tile, is a device function so that the fast kernels can also redo such polytopes
+// in place instead of leaving them to a second launch.
+//
+// Reference behaviour restated (polytope/polytope.py:1053-1163, `reduce`), per polytope:
+//   1. is_fulldim -> cheby_ball: LP F1, r > abs_tol                      (:1081, :962-985, :1241-1300)
+//   2. pairwise parallel-row dedupe on unit rows                          (:1094-1112)
+//   3. early return when neq <= nx+1                                      (:1114-1116)
+//   4. if neq > 3 nx: bounding box = 2 nx LPs F3, prefilter rows          (:1118-1134, :1367-1409)
+//   5. early return when neq <= nx+1                                      (:1136-1138)
+//   6. one redundancy LP F2 per remaining row k (h[k] += 0.1 ... -= 0.1)  (:1142-1160)
+// Output: 64-bit keep mask over the INPUT rows, flags, Chebyshev ball, number of LPs solved.
+//
+// Mapping: a 256-thread workgroup takes a tile of NG = 256/GS polytopes (GS lanes per group,
+// GS >= rows).  The tile's rows are read from HBM once, coalesced, into LDS.  Group p then runs
+// the whole pipeline of polytope p: lane i keeps row i (a_i, b_i) in VGPRs for the entire
+// sequence F1 -> dedupe -> 2d F3 -> prefilter -> one F2 per surviving row; the 64/GS groups of a
+// wavefront advance in lockstep, LP by LP.  The LPs of one polytope share everything but the
+// objective and one right-hand side entry, so setting one up is a handful of register moves:
+//   * F2/F3 start from the dictionary translated to the Chebyshev centre (b - A xc > 0), which is
+//     primal feasible: no phase 1;
+//   * the optimal value is read off the dictionary (zeta = -negz), not recomputed from x.
+// LDS is only read after the staging barrier (row k's coefficients = objective of F2(k), other
+// rows for the dedupe), so the groups never synchronise with each other.
+// HBM traffic = 8 m (d+1) bytes in + 24 + 8 d bytes out per polytope.
+//
+// reduce_general_tile:
 // NT = threads per workgroup; a tile = NT / gs polytopes (gs lanes per polytope, gs >= rows); smem_raw: at least
 // (NT / gs) * gs * (D + 1) doubles.  `mine`: my lane group's polytope takes part (others are left untouched).
 #pragma once
@@ -241,6 +266,60 @@ __device__ __forceinline__ void reduce_general_tile(unsigned char* smem_raw, con
 #pragma unroll
         for (int k = 0; k < D; ++k)
             if (i == (k & (gs - 1)) ) xc_out[pg * D + k] = ball ? xc[k] : qnan;
+    }
+}
+
+// Waves per SIMD the register allocator must leave room for (2nd __launch_bounds__ argument).
+// Measured on MI355X at d=3 (100k polytopes, m=16): 3 waves 0.820 ms, 4 waves 0.719 ms,
+// 5 waves 0.703 ms (24 VGPRs spilled outside the pivot loop), 6 waves 0.706 ms: the kernel is
+// VALU-issue bound from ~4 waves on, and the 5/6-wave builds pay for their spills with scratch
+// traffic (WRITE_SIZE 4.7 MB -> 132 MB per launch).  Larger d needs the registers more than the
+// occupancy.
+#ifndef PLP_REDUCE_WAVES
+#define PLP_REDUCE_WAVES(D) ((D) <= 4 ? 4 : ((D) <= 8 ? 3 : 2))
+#endif
+
+template <int D>
+__global__ __launch_bounds__(BLOCK, PLP_REDUCE_WAVES(D)) void reduce_kernel(long long B, int m_max, int gs,
+                                                       const double* __restrict__ Ag,
+                                                       const double* __restrict__ bg,
+                                                       const int* __restrict__ mrows, double abs_tol,
+                                                       int retry_only,
+                                                       unsigned long long* __restrict__ keep_out,
+                                                       int* __restrict__ flags_out,
+                                                       double* __restrict__ r_out,
+                                                       double* __restrict__ xc_out,
+                                                       int* __restrict__ nlp_out,
+                                                       const unsigned long long* __restrict__ retry_word,
+                                                       unsigned long long epoch) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    // second pass: the fast kernels raise the call's word when they hand a polytope back; normally they did not
+    // The word lives in a ring of 64 (slot = epoch & 63, raised with atomicMax): a value BELOW this call's epoch means no
+    // tile of this call asked for the second pass; this call's own epoch means some did; a LARGER value is a later call
+    // (64 or more calls of one context in flight on other streams) that took the slot over -- then nothing is known and
+    // the flags of the batch are swept as if the word were not there.
+    if (retry_only && retry_word && *retry_word < epoch) return;
+    const int NG = BLOCK / gs;
+    const int gib = threadIdx.x / gs;
+
+    if (retry_only) {
+        // normally nothing was handed back: all flag loads of this workgroup's tiles are issued at once (one
+        // memory round trip instead of one per tile of the sweep below) and the workgroup leaves
+        bool any = false;
+        for (long long tile = (long long)blockIdx.x * NG; tile < B; tile += (long long)gridDim.x * NG)
+            any = any | ((tile + gib < B) && (flags_out[tile + gib] & RF_RETRY) != 0);
+        if (!__syncthreads_or(any)) return;
+    }
+    for (long long tile = (long long)blockIdx.x * NG; tile < B; tile += (long long)gridDim.x * NG) {
+        const int ntile = (B - tile) < NG ? (int)(B - tile) : NG;
+        // second pass after reduce_r_kernel: only polytopes it flagged RF_RETRY (tiles without one are skipped)
+        bool mine = true;
+        if (retry_only) {
+            mine = (gib < ntile) && (flags_out[tile + gib] & RF_RETRY) != 0;
+            if (!__syncthreads_or(mine)) continue;
+        }
+        reduce_general_tile<D, BLOCK>(smem_raw, tile, ntile, mine, m_max, gs, Ag, bg, mrows, abs_tol, keep_out, flags_out, r_out,
+                                      xc_out, nlp_out);
     }
 }
 

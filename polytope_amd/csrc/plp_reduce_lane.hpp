@@ -1,4 +1,4 @@
-// plp_reduce_lane.hip -- reduce_lane_kernel<D>: the fused reduce() (polytope/polytope.py:1053-1163) for polytopes of up
+// plp_reduce_lane.hpp -- reduce_lane_kernel<D>: the fused reduce() (polytope/polytope.py:1053-1163) for polytopes of up
 // to 16 rows in d <= 3 -- BASELINE configs[1], the bench shape -- with the box LPs (F3, :1118-1134) and the redundancy
 // LPs the presolve leaves (F2, :1142-1160) solved ONE LP PER LANE (plp_lane_lp.hpp) instead of one LP per lane group.
 //
@@ -23,8 +23,7 @@
 //
 // An LP the lane engine hands back (ST_RETRY: a run of degenerate steps, dependent active rows) sends its polytope to the
 // general engine (plp_reduce_general.hpp, Bland's rule) at the end of the SAME tile: a step is one launch.
-#include <stdlib.h>
-
+#pragma once
 #include <type_traits>
 
 #include "plp_lane_lp.hpp"
@@ -36,16 +35,11 @@ namespace plp {
 #ifndef PLP_LANE_CH
 #define PLP_LANE_CH 4   // rows per trip of the ratio loop (the fewest rows a lane tests: 16 / 4 in quad mode)
 #endif
-#ifndef PLP_LANE_DEDUPE_SCREEN
-#define PLP_LANE_DEDUPE_SCREEN 1
-#endif
 
 constexpr int LN_ROWS = 16;   // row slots per polytope (ROWS = 32: polytopes of 17..32 rows, e.g. the stack of Polytope.intersect, ref :268-275)
 // GS lanes per polytope (4 / 8 / 16), R = 16 / GS rows per lane in the lane-group stages, NG = 64 / GS polytopes per tile
 // (= per wavefront).  GS = 4 is the throughput form; 8 and 16 put fewer polytopes on a wavefront and finish a tile in
 // about 0.6 / 0.4 of the time: the latency forms for batches that cannot fill the chip, and the tail of a large launch.
-
-static inline size_t reduce_lane_smem_bytes(int D, int GS, int ROWS = LN_ROWS) { return (size_t)(64 / GS) * ROWS * (D + 2) * 8; }
 
 // The polytopes of a tile that the fast path handed back (bit GS p of `rb64`: polytope p), redone by the general engine
 // (plp_reduce_general.hpp: one dictionary row per lane, 16 lanes per polytope, Bland's rule in the simplex).
@@ -237,9 +231,7 @@ __device__ __forceinline__ void reduce_lane_tile(
         for (int k = 0; k < R; ++k) live |= spread_rows<R, GS>(grp_ballot(((has >> k) & 1u) != 0u, g)) << k;
     } else {
         unsigned remmask = 0u;
-#if PLP_LANE_DEDUPE_SCREEN
         const double scr_thr = sqrt(2.0 * abs_tol) * 1.0001 + 1e-12;   // (wave-uniform)
-#endif
         double ni[R][D], bin_[R];
 #pragma unroll
         for (int k = 0; k < R; ++k) {
@@ -255,11 +247,9 @@ __device__ __forceinline__ void reduce_lane_tile(
                 const int i = row0 + k;
                 const int j = (i + t) & (rows - 1);
                 const double an_j = LN(j);
-#if PLP_LANE_DEDUPE_SCREEN
                 // unit rows with dot > 1 - tol differ by less than sqrt(2 tol) in every component: when no pair of the
                 // wavefront passes that test on the first component (random rows: never) the pair is skipped
                 if (!__any(fabs(ni[k][0] - LA(j, 0) * an_j) < scr_thr)) continue;
-#endif
                 double dot = 0.0;
 #pragma unroll
                 for (int kk = 0; kk < D; ++kk) dot = dot + ni[k][kk] * (LA(j, kk) * an_j);
@@ -708,132 +698,6 @@ __global__ __launch_bounds__(RBLOCK, PLP_REDUCE_LANE_WAVES(D)) void bbox_lane_ke
     // (BBOX: the tile's keep_out argument carries the verifier's buffer of final points, [B][2 D][D] doubles or nullptr)
     reduce_lane_tile<D, GS, ROWS, true>((long long)blockIdx.x * (64 / GS), B, m_max, Ag, bg, mrows, 0.0, force_retry,
                                         reinterpret_cast<unsigned long long*>(xfin), status, lb, ub, nullptr, nullptr);
-}
-
-// Tile shape by batch size, measured on (16,3) batches (scripts/debug/lane_sweep.py, us per launch GS 4 / 8 / 16):
-//   B = 3 000: 51 / 35 / 27.5    8 000: 56 / 38 / 34    12 000: 58 / 46 / 41    16 000: 58 / 47 / 49    20 000: 66 / 56 / 62
-//   30 000: 71 / 69 / 81    40 000: 89 / 88 / 101    (lane-group kernels: 40 / 48 / 60 / 62 / 75 / 91 / 106)
-#ifndef PLP_REDUCE_LANE32_GS16_MAXB
-#define PLP_REDUCE_LANE32_GS16_MAXB 16000  // 17..32 rows: batches up to this size on 4 polytopes per wavefront
-#endif
-#ifndef PLP_REDUCE_LANE_GS8_MAXB
-#define PLP_REDUCE_LANE_GS8_MAXB 40000   // batches up to this size: 8 polytopes per wavefront
-#endif
-#ifndef PLP_REDUCE_LANE_GS16_MAXB
-#define PLP_REDUCE_LANE_GS16_MAXB 14000  // ... up to this size: 4 polytopes per wavefront
-#endif
-// Larger batches: 16 polytopes per wavefront, the LAST eighth of the tiles (at most 1024) as 8-polytope tiles.  The
-// workgroups of a launch are handed out over tens of microseconds and the launch ends when the ones that started last
-// end: short tiles there cut 12 us off 50 000 .. 100 000 polytopes (100 000: 166 us without, 153-155 with 2/64 .. 8/64 of
-// the tiles, 159-172 beyond 12/64; 50 000: 104 -> 91).  PLP_REDUCE_LANE_MIX=k: k / 64 of the tiles (0: none).
-
-template <int D>
-static int launch_reduce_lane_d(long long B, int m_max, const double* A, const double* b, const int* mrows, double abs_tol,
-                                unsigned long long* keep, int* flags, double* r, double* xc, int* nlp, hipStream_t st) {
-    if (B > 2147483647ll) return 2;
-    const char* fr = getenv("PLP_REDUCE_RETRY_ALL");
-    const int force = (fr && fr[0] == '1') ? 1 : 0;
-    const char* eg = getenv("PLP_REDUCE_LANE_GS");   // 4 / 8 / 16: that tile shape whatever the batch size (A/B)
-    if (m_max > LN_ROWS) {
-        // 17..32 rows: 32 row slots per polytope, 8 polytopes per wavefront (four rows per lane) or 4 (two rows per lane)
-        int gs32 = B <= PLP_REDUCE_LANE32_GS16_MAXB ? 16 : 8;
-        if (eg) gs32 = atoi(eg) == 16 ? 16 : 8;
-        const long long ng32 = 64 / gs32;
-        long long blocks32 = (B + ng32 - 1) / ng32;
-        if (blocks32 < 1) blocks32 = 1;
-        const char* mx32 = getenv("PLP_REDUCE_LANE_MIX");
-        long long tail32 = blocks32 / 8 < 1024 ? blocks32 / 8 : 1024;
-        if (mx32) tail32 = blocks32 * atoi(mx32) / 64;
-        if (eg || D == 4) tail32 = 0;   // (d = 4: the short tiles do not pay at 32 row slots, (20,4) x 50 000: 315 us with, 300 without)
-        if (gs32 == 16)
-            hipLaunchKernelGGL((reduce_lane_kernel<D, 16, 32>), dim3((unsigned)blocks32), dim3(RBLOCK), reduce_lane_smem_bytes(D, 16, 32),
-                               st, B, m_max, A, b, mrows, abs_tol, force, keep, flags, r, xc, nlp, t_reduce_ctr);
-        else if (tail32 > 0 && blocks32 > 512) {
-            const long long nbig = blocks32 - tail32;
-            const long long nsmall = (B - nbig * 8 + 3) / 4;
-            hipLaunchKernelGGL((reduce_lane_mix_kernel<D, 32, 8, 16>), dim3((unsigned)(nbig + nsmall)), dim3(RBLOCK),
-                               reduce_lane_smem_bytes(D, 8, 32), st, (int)nbig, B, m_max, A, b, mrows, abs_tol, force, keep, flags, r,
-                               xc, nlp, t_reduce_ctr);
-        } else
-            hipLaunchKernelGGL((reduce_lane_kernel<D, 8, 32>), dim3((unsigned)blocks32), dim3(RBLOCK), reduce_lane_smem_bytes(D, 8, 32),
-                               st, B, m_max, A, b, mrows, abs_tol, force, keep, flags, r, xc, nlp, t_reduce_ctr);
-        return 3;
-    }
-    int gs = B <= PLP_REDUCE_LANE_GS16_MAXB ? 16 : (B <= PLP_REDUCE_LANE_GS8_MAXB ? 8 : 4);
-    if (eg) gs = atoi(eg) == 16 ? 16 : (atoi(eg) == 8 ? 8 : 4);
-    const long long ng = 64 / gs;
-    long long blocks = (B + ng - 1) / ng;
-    if (blocks < 1) blocks = 1;
-    if (gs == 16) {
-        hipLaunchKernelGGL((reduce_lane_kernel<D, 16>), dim3((unsigned)blocks), dim3(RBLOCK), reduce_lane_smem_bytes(D, 16), st, B,
-                           m_max, A, b, mrows, abs_tol, force, keep, flags, r, xc, nlp, t_reduce_ctr);
-    } else if (gs == 8) {
-        hipLaunchKernelGGL((reduce_lane_kernel<D, 8>), dim3((unsigned)blocks), dim3(RBLOCK), reduce_lane_smem_bytes(D, 8), st, B,
-                           m_max, A, b, mrows, abs_tol, force, keep, flags, r, xc, nlp, t_reduce_ctr);
-    } else {
-        const char* mx = getenv("PLP_REDUCE_LANE_MIX");
-        long long tail_tiles = blocks / 8 < 1024 ? blocks / 8 : 1024;
-        if (mx) tail_tiles = blocks * atoi(mx) / 64;
-        if (eg) tail_tiles = 0;   // (a forced shape is that shape only)
-        if (tail_tiles > 0 && blocks > 512) {
-            const long long nbig = blocks - tail_tiles;
-            const long long rest = B - nbig * 16;
-            const long long nsmall = (rest + 7) / 8;
-            hipLaunchKernelGGL((reduce_lane_mix_kernel<D, LN_ROWS, 4, 8>), dim3((unsigned)(nbig + nsmall)), dim3(RBLOCK),
-                               reduce_lane_smem_bytes(D, 4), st, (int)nbig, B, m_max, A, b, mrows, abs_tol, force, keep, flags, r,
-                               xc, nlp, t_reduce_ctr);
-        } else {
-            hipLaunchKernelGGL((reduce_lane_kernel<D, 4>), dim3((unsigned)blocks), dim3(RBLOCK), reduce_lane_smem_bytes(D, 4), st,
-                               B, m_max, A, b, mrows, abs_tol, force, keep, flags, r, xc, nlp, t_reduce_ctr);
-        }
-    }
-    return 3;   // complete: what the fast path hands back is redone inside the kernel, no second pass
-}
-
-template <int D>
-static int launch_bbox_lane_d(long long B, int m_max, const double* A, const double* b, const int* mrows, double* lb, double* ub,
-                              int* status, hipStream_t st, double* xfin) {
-    if (B > 2147483647ll) return 1;
-    const int force = 0;   // (nothing to force: what this kernel does not settle goes back to the caller as status 1)
-    const bool wide = m_max > LN_ROWS;
-    int gs = wide ? (B <= PLP_REDUCE_LANE32_GS16_MAXB ? 16 : 8) : (B <= PLP_REDUCE_LANE_GS16_MAXB ? 16 : (B <= PLP_REDUCE_LANE_GS8_MAXB ? 8 : 4));
-    const long long ng = 64 / gs;
-    long long blocks = (B + ng - 1) / ng;
-    if (blocks < 1) blocks = 1;
-#define PLP_BBL(GSV, RV)                                                                                                     \
-    hipLaunchKernelGGL((bbox_lane_kernel<D, GSV, RV>), dim3((unsigned)blocks), dim3(RBLOCK), reduce_lane_smem_bytes(D, GSV, RV), st, B, \
-                       m_max, A, b, mrows, force, lb, ub, status, xfin)
-    if (wide) { if (gs == 16) PLP_BBL(16, 32); else PLP_BBL(8, 32); }
-    else if (gs == 16) PLP_BBL(16, 16);
-    else if (gs == 8) PLP_BBL(8, 16);
-    else PLP_BBL(4, 16);
-#undef PLP_BBL
-    return 0;
-}
-
-// bounding boxes of polytopes with up to 32 rows in d <= 3 (the contract of launch_bbox); 0 when launched, 1 when not taken
-int launch_bbox_lane(long long B, int m_max, int d, const double* A, const double* b, const int* mrows, double* lb, double* ub,
-                     int* status, hipStream_t st, double* xfin) {
-    if (m_max < 1 || m_max > 2 * LN_ROWS) return 1;
-    switch (d) {
-        case 1: return launch_bbox_lane_d<1>(B, m_max, A, b, mrows, lb, ub, status, st, xfin);
-        case 2: return launch_bbox_lane_d<2>(B, m_max, A, b, mrows, lb, ub, status, st, xfin);
-        case 3: return launch_bbox_lane_d<3>(B, m_max, A, b, mrows, lb, ub, status, st, xfin);
-        default: return 1;
-    }
-}
-
-// returns 3 when launched (complete: launch_reduce adds no second pass), 1 when this kernel does not take the shape
-int launch_reduce_lane(long long B, int m_max, int d, const double* A, const double* b, const int* mrows, double abs_tol,
-                       unsigned long long* keep, int* flags, double* r, double* xc, int* nlp, hipStream_t st) {
-    if (m_max < 1 || m_max > 2 * LN_ROWS) return 1;
-    switch (d) {
-        case 1: return launch_reduce_lane_d<1>(B, m_max, A, b, mrows, abs_tol, keep, flags, r, xc, nlp, st);
-        case 2: return launch_reduce_lane_d<2>(B, m_max, A, b, mrows, abs_tol, keep, flags, r, xc, nlp, st);
-        case 3: return launch_reduce_lane_d<3>(B, m_max, A, b, mrows, abs_tol, keep, flags, r, xc, nlp, st);
-        case 4: return launch_reduce_lane_d<4>(B, m_max, A, b, mrows, abs_tol, keep, flags, r, xc, nlp, st);
-        default: return 1;
-    }
 }
 
 }  // namespace plp

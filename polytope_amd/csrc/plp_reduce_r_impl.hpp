@@ -1,5 +1,5 @@
-// plp_reduce_r_impl.hpp -- reduce_r_kernel<D,GS,R> and its launcher (included by plp_reduce_r.hip, d <= 8, and
-// plp_reduce_r2a/b.hip, d = 9..16): fused reduce() (polytope/polytope.py:1053-1163) with R = 4 rows per lane.
+// plp_reduce_r_impl.hpp -- reduce_r_kernel<D,GS,R> and the other lane-group and one-polytope-per-wavefront kernels
+// (launched by plp_reduce_launch.hpp, as plp_reduce_plan.hpp decides): fused reduce() (polytope/polytope.py:1053-1163) with R = 4 rows per lane.
 //
 // Same pipeline and the same reference steps as plp_reduce.hip (F1 -> dedupe -> 2d F3 -> prefilter
 // -> one F2 per surviving row, all LPs of a polytope solved by one lane group out of registers),
@@ -14,6 +14,7 @@
 #include "plp_kernels.hpp"
 #include "plp_simplex_r.hpp"
 #include "plp_lazy.hpp"
+#include "plp_reduce_plan.hpp"
 
 namespace plp {
 
@@ -27,29 +28,8 @@ __device__ __forceinline__ int stat_wave_max(int v) {
 #define PLP_STAT_ADD(i, v) atomicAdd(&plp_stage_stats[i], (unsigned long long)(v))
 #endif
 
-constexpr int RR = 4;  // rows per lane (default; R8 variant: 8 rows per lane, groups of 2 lanes for m <= 16)
+constexpr int RR = 4;  // rows per lane (default)
 
-#ifndef PLP_REDUCE_R_BLOCK
-// One wavefront per workgroup: at C2 (100000 polytopes = 6250 wavefronts over 4096 resident slots) the last
-// round is spread over the CUs wave by wave instead of in blocks of four (measured 256: 0.306 ms, 128: 0.305,
-// 64: 0.299), and the workgroup barriers cost nothing.
-#define PLP_REDUCE_R_BLOCK 64
-#endif
-constexpr int RBLOCK = PLP_REDUCE_R_BLOCK;  // threads per workgroup
-
-static inline int group_size_r(int m_max) {
-    if (m_max <= 16) return 4;
-    if (m_max <= 32) return 8;
-    return 16;
-}
-
-// (bench shape: 16 polytopes x 16 rows x 5 doubles = 10 240 B per one-wavefront workgroup, and 16 of them -- four waves per
-// SIMD -- are EXACTLY the CU's 160 KB: 384 B more per workgroup (the centres kept in LDS, tried in round 4 against the
-// spills) and a CU holds 15, 0.194 -> 0.213 ms)
-static inline size_t reduce_r_smem_bytes(int gs, int D, int R) {
-    const int NG = RBLOCK / gs;
-    return ((size_t)NG * gs * R * (D + 2) * 8 + 15) & ~(size_t)15;  // A rows, b, 1/||a||
-}
 
 // bit l of x (l < 16)  ->  bit 4l
 __device__ __forceinline__ uint64_t spread4(uint64_t x) {
@@ -96,37 +76,7 @@ __device__ __forceinline__ void ctr_add(unsigned long long* ctr, int v, bool lea
 #endif
 
 #ifndef PLP_REDUCE_R2MID_WAVES
-#define PLP_REDUCE_R2MID_WAVES 3  // d = 5..8 on two rows per lane (plp_reduce_r2c.hip)
-#endif
-
-#ifndef PLP_R_ASYNC
-#define PLP_R_ASYNC 1  // F2: every lane group walks its own LP list inside one pivot loop (0: lock-step, for A/B runs)
-#endif
-
-#ifndef PLP_R_POOL
-#define PLP_R_POOL 1  // F2: the LPs the presolve left form one list per tile, any lane group takes the next (0: every group its own rows)
-#endif
-
-#ifndef PLP_R_FAST
-#define PLP_R_FAST 1  // F2/F3 on SimplexR::run_fast (0: the general step(), for A/B runs)
-#endif
-
-#ifndef PLP_REDUCE_R8_MAXD
-// m <= 16 and d <= this: 8 rows per lane, two lanes per polytope (32 polytopes per wavefront).  Measured at C2:
-// 22 % fewer VALU instructions per polytope but 228 VGPRs = 2 waves per SIMD, and the kernel is then bound by the
-// latency of the pivot's dependency chain: 0.344 ms against 0.297 ms (at 3 waves it spills: 0.444 ms).  Off.
-#define PLP_REDUCE_R8_MAXD 0
-#endif
-#ifndef PLP_REDUCE_R8_WAVES
-#define PLP_REDUCE_R8_WAVES 2
-#endif
-
-#ifndef PLP_R_DEDUPE_HALF
-#define PLP_R_DEDUPE_HALF 1  // 16 rows at four per lane: every pair of rows once (0: every lane all 16 partners of its rows)
-#endif
-
-#ifndef PLP_R_PRESOLVE
-#define PLP_R_PRESOLVE 2  // F2: rows answered by the presolve below skip the simplex (0: every LP on the simplex; 1: first witness only; A/B runs)
+#define PLP_REDUCE_R2MID_WAVES 3  // d = 5..8 on two rows per lane
 #endif
 
 // F2 presolve ("ray certificate").  The redundancy LP of row k (:1142-1160) is
@@ -148,7 +98,7 @@ __device__ __forceinline__ void ctr_add(unsigned long long* ctr, int v, bool lea
 // Rows zeroed in LDS (never present, removed by the dedupe or the prefilter) pass every test: 0 <= 0.
 // Returns my rows' bits (bit k: row row0 + k is settled as "keep").
 // LS: distance (in doubles) between consecutive elements of the three arrays (1: a polytope's rows are contiguous;
-// 16: the polytope-interleaved tile of plp_reduce_lane.hip)
+// 16: the polytope-interleaved tile of plp_reduce_lane.hpp)
 // BETA: the third array holds the slacks  beta_i = max(b_i - a_i.xc, 0)  themselves instead of s_i = a_i.xc
 template <int D, int R, int LS = 1, bool BETA = false>
 __device__ __forceinline__ unsigned f2_presolve(const double* myA, double* myb, const double* myan, int row0, int m_loop,
@@ -188,7 +138,6 @@ __device__ __forceinline__ unsigned f2_presolve(const double* myA, double* myb, 
             jb[k] = fine ? jb[k] : i;
         }
     }
-#if PLP_R_PRESOLVE >= 2
     // Second witness for the candidates whose ray is blocked (the foot point of xc on row k's plane lies outside the
     // facet): up to the blocking row j, then along its plane in the direction of a_k projected onto it,
     //     x* = xc + t1 a_k + t2 d,   t1 = s_j / (a_j.a_k) (a hair less),   d = a_k - rho a_j,  rho = a_j.a_k / |a_j|^2,
@@ -265,7 +214,6 @@ __device__ __forceinline__ unsigned f2_presolve(const double* myA, double* myb, 
         }
     }
     ok |= ok2;
-#endif
 #pragma unroll
     for (int k = 0; k < R; ++k)
         if ((ok >> k) & 1u) myb[(row0 + k) * LS] = (myb[(row0 + k) * LS] + 0.1) - 0.1;  // (:1149-1151), see above
@@ -292,8 +240,8 @@ __device__ __forceinline__ void reduce_r_tile(
     int* __restrict__ nlp_out, unsigned long long* __restrict__ ctr, unsigned long long* __restrict__ retry_word,
     unsigned long long epoch) {
     constexpr unsigned RMASK = (1u << R) - 1u;
-    constexpr int RSH = R == 8 ? 3 : (R == 4 ? 2 : (R == 2 ? 1 : 0));  // log2(R)
-    static_assert(R == 1 || R == 2 || R == 4 || R == 8, "rows per lane");
+    constexpr int RSH = R == 4 ? 2 : (R == 2 ? 1 : 0);  // log2(R)
+    static_assert(R == 1 || R == 2 || R == 4, "rows per lane");
     static_assert(!LAZY || (GS == 64 && R == 1 && RBLOCK == 64), "lazy LPs: one polytope per wavefront and workgroup");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     constexpr int gs = GS;
@@ -404,12 +352,8 @@ __device__ __forceinline__ void reduce_r_tile(
             f1open = valid & (st1 != ST_OPT) & (st1 != ST_INFEAS);   // (RF_F1OPEN, plp_common.hpp)
         } else
         {
-#if PLP_R_FAST
             SimplexR<D + 1, R, false, true> S;  // forced first pivot handed to run_fast
             double qi[R];
-#else
-            SimplexR<D + 1, R, true> S;
-#endif
             S.reset(D + 1, m, row0);
             unsigned actb = 0u;
             bool inf0 = false, finite = true;
@@ -433,11 +377,7 @@ __device__ __forceinline__ void reduce_r_tile(
                 const bool on = h & !zero;
                 S.T[k][D] = on ? nrm : 0.0;
                 S.beta[k] = on ? bk : 0.0;
-#if PLP_R_FAST
                 qi[k] = bk / nrm;
-#else
-                S.init_q[k] = bk / nrm;
-#endif
                 actb |= on ? (1u << k) : 0u;
                 inf0 = inf0 | (h & zero & (bk < -TOL_FEAS));
             }
@@ -445,17 +385,9 @@ __device__ __forceinline__ void reduce_r_tile(
             const bool infeasible0 = grp_ballot(inf0, g) != 0;
             const bool bad = (grp_ballot(!finite, g) != 0) | (m > rows);
             S.cost[D] = -1.0;
-#if PLP_R_FAST
             S.mode = M_P2;
-#else
-            S.init_elig = actb;
-            S.mode = M_INIT;
-            S.init_col = D;
-            S.mode_after_init = M_P2;
-#endif
             if (!valid | bad) { S.mode = M_DONE; S.status = ST_NUM; }
             else if (infeasible0) { S.mode = M_DONE; S.status = ST_INFEAS; }
-#if PLP_R_FAST
             S.template run_fast<GS, true>(g, qi, actb);
             retry = retry | (valid & (S.status == ST_RETRY));
 #ifdef PLP_STAGE_STATS
@@ -464,9 +396,6 @@ __device__ __forceinline__ void reduce_r_tile(
                 if (threadIdx.x == 0) { PLP_STAT_ADD(0, 1); PLP_STAT_ADD(1, wm); }
                 if (valid & (g.gl == 0)) { PLP_STAT_ADD(2, S.iters); PLP_STAT_ADD(11, 1); }
             }
-#endif
-#else
-            S.run(g);
 #endif
             const bool ok = S.status == ST_OPT;
             f1open = valid & !ok & (S.status != ST_INFEAS);   // (RF_F1OPEN, plp_common.hpp)
@@ -491,7 +420,7 @@ __device__ __forceinline__ void reduce_r_tile(
         __syncthreads();  // 1/||a|| of every row is in LDS
         // ---------------------------------------------------------------- dedupe (:1094-1110)
         // (rows are re-read from LDS: the register file limits the occupancy of this kernel, LDS is idle)
-        if constexpr (!SPLIT && !LAZY && rows == 16 && R == 4 && PLP_R_DEDUPE_HALF) {
+        if constexpr (!SPLIT && !LAZY && rows == 16 && R == 4) {
             // Sixteen row slots, four per lane: every unordered pair {i, j} once instead of twice.  Row i meets its partners
             // j = i + 1 .. i + 8 (mod 16): the 8 cyclic distances cover all 120 pairs (distance 8 twice: harmless), the
             // dot product is the same number whichever of the two rows' owners forms it (products commute, same order
@@ -717,7 +646,6 @@ __device__ __forceinline__ void reduce_r_tile(
                 }
                 S_.ract = lloc;
                 S_.mode = go ? M_P2 : M_DONE;
-#if PLP_R_FAST
                 S_.template run_fast<GS>(g);
                 retry = retry | (go & (S_.status == ST_RETRY));
 #ifdef PLP_STAGE_STATS
@@ -726,9 +654,6 @@ __device__ __forceinline__ void reduce_r_tile(
                     if (threadIdx.x == 0) { PLP_STAT_ADD(3, wm); PLP_STAT_ADD(10, 1); }
                     if (go & (g.gl == 0)) { PLP_STAT_ADD(4, S_.iters); PLP_STAT_ADD(5, 1); }
                 }
-#endif
-#else
-                S_.run(g);
 #endif
                 S.status = S_.status;
                 S.negz = S_.negz;
@@ -849,7 +774,6 @@ __device__ __forceinline__ void reduce_r_tile(
                 uint64_t todo = ((uint64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(live >> 32)) << 32) |
                                 (uint64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)live);
                 nlp += __popcll(live);
-#if PLP_R_PRESOLVE
                 {   // rows the presolve settles as "keep" need no LP (lane i = row i: the ballot is the row mask)
                     const uint64_t cert = __ballot((f2_presolve<D, 1>(myA, myb, myan, row0, m_max, lloc & 1u, abs_tol) & 1u) != 0u);
                     keep |= cert;
@@ -857,7 +781,6 @@ __device__ __forceinline__ void reduce_r_tile(
                     todo &= ~(((uint64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(cert >> 32)) << 32) |
                               (uint64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)cert));
                 }
-#endif
                 while (todo != 0ull) {
                     const int kr = __ffsll((long long)todo) - 1;
                     todo &= todo - 1ull;
@@ -885,7 +808,6 @@ __device__ __forceinline__ void reduce_r_tile(
                 flags |= RF_MINREP;
             }
         } else {
-#if PLP_R_ASYNC && PLP_R_FAST
         // The 16 polytopes of a wavefront need different numbers of LPs (rows that survived the dedupe and
         // the prefilter) and their LPs different numbers of pivots; in lock-step every LP costs the wave the
         // maximum over its polytopes (measured: 3.9 pivots against a mean of 2.3).  Here every group walks its
@@ -895,7 +817,6 @@ __device__ __forceinline__ void reduce_r_tile(
             const unsigned lloc = ((unsigned)(live >> row0) & RMASK);
             uint64_t todo = (stage == 2) ? live : 0ull;
             if (stage == 2) nlp += __popcll(live);
-#if PLP_R_PRESOLVE
             {   // rows the ray presolve settles as "keep" need no simplex run
                 const unsigned okb = f2_presolve<D, R>(myA, myb, myan, row0, m_max, (stage == 2) ? lloc : 0u, abs_tol);
                 uint64_t cert = 0ull;
@@ -905,7 +826,6 @@ __device__ __forceinline__ void reduce_r_tile(
                 todo &= ~cert;
                 ctr_add(ctr, -__popcll(cert), g.gl == 0);
             }
-#endif
             SimplexR<D, R, false, false> S;
             S.reset(D, __popcll(live), row0);
             S.mode = M_DONE;
@@ -913,8 +833,7 @@ __device__ __forceinline__ void reduce_r_tile(
             bool busy = false;
             int kr = 0, e = -1, chi = 0;
             double cxc = 0.0, best = 0.0;
-#if PLP_R_POOL
-            if constexpr (rows <= 32 && PLP_R_PRESOLVE) {
+            if constexpr (rows <= 32) {
                 // ---- pooled: the LPs the presolve left are few (2.1 per polytope at C2) and unevenly spread -- with every
                 // group on its own list the wavefront waits for the group with most left (15.9 iterations for a mean of
                 // 6.6 pivots).  Here the LPs of all polytopes of the tile form ONE list (polytope order, then row order)
@@ -1046,7 +965,6 @@ __device__ __forceinline__ void reduce_r_tile(
                 }
                 retry = retry | (__any(pool_retry) != 0);   // (rare: the whole tile is redone by the general kernel)
             } else
-#endif
             for (;;) {
                 const bool fin = busy & (S.mode == M_DONE);
                 const bool start = (fin | !busy) & (todo != 0ull);
@@ -1101,56 +1019,6 @@ __device__ __forceinline__ void reduce_r_tile(
             }
             if (stage == 2) flags |= RF_MINREP;
         }
-#else
-        if (__any(stage == 2)) {
-            const unsigned lloc = ((unsigned)(live >> row0) & RMASK);
-            uint64_t todo = (stage == 2) ? live : 0ull;
-            if (stage == 2) nlp += __popcll(live);
-            while (__any(todo != 0ull)) {
-                const bool go = todo != 0ull;
-                const int kr = go ? __ffsll((long long)todo) - 1 : 0;
-                todo &= todo - 1ull;
-                SimplexR<D, R, false, false> S;
-                S.reset(D, __popcll(live), row0);
-                double cxc = 0.0;
-#pragma unroll
-                for (int kk = 0; kk < D; ++kk) {
-                    const double ck = -myA[kr * D + kk];  // f = -A[k,:]  (:1145)
-                    S.cost[kk] = ck;
-                    cxc = fma(ck, xc[kk], cxc);
-                }
-                // h[k] += 0.1 in place, as the reference does (:1149); undone after the LP (:1151), so rows
-                // k' < k carry the (+0.1, -0.1) round trip into the later LPs
-                const bool owner = go & ((kr >> RSH) == g.gl);
-                if (owner) myb[kr] = myb[kr] + 0.1;
-#pragma unroll
-                for (int k = 0; k < R; ++k) {
-#pragma unroll
-                    for (int kk = 0; kk < D; ++kk) S.T[k][kk] = myA[(row0 + k) * D + kk];
-                    S.beta[k] = fmax(myb[row0 + k] - myan[row0 + k], 0.0);  // 0 for the zeroed rows
-                }
-                S.ract = lloc;
-                S.mode = go ? M_P2 : M_DONE;
-#if PLP_R_FAST
-                S.template run_fast<GS>(g);
-                retry = retry | (go & (S.status == ST_RETRY));
-#else
-                S.run(g);
-#endif
-                const double fun = cxc - S.negz;  // c.xc + zeta, zeta = -negz
-                // b[k] after the round trip: computed by the lane that owns row k and handed to the others
-                // through registers (an LDS store of one lane followed by loads of other lanes would need a
-                // fence for the compiler, which otherwise keeps an earlier load)
-                double hk_own = 0.0;
-                if (owner) { hk_own = myb[kr] - 0.1; myb[kr] = hk_own; }
-                const double hk = bcast(hk_own, g.gbase + (kr >> RSH));
-                const double obj = -fun - hk;     // (:1156)
-                const bool keepk = go & (((S.status == ST_OPT) & (obj > abs_tol)) | (S.status == ST_UNBND));
-                keep |= keepk ? (1ull << kr) : 0ull;
-            }
-            if (stage == 2) flags |= RF_MINREP;
-        }
-#endif
         }
         // ---------------------------------------------------------------- results
         if (valid & (g.gl == 0) & (!SPLIT || grp == 0)) {
@@ -1172,12 +1040,6 @@ __device__ __forceinline__ void reduce_r_tile(
 // One polytope of up to 64 rows per wavefront, F3 / F2 on plp_lazy.hpp (d = 9..16, see there).
 #ifndef PLP_REDUCE_LAZY_WAVES
 #define PLP_REDUCE_LAZY_WAVES 3
-#endif
-#ifndef PLP_REDUCE_WDENSE_MAXD
-// one polytope per wavefront: F3 / F2 on the dense one-LP-per-wavefront engine up to this d, without a stored dictionary
-// beyond (measured, scripts/debug/wdense_ab.py, 64 rows, B = 20 000, ms dense / lazy: d = 8 1.39 / 2.30, 12 1.66 / 1.90,
-// 13 1.58 / 1.65, 14 1.48 / 1.48, 15 1.48 / 1.38, 16 1.60 / 1.33)
-#define PLP_REDUCE_WDENSE_MAXD 13
 #endif
 #ifndef PLP_REDUCE_WDENSE_WAVES
 #define PLP_REDUCE_WDENSE_WAVES 4
@@ -1260,7 +1122,6 @@ __device__ __forceinline__ bool f2_presolve_ws(const double* myA, const double* 
         const int jq = sjb[q * 64 + lane];
         j = jq >= 0 ? jq : j;
     }
-#if PLP_R_PRESOLVE >= 2
     bool ok2 = cand & !okall;
     if (__any(ok2)) {   // (the same in every wavefront: the barrier below is met by all or by none)
         double aj[D];
@@ -1302,7 +1163,6 @@ __device__ __forceinline__ bool f2_presolve_ws(const double* myA, const double* 
         for (int q = 0; q < NW; ++q) all2 = all2 & (((smask[NW + q] >> lane) & 1ull) != 0ull);
         okall = okall | (cand & !okall & all2);
     }
-#endif
     return okall;
 }
 
@@ -1315,25 +1175,8 @@ __device__ __forceinline__ bool f2_presolve_ws(const double* myA, const double* 
 // wide::solve_dense on the rows in LDS exactly as in reduce_wdense_kernel; the in-place h[k] +- 0.1 round trip
 // (:1149-1151) becomes the rule reduce_split_kernel uses (an unsettled row that had its turn before row k carries
 // (b + 0.1) - 0.1, row k itself b + 0.1), so the outputs are bit for bit those of the one-wavefront form.
-#ifndef PLP_REDUCE_WSPLIT_MAXB
-// Measured (scripts/debug/wsplit_sweep.py, ms with one / two / four wavefronts per polytope):
-//   (64,8)   B = 1  0.192 / 0.116 / 0.085    250  0.230 / 0.142 / 0.100    1 000  0.251 / 0.162 / 0.131    2 000  0.292 / 0.212 / 0.222
-//            5 000  0.444 / 0.417 / 0.432    8 000  0.658 / 0.597 / 0.640    16 000  1.127 / 1.077 / 1.218
-//   (48,6)   250  0.159 / 0.096 / 0.070    5 000  0.301 / 0.253 / 0.254    16 000  0.678 / 0.620 / 0.681
-//   (64,12)  250  0.267 / 0.161 / 0.120    5 000  0.580 / 0.495 / 0.543    16 000  1.336 / 1.319 / 1.591
-// two wavefronts per polytope up to here, four up to PLP_REDUCE_WSPLIT_MAXB4
-#define PLP_REDUCE_WSPLIT_MAXB 16000
-#endif
-#ifndef PLP_REDUCE_WSPLIT_MAXB4
-#define PLP_REDUCE_WSPLIT_MAXB4 2000   // four wavefronts per polytope up to here
-#endif
 template <int D>
 __host__ __device__ constexpr size_t wsplit_block_bytes() { return (sizeof(wide::WideShared<D + 1>) + 15) & ~(size_t)15; }
-template <int D, int NW>
-static inline size_t reduce_wsplit_smem_bytes() {
-    return (size_t)64 * (D + 2) * 8 + (size_t)(D + 2 + 2 * D) * 8 + 8 * 8 + 8 * 4 + 64 * 4 + NW * wsplit_block_bytes<D>() +
-           (size_t)2 * NW * 8 + (size_t)NW * 64 * 4;  // + the presolve's masks and blocking rows
-}
 // (d <= 8: the presolve is the register peak -- 94 VGPRs at d = 8 --; held to 80, six waves per SIMD, nothing spills: 78.
 //  From d = 9 on the same bound sends the 16-wide row vector to scratch: unconstrained there, 92..130)
 #ifndef PLP_REDUCE_WSPLIT_WAVES8
@@ -1558,7 +1401,6 @@ __global__ __launch_bounds__(64 * NW, PLP_REDUCE_WSPLIT_WAVES(D)) void reduce_ws
         const int nlive = __popcll(live);
         nlp += nlive;
         uint64_t todo = live;
-#if PLP_R_PRESOLVE
         // rows the presolve settles as "keep" need no LP: every wavefront takes a range of the rows to test against
         const bool settled = f2_presolve_ws<D, NW>(myA, myb, myan, lane, m_max, act, abs_tol, w, smask, sjb);
         const uint64_t cert = __ballot(settled);   // (lane i = row i: the ballot is the row mask, the same in every wavefront)
@@ -1568,7 +1410,6 @@ __global__ __launch_bounds__(64 * NW, PLP_REDUCE_WSPLIT_WAVES(D)) void reduce_ws
             if ((lane == 0) & (cert != 0ull)) atomicOr(&s64[1], (unsigned long long)cert);
             if (settled) myb[lane] = (myb[lane] + 0.1) - 0.1;  // (:1149-1151), as f2_presolve leaves the settled rows
         }
-#endif
         if ((w == 0) && ((todo >> lane) & 1ull)) slist[__popcll(todo & ((1ull << lane) - 1ull))] = lane;
         __syncthreads();
         const int ntodo = __popcll(todo);
@@ -1612,60 +1453,6 @@ __global__ __launch_bounds__(64 * NW, PLP_REDUCE_WSPLIT_WAVES(D)) void reduce_ws
     }
 }
 
-template <int D>
-static int launch_reduce_lazy(long long B, int m_max, const double* A, const double* b, const int* mrows, double abs_tol,
-                              unsigned long long* keep, int* flags, double* r, double* xc, int* nlp, hipStream_t st) {
-    const size_t smem = reduce_r_smem_bytes(64, D, 1) + lazy::lds_bytes<D>();
-    if (B > 2147483647ll) return 2;
-    const char* fr = getenv("PLP_REDUCE_RETRY_ALL");
-    // PLP_REDUCE_WDENSE=0 / 1: F3 / F2 without / with a stored dictionary (A/B)
-    const char* wd = getenv("PLP_REDUCE_WDENSE");
-    const bool dense = wd ? wd[0] == '1' : (D <= PLP_REDUCE_WDENSE_MAXD);
-    // 3: complete -- the dense LPs carry Bland's rule inside, no polytope is handed to a second pass (the caller then
-    // launches none: at small batches the idle second launch was 5 % of the call)
-    const int done = (dense && !(fr && fr[0] == '1')) ? 3 : 0;
-    {
-        // batches that leave the chip part empty at one wavefront per polytope: NW wavefronts per polytope
-        // (PLP_REDUCE_WSPLIT=0: never, 2 / 4: always with that many; PLP_REDUCE_WSPLIT_MAXB / _MAXB4: the largest batches that take them)
-        const char* ws = getenv("PLP_REDUCE_WSPLIT");
-        const char* wb = getenv("PLP_REDUCE_WSPLIT_MAXB");
-        const char* wb4 = getenv("PLP_REDUCE_WSPLIT_MAXB4");
-        // (without a stored dictionary, d = 14..16: (64,16) B = 250 0.228 / 0.143 / 0.112 ms with one / two / four wavefronts,
-        // 1 000 0.248 / 0.170 / 0.201, 3 000 0.355 / 0.346 / 0.437, 8 000 0.704 / 0.703 / 0.951)
-        const long long maxb = wb ? atoll(wb) : (dense ? PLP_REDUCE_WSPLIT_MAXB : 3000);
-        // (with the presolve over the wavefronts: four ahead of two up to 12 000 polytopes at d <= 8 -- (64,8) 5 000 0.379 / 0.402,
-        // 12 000 0.803 / 0.810, 16 000 1.051 / 1.026 -- and up to ~3 000 at d = 9..13: (64,12) 3 000 0.338 / 0.366, 5 000 0.502 / 0.495)
-        const long long maxb4 = wb4 ? atoll(wb4) : (dense ? (D <= 8 ? 12000 : PLP_REDUCE_WSPLIT_MAXB4) : 500);
-        const int fi = (fr && fr[0] == '1') ? 1 : 0;
-        int nw = 0;
-        if (B >= 1 && !(ws && ws[0] == '0')) {
-            if ((ws && ws[0] == '4') || (!ws && B <= maxb4)) nw = 4;
-            else if ((ws && ws[0] == '2') || (!ws && B <= maxb)) nw = 2;
-        }
-#define PLP_WSPLIT_LAUNCH(NW_, DENSE_)                                                                                          \
-        {                                                                                                                       \
-            const size_t smem_ws = reduce_wsplit_smem_bytes<D, NW_>();                                                          \
-            hipLaunchKernelGGL((reduce_wsplit_kernel<D, NW_, DENSE_>), dim3((unsigned)B), dim3(64 * NW_), smem_ws, st, B, m_max, A, b, \
-                               mrows, abs_tol, fi, keep, flags, r, xc, nlp, t_reduce_ctr, t_reduce_retry, t_reduce_epoch);        \
-            return done;                                                                                                        \
-        }
-        if constexpr (D <= PLP_REDUCE_WDENSE_MAXD) {
-            if (dense && nw == 4) PLP_WSPLIT_LAUNCH(4, true)
-            if (dense && nw == 2) PLP_WSPLIT_LAUNCH(2, true)
-        } else {
-            if (!dense && nw == 4) PLP_WSPLIT_LAUNCH(4, false)
-            if (!dense && nw == 2) PLP_WSPLIT_LAUNCH(2, false)
-        }
-#undef PLP_WSPLIT_LAUNCH
-    }
-    if (dense)
-        hipLaunchKernelGGL((reduce_wdense_kernel<D>), dim3((unsigned)(B < 1 ? 1 : B)), dim3(RBLOCK), smem, st, B, m_max, A, b,
-                           mrows, abs_tol, (fr && fr[0] == '1') ? 1 : 0, keep, flags, r, xc, nlp, t_reduce_ctr, t_reduce_retry, t_reduce_epoch);
-    else
-        hipLaunchKernelGGL((reduce_lazy_kernel<D>), dim3((unsigned)(B < 1 ? 1 : B)), dim3(RBLOCK), smem, st, B, m_max, A, b,
-                           mrows, abs_tol, (fr && fr[0] == '1') ? 1 : 0, keep, flags, r, xc, nlp, t_reduce_ctr, t_reduce_retry, t_reduce_epoch);
-    return done;
-}
 
 // Small batches: one polytope per wavefront, its LPs spread over the lane groups (reduce_r_tile, SPLIT).
 template <int D, int GS, int R = RR>
@@ -1679,19 +1466,9 @@ __global__ __launch_bounds__(RBLOCK, PLP_REDUCE_R_WAVES(D)) void reduce_split_ke
                                          flags_out, r_out, xc_out, nlp_out, ctr, retry_word, epoch);
 }
 
-// Batches up to this size take the latency form.  Measured (device time per call, batch form -> latency form): (16,3)
-// B = 1: 49 -> 21 us, 256: 77 -> 25, 4096: 81 -> 50, 16384: 90 -> 153; (32,6) 256: 274 -> 79, 4096: 306 -> 202;
-// (64,8) 256: 652 -> 257, 4096: 896 -> 728; (16,8) 256: 80 -> 75, 4096: 82 -> 111 (16 rows at d >= 7 gain nothing:
-// the 2d box LPs already fill the 16 groups).  ~20 us of every figure are the launches of a call.
-#ifndef PLP_REDUCE_SPLIT_MAXB
-// (round 3, with the F2 presolve and d = 5..8 on two rows per lane beyond this size: (32,6) B = 2048: 0.121 ms here vs 0.181,
-// B = 4096: 0.222 vs 0.187; (64,8) B = 1024: 0.302 vs 0.366, B = 2000: 0.426 vs 0.404)
-#define PLP_REDUCE_SPLIT_MAXB(D, GS) \
-    ((((GS) == 4 && (D) >= 7) || (D) > 8 || ((D) >= 5 && (GS) == 16)) ? 1024 : ((D) >= 5 ? 2048 : 4096))  // (d > 8: four groups only; (32,12) B = 4096: 154 -> 201 us)
-#endif
 
 template <int D, int GS, int R = RR>
-__global__ __launch_bounds__(RBLOCK, (R == 8 ? PLP_REDUCE_R8_WAVES : (R == 2 && D <= 8 ? PLP_REDUCE_R2MID_WAVES : PLP_REDUCE_R_WAVES(D)))) void reduce_r_kernel(
+__global__ __launch_bounds__(RBLOCK, (R == 2 && D <= 8 ? PLP_REDUCE_R2MID_WAVES : PLP_REDUCE_R_WAVES(D))) void reduce_r_kernel(
     long long B, int m_max, const double* __restrict__ Ag, const double* __restrict__ bg,
     const int* __restrict__ mrows, double abs_tol, int force_retry, unsigned long long* __restrict__ keep_out,
     int* __restrict__ flags_out, double* __restrict__ r_out, double* __restrict__ xc_out,
@@ -1718,65 +1495,6 @@ __global__ __launch_bounds__(RBLOCK, PLP_REDUCE_R_WAVES(D)) void reduce_r_mix_ke
     else
         reduce_r_tile<D, 8, 2>((long long)nbig * (RBLOCK / 4) + (long long)((int)blockIdx.x - nbig) * (RBLOCK / 8), B, m_max,
                                Ag, bg, mrows, abs_tol, force_retry, keep_out, flags_out, r_out, xc_out, nlp_out, ctr, retry_word, epoch);
-}
-
-template <int D, int GS, int R = RR>
-static int launch_reduce_r_dg(long long B, int m_max, const double* A, const double* b, const int* mrows,
-                             double abs_tol, unsigned long long* keep, int* flags, double* r, double* xc, int* nlp,
-                             hipStream_t st) {
-    const size_t smem = reduce_r_smem_bytes(GS, D, R);
-    const long long NG = RBLOCK / GS;
-    long long blocks = (B + NG - 1) / NG;
-    if (blocks > 2147483647ll) return 2;  // grid.x limit (never reached for realistic batches)
-    if (smem > 48 * 1024)  // 64 rows x d>=5: up to 82 KB of the CU's 160 KB
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(reduce_r_kernel<D, GS, R>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (blocks < 1) blocks = 1;
-    const char* fr = getenv("PLP_REDUCE_RETRY_ALL");
-    if constexpr ((R == 4 && D <= 8) || (R == 2 && D > 8)) {
-        // small batches: one polytope per wavefront, LPs in parallel (PLP_REDUCE_SPLIT=0 / 1: never / always)
-        const char* sp = getenv("PLP_REDUCE_SPLIT");
-        if ((sp && sp[0] == '1') || (!(sp && sp[0] == '0') && B <= PLP_REDUCE_SPLIT_MAXB(D, GS))) {
-            const size_t sm1 = (((size_t)GS * R * (D + 2) + 2 * D + 2) * 8 + 15) & ~(size_t)15;
-            hipLaunchKernelGGL((reduce_split_kernel<D, GS, R>), dim3((unsigned)(B < 1 ? 1 : B)), dim3(RBLOCK), sm1, st, B, m_max,
-                               A, b, mrows, abs_tol, (fr && fr[0] == '1') ? 1 : 0, keep, flags, r, xc, nlp, t_reduce_ctr, t_reduce_retry, t_reduce_epoch);
-            return 0;
-        }
-    }
-    if constexpr (GS == 4 && R == 4 && D <= 4) {
-        // more tiles than the chip holds at once (4096 wavefront slots): the last 1/16 of the tiles (at most 1024) are
-        // split into half-size ones.  Measured at C2 (6250 tiles): 0.2765 ms without, 0.2579-0.2609 ms with 2/64 .. 9/64
-        // of the batch in half-size tiles (a flat optimum), 0.27-0.29 ms beyond 10/64.  PLP_REDUCE_MIX=k: k/64 (0: off).
-        // A third class of quarter-size tiles (16 lanes x 1 row) behind the half-size ones was measured too: no gain
-        // (0.2557-0.2602 ms for the last 2/256 .. 12/256 of the batch), not kept.
-        const char* mx = getenv("PLP_REDUCE_MIX");
-        // (round 4: 1/32 of the tiles instead of 1/16 -- the optimum is flat between 2/64 and 8/64: 0.1908 / 0.1919 ms)
-        long long tail_tiles = blocks / 32 < 1024 ? blocks / 32 : 1024;
-        if (mx) tail_tiles = blocks * atoi(mx) / 64;
-        // medium batches (fewer full tiles than half the chip's wavefront slots): half-size tiles only -- twice the
-        // wavefronts, each done in about half the time.  PLP_REDUCE_HALF=0 / 1: never / whenever blocks <= 4096 (A/B).
-        const char* hf = getenv("PLP_REDUCE_HALF");
-        if (!mx && blocks <= 4096 && ((hf && hf[0] == '1') || (!(hf && hf[0] == '0') && blocks <= 2048))) {
-            const long long nsmall = (B + NG / 2 - 1) / (NG / 2);
-            const size_t smem2 = reduce_r_smem_bytes(8, D, 2);
-            hipLaunchKernelGGL((reduce_r_mix_kernel<D>), dim3((unsigned)nsmall), dim3(RBLOCK), smem > smem2 ? smem : smem2, st,
-                               0, B, m_max, A, b, mrows, abs_tol, (fr && fr[0] == '1') ? 1 : 0, keep, flags, r, xc, nlp, t_reduce_ctr, t_reduce_retry, t_reduce_epoch);
-            return 0;
-        }
-        if (tail_tiles > 0 && tail_tiles < blocks && blocks > 4096) {
-            long long nbig = blocks - tail_tiles;
-            const long long rest = B - nbig * NG;
-            const long long nsmall = (rest + NG / 2 - 1) / (NG / 2);
-            const size_t smem2 = reduce_r_smem_bytes(8, D, 2);
-            hipLaunchKernelGGL((reduce_r_mix_kernel<D>), dim3((unsigned)(nbig + nsmall)), dim3(RBLOCK),
-                               smem > smem2 ? smem : smem2, st, (int)nbig, B, m_max, A, b, mrows, abs_tol,
-                               (fr && fr[0] == '1') ? 1 : 0, keep, flags, r, xc, nlp, t_reduce_ctr, t_reduce_retry, t_reduce_epoch);
-            return 0;
-        }
-    }
-    hipLaunchKernelGGL((reduce_r_kernel<D, GS, R>), dim3((unsigned)blocks), dim3(RBLOCK), smem, st, B, m_max, A, b, mrows,
-                       abs_tol, (fr && fr[0] == '1') ? 1 : 0, keep, flags, r, xc, nlp, t_reduce_ctr, t_reduce_retry, t_reduce_epoch);
-    return 0;
 }
 
 }  // namespace plp

@@ -25,10 +25,6 @@ struct Grp {
     }
 };
 
-#ifndef PLP_USE_DPP
-#define PLP_USE_DPP 1
-#endif
-
 // dpp_ctrl encodings (LLVM AMDGPU): quad_perm = sel0|sel1<<2|sel2<<4|sel3<<6,
 // row_mirror = 0x140, row_half_mirror = 0x141
 #define PLP_DPP_XOR1 0xB1  // quad_perm [1,0,3,2]
@@ -53,17 +49,10 @@ __device__ __forceinline__ unsigned min_u(unsigned a, unsigned b) { return b < a
 
 // all-reduce(min) over the lanes of my group; every lane of the group gets the result.
 __device__ __forceinline__ double grp_min(double v, int gs) {
-#if PLP_USE_DPP
     v = min_d(v, dpp_d<PLP_DPP_XOR1>(v));
     v = min_d(v, dpp_d<PLP_DPP_XOR2>(v));
     v = min_d(v, dpp_d<PLP_DPP_HMIRROR>(v));
     if (gs > 8) v = min_d(v, dpp_d<PLP_DPP_MIRROR>(v));
-#else
-    v = min_d(v, __shfl_xor(v, 1, 64));
-    v = min_d(v, __shfl_xor(v, 2, 64));
-    v = min_d(v, __shfl_xor(v, 4, 64));
-    if (gs > 8) v = min_d(v, __shfl_xor(v, 8, 64));
-#endif
     if (gs > 16) v = min_d(v, __shfl_xor(v, 16, 64));
     if (gs > 32) v = min_d(v, __shfl_xor(v, 32, 64));
     return v;
@@ -77,17 +66,10 @@ __device__ __forceinline__ double grp_min(double v, int gs) {
     asm volatile("s_nop 1\n\tv_min_u32_dpp %0, %0, %0 " CTRL " row_mask:0xf bank_mask:0xf" : "+v"(v))
 
 __device__ __forceinline__ unsigned grp_min(unsigned v, int gs) {
-#if PLP_USE_DPP
     PLP_MIN_U32_DPP(v, "quad_perm:[1,0,3,2]");
     PLP_MIN_U32_DPP(v, "quad_perm:[2,3,0,1]");
     if (gs > 4) PLP_MIN_U32_DPP(v, "row_half_mirror");
     if (gs > 8) PLP_MIN_U32_DPP(v, "row_mirror");
-#else
-    v = min_u(v, (unsigned)__shfl_xor((int)v, 1, 64));
-    v = min_u(v, (unsigned)__shfl_xor((int)v, 2, 64));
-    if (gs > 4) v = min_u(v, (unsigned)__shfl_xor((int)v, 4, 64));
-    if (gs > 8) v = min_u(v, (unsigned)__shfl_xor((int)v, 8, 64));
-#endif
     if (gs > 16) v = min_u(v, (unsigned)__shfl_xor((int)v, 16, 64));
     if (gs > 32) v = min_u(v, (unsigned)__shfl_xor((int)v, 32, 64));
     return v;

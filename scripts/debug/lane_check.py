@@ -1,4 +1,4 @@
-"""GPU: reduce_lane_kernel (one LP per lane, plp_reduce_lane.hip) against the lane-group kernels and the oracle, and its
+"""GPU: reduce_lane_kernel (one LP per lane, plp_reduce_lane.hpp) against the lane-group kernels and the oracle, and its
 timing next to theirs.   gpurun -- 'python scripts/debug/lane_check.py [lib.so ...]'"""
 import os
 import sys

@@ -2,7 +2,6 @@
 -DPLP_STAGE_STATS: build_variants/libplp_hip_stats.so, PLP_LIB points at it)."""
 import ctypes, os, sys
 os.environ["PLP_LIB"] = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "build_variants", "libplp_hip_stats.so")
-os.environ.setdefault("PLP_REDUCE_MIX", "0")
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
 import torch
 import polytope_amd as pa

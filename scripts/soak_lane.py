@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Soak of the one-LP-per-lane kernels (plp_reduce_lane.hip) on the GPU box, not part of the test suite: fused reduce and
+"""Soak of the one-LP-per-lane kernels (plp_reduce_lane.hpp) on the GPU box, not part of the test suite: fused reduce and
 stand-alone bounding boxes at (<= 32 rows, d <= 4) over every dispatch class (4 / 8 / 16 polytopes per wavefront, the mixed
 launch, 17..32 rows, d = 4 forced and by size), on random, ragged, unbounded-allowed, duplicated / nearly duplicated,
 rescaled and structured data -- EVERY polytope against the oracle (keep mask, flags, LP count exact; radius 1e-9), the
@@ -213,7 +213,7 @@ def main():
         if m > 16 or d == 4:
             B = min(B, 36000)
         fam = fams[int(rng.integers(0, len(fams)))]
-        force = bool(rng.random() < 0.5)   # d = 4: small batches (plp_reduce_r.hip: PLP_REDUCE_LANE4_MINB*) go to the lane kernel only when asked to
+        force = bool(rng.random() < 0.5)   # d = 4: small batches (plp_reduce_plan.hpp: PLP_REDUCE_LANE4_MINB*) go to the lane kernel only when asked to
         for k_ in ("PLP_REDUCE_LANE", "PLP_REDUCE_LANE_GS"):
             os.environ.pop(k_, None)
         if force:
