@@ -172,6 +172,37 @@ int plp_reduce_wide_batch_dev(plp_ctx *ctx, void *stream, int64_t B, int m_max, 
                               int32_t *flags, double *r, double *xc, int32_t *nlp);
 
 /*
+ * One Fourier-Motzkin elimination step of projection(solver="fm") (polytope/polytope.py:1911-1952) for B packed
+ * polytopes, fused with the compaction of the reduce() that produced their rows.
+ * In:  A[B][m_max][d], b[B][m_max], m[B] (NULL = m_max) as for plp_reduce_batch;
+ *      keep[B][kw] (NULL = every row) and flags[B] (NULL = none) of the plp_reduce_batch / plp_reduce_wide_batch call
+ *      that produced the rows: only rows whose keep bit is set are read; with flags, each such row gets what
+ *      reduce() does to it on the way out (PLP_RF_MINREP: b = (b + 0.1) - 0.1; then one Polytope constructor pass:
+ *      scale by the reciprocal norm, rows of norm <= 1e-10 dropped); first != 0 adds one more constructor pass (the
+ *      copy() of the first step, :1923); polytopes flagged PLP_RF_EMPTY / PLP_RF_LPFAIL / 32 (re-examine) have no rows.
+ *      col: the column eliminated (0 <= col < d, d >= 2); col < 0: no elimination, the staged rows themselves.
+ * plp_fm_count: count[B] = |N| + |P| |Q| with P: a_col > abs_tol, Q: a_col < -abs_tol, N: |a_col| < abs_tol
+ *      (a coefficient of exactly +-abs_tol: the row is dropped, :1925-1927).
+ * plp_fm_emit: the rows, in the reference's order (P x Q with P major, then N), column col removed, each scaled by the
+ *      constructor (rows of norm <= 1e-10 dropped), into A_out[B][mo_max][d_out], b_out[B][mo_max] (d_out = d - 1, or d
+ *      for col < 0; rows from m_out[B] on are zero) and m_out[B]; m_out = -1: more than mo_max rows, nothing written.
+ *      A combined row is  fma(a_j,col, x_k, (-a_k,col) * x_j)  element-wise, A and b alike.
+ * The input of a polytope must fit the LDS of a CU: m_max (d + 1) 8 + 12 m_max <= 160 KB, else PLP_EUNSUPPORTED.
+ */
+int plp_fm_count(plp_ctx *ctx, int64_t B, int m_max, int d, const double *A, const double *b, const int32_t *m,
+                 const uint64_t *keep, int kw, const int32_t *flags, int col, int first, double abs_tol,
+                 int32_t *count);
+int plp_fm_count_dev(plp_ctx *ctx, void *stream, int64_t B, int m_max, int d, const double *A, const double *b,
+                     const int32_t *m, const uint64_t *keep, int kw, const int32_t *flags, int col, int first,
+                     double abs_tol, int32_t *count);
+int plp_fm_emit(plp_ctx *ctx, int64_t B, int m_max, int d, const double *A, const double *b, const int32_t *m,
+                const uint64_t *keep, int kw, const int32_t *flags, int col, int first, double abs_tol, int mo_max,
+                double *A_out, double *b_out, int32_t *m_out);
+int plp_fm_emit_dev(plp_ctx *ctx, void *stream, int64_t B, int m_max, int d, const double *A, const double *b,
+                    const int32_t *m, const uint64_t *keep, int kw, const int32_t *flags, int col, int first,
+                    double abs_tol, int mo_max, double *A_out, double *b_out, int32_t *m_out);
+
+/*
  * Containment of N points in P polytopes:  all_i( A_p[i,:].x - b_p[i] < abs_tol ).
  * Replaces: Polytope.contains (polytope/polytope.py:206-218), Region.contains (:732-746),
  *           is_inside (:1017-1029), __contains__ (:191-204, :723-730).

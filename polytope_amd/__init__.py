@@ -9,9 +9,11 @@ Drop-in surface: the package root carries the names the reference's root carries
     import polytope_amd as polytope
     polytope.solvers.default_solver = 'hip'
 
-is the whole switch.  `grid_region` and `projection` (and plotting) are outside the hot path
- and are not provided.  The batched entry points (`*_batch`, no reference
-counterpart) sit beside them.
+is the whole switch.  `grid_region` (and plotting) are outside the hot path
+and are not provided.  `projection` and its helpers are reachable where the reference defines them,
+as `polytope.polytope.projection` (and `Polytope.project`), not at the package root; on 'hip' its
+Fourier-Motzkin steps run on the device.  The batched entry points (`*_batch`, no reference
+counterpart, `projection_batch` among them) sit beside them.
 
 The compute path is hand-written HIP (polytope_amd/csrc, built into libplp_hip.so and
 reached through the C ABI of include/plp.h).  There is no CPU fallback: without the
@@ -31,7 +33,7 @@ from .prop2partition import (  # noqa: F401
 from . import polytope, prop2partition, quickhull  # noqa: F401,E402  (submodules, as `polytope.polytope` etc.)
 from .batch import (  # noqa: F401
     lpsolve_batch, cheby_ball_batch, bbox_batch, reduce_batch, contains_batch, assign_batch, adjacent_pairs, keep_to_bool,
-    verify_careful_lps, lp_histograms,
+    verify_careful_lps, lp_histograms, projection_batch,
 )
 
 __version__ = "0.1.0"

@@ -8,6 +8,7 @@ on torch's current stream, results come back as CUDA tensors, nothing synchronis
 Packing: A[B, m_max, d], b[B, m_max], optional int32 m[B] (rows used per polytope).
 """
 import ctypes as C
+import time
 
 import numpy as np
 
@@ -657,3 +658,378 @@ def quickhull_run(X0, simplex, abs_tol=1e-7):
     finally:
         lib.plp_qh_result_free(h)
     return normals, offsets, verts, dict(iterations=int(it.value), facets_made=int(made.value))
+
+
+# ------------------------------------------------------------------------------------- projection (Fourier-Motzkin)
+def _fm_call(emit, A, b, col, m=None, keep=None, flags=None, first=False, abs_tol=1e-7, mo_max=0):
+    lib = _lib.load()
+    if _is_torch(A):
+        torch, ctx, stream = _torch_stream_ctx(A)
+        A = _tprep(torch, A, torch.float64)
+        b = _tprep(torch, b, torch.float64)
+        m = _tprep(torch, m, torch.int32)
+        flags = _tprep(torch, flags, torch.int32)
+        if keep is not None:
+            keep = _tprep(torch, keep.reshape(keep.shape[0], -1), torch.int64)
+        B, m_max, d = A.shape
+        kw = 0 if keep is None else int(keep.shape[1])
+        dout = d - 1 if col >= 0 else d
+        if not emit:
+            count = torch.empty((B,), dtype=torch.int32, device=A.device)
+            _lib.check(lib.plp_fm_count_dev(ctx.handle, stream, B, m_max, d, _ptr(A), _ptr(b), _ptr(m), _ptr(keep), kw,
+                                            _ptr(flags), int(col), int(bool(first)), float(abs_tol), _ptr(count)),
+                       "plp_fm_count_dev")
+            return count
+        Ao = torch.empty((B, mo_max, dout), dtype=torch.float64, device=A.device)
+        bo = torch.empty((B, mo_max), dtype=torch.float64, device=A.device)
+        mo = torch.empty((B,), dtype=torch.int32, device=A.device)
+        _lib.check(lib.plp_fm_emit_dev(ctx.handle, stream, B, m_max, d, _ptr(A), _ptr(b), _ptr(m), _ptr(keep), kw,
+                                       _ptr(flags), int(col), int(bool(first)), float(abs_tol), int(mo_max), _ptr(Ao),
+                                       _ptr(bo), _ptr(mo)), "plp_fm_emit_dev")
+        return Ao, bo, mo
+    A = _np(A)
+    if A.ndim != 3:
+        raise ValueError("A must be [B, m_max, d]")
+    B, m_max, d = A.shape
+    b = _np(b).reshape(B, m_max)
+    mm = None if m is None else _np(m, np.int32).reshape(B)
+    fl = None if flags is None else _np(flags, np.int32).reshape(B)
+    kp = None if keep is None else _np(keep, np.uint64).reshape(B, -1)
+    kw = 0 if kp is None else kp.shape[1]
+    dout = d - 1 if col >= 0 else d
+    if not emit:
+        count = np.empty(B, np.int32)
+        _lib.check(lib.plp_fm_count(_lib.context().handle, B, m_max, d, _ptr(A), _ptr(b), _ptr(mm), _ptr(kp), kw, _ptr(fl),
+                                    int(col), int(bool(first)), float(abs_tol), _ptr(count)), "plp_fm_count")
+        return count
+    Ao = np.empty((B, mo_max, dout))
+    bo = np.empty((B, mo_max))
+    mo = np.empty(B, np.int32)
+    _lib.check(lib.plp_fm_emit(_lib.context().handle, B, m_max, d, _ptr(A), _ptr(b), _ptr(mm), _ptr(kp), kw, _ptr(fl),
+                               int(col), int(bool(first)), float(abs_tol), int(mo_max), _ptr(Ao), _ptr(bo), _ptr(mo)),
+               "plp_fm_emit")
+    return Ao, bo, mo
+
+
+def fm_count(A, b, col, m=None, keep=None, flags=None, first=False, abs_tol=1e-7):
+    """Rows one Fourier-Motzkin step on column `col` forms per polytope, |N| + |P| |Q| (include/plp.h: plp_fm_count).
+    `keep` / `flags`: the reduce_batch result that produced the rows (only kept rows are read, and each gets what reduce()
+    does to it on the way out); `first`: one more constructor pass (the copy() of projection_fm's first step)."""
+    return _fm_call(False, A, b, col, m, keep, flags, first, abs_tol)
+
+
+def fm_emit(A, b, col, mo_max, m=None, keep=None, flags=None, first=False, abs_tol=1e-7):
+    """The rows of that step -> (A_out[B, mo_max, d - 1], b_out[B, mo_max], m_out[B]) in the reference's order, each scaled
+    as Polytope() does; m_out = -1 where the step forms more than mo_max rows (include/plp.h: plp_fm_emit).  col < 0: no
+    elimination, the staged rows themselves (d columns)."""
+    return _fm_call(True, A, b, col, m, keep, flags, first, abs_tol, mo_max)
+
+
+# status codes of projection_batch
+PROJ_OK, PROJ_EMPTY, PROJ_INPUT, PROJ_RAISES, PROJ_LPFAIL = 0, 1, 2, 3, 4
+# projection_fm calls reduce() / is_fulldim() with the module's tolerance, whatever projection() was given (ref :1940-1950)
+_REDUCE_TOL = 1e-7
+
+# what the last projection_batch call did (scripts/bench_projection.py): launches and device-to-host bytes per step
+fm_stats = {}
+
+
+def _keep_width(rows):
+    """Keep words per polytope for a tensor of `rows` row slots: the step kernels read ceil(rows / 64) of them whatever
+    the row counts in use (include/plp.h: kw >= ceil(m_max / 64))."""
+    return max(1, (int(rows) + 63) // 64)
+
+
+def _reduce_split(torch, Ao, bo, mo_h, sel, stats):
+    """Fused reduce of the polytopes `sel` (host indices into Ao) whose rows Ao[k, :mo_h[k]] hold: the ones of up to 64 rows
+    on the register-resident kernels, the longer ones on the LDS kernel, each group packed to its own row count.
+    -> keep words int64[len(sel), W] with W = _keep_width(Ao.shape[1]) (the words travel with Ao to the next step),
+    flags int32[len(sel)] (device)"""
+    n = len(sel)
+    dev = Ao.device
+    m_sel = mo_h[sel]
+    W = _keep_width(Ao.shape[1])
+    keep = torch.zeros((n, W), dtype=torch.int64, device=dev)
+    flags = torch.empty((n,), dtype=torch.int32, device=dev)
+    for grp in (np.nonzero(m_sel <= MAX_M)[0], np.nonzero(m_sel > MAX_M)[0]):
+        if grp.size == 0:
+            continue
+        rows = int(m_sel[grp].max())
+        gi = torch.as_tensor(np.asarray(sel)[grp], device=dev)
+        Ag = Ao.index_select(0, gi)[:, :rows].contiguous()
+        bg = bo.index_select(0, gi)[:, :rows].contiguous()
+        mg = torch.as_tensor(m_sel[grp].astype(np.int32), device=dev)
+        res = reduce_batch(Ag, bg, m=mg, abs_tol=_REDUCE_TOL)
+        stats["launches"] += 1
+        gt = torch.as_tensor(grp, device=dev)
+        kw = res["keep"].reshape(len(grp), -1)
+        keep[gt, :kw.shape[1]] = kw
+        flags[gt] = res["flags"]
+    return keep, flags
+
+
+def _fm_batch(A, b, m, cols, abs_tol, reduced, on_host, stats=None):
+    # abs_tol: the P / Q / N split (projection_fm's own argument); the reductions use the module's tolerance
+    """Fourier-Motzkin steps of projection_fm (polytope/polytope.py:1911-1952) on packed device tensors.  `cols`: columns to
+    eliminate, highest first.  reduced[k]: the rows of polytope k are already what projection_fm copies (a minimal
+    representation, or the output of reduce()); otherwise the first reduce() runs here, fused.  on_host(k, poly, cols_left,
+    first): the host continuation for polytope k, given the Polytope about to be eliminated on cols_left.
+    -> list of B entries, (status, A_k, b_k, minrep) for polytopes that ended early, None for those handed to on_host
+    or finished in the last step, followed by (idx, A, b, m, minrep) of the latter (packed, host arrays) or None."""
+    import torch
+    from .polytope import Polytope, _max_rows_reduce
+    B, m_max, d = A.shape
+    dev = A.device
+    stats = [] if stats is None else stats   # (one dict per phase: launches, device-to-host bytes)
+    out = [None] * B
+    idx = np.arange(B)                   # polytope of each row of the current tensors
+    m_h = m.cpu().numpy().astype(np.int64)
+    keep = flags = None
+    min_h = np.zeros(B, bool)            # minrep of the polytope the last reduce() returned (reduced inputs: False)
+    cur_A, cur_b, cur_m = A, b, m
+    first = True
+    red = np.asarray(reduced, dtype=bool)
+    if red.any() and not red.all():
+        raise ValueError("_fm_batch: a batch is either all reduced or all unreduced")
+    if not red.all():
+        st = dict(step="reduce", launches=0, d2h=0, t=time.perf_counter())
+        sel = np.nonzero(~red)[0]
+        keep_r, flags_r = _reduce_split(torch, A, b, m_h, sel, st)
+        keep, flags = keep_r, flags_r
+        fl_h = flags.cpu().numpy()
+        min_h = (fl_h & _lib.RF_MINREP) != 0
+        st["d2h"] += 4 * B
+        stats.append(st)
+        dead = _fm_flags(fl_h)
+        for k in np.nonzero(dead == 1)[0]:
+            out[k] = (PROJ_RAISES, None, None, False)   # reduce() returned Polytope(): the reference fails on poly.A[:, i]
+        for k in np.nonzero(dead == 3)[0]:
+            out[k] = (PROJ_LPFAIL, None, None, False)
+        for k in np.nonzero(dead == 2)[0]:
+            on_host(int(k), Polytope(A[k, :m_h[k]].cpu().numpy(), b[k, :m_h[k]].cpu().numpy(), normalize=False), list(cols),
+                    None)
+            out[k] = None
+        live = np.nonzero(dead == 0)[0]
+        idx = live
+        min_h = min_h[live]
+        if live.size < B:
+            li = torch.as_tensor(live, device=dev)
+            cur_A, cur_b, cur_m = A.index_select(0, li), b.index_select(0, li), m.index_select(0, li)
+            keep, flags = keep.index_select(0, li), flags.index_select(0, li)
+    d_cur = d
+    for s, col in enumerate(cols):
+        if idx.size == 0:
+            break
+        st = dict(step="col %d" % col, launches=0, d2h=0, t=time.perf_counter())
+        stats.append(st)
+        count = fm_count(cur_A, cur_b, int(col), m=cur_m, keep=keep, flags=flags, first=first, abs_tol=abs_tol)
+        st["launches"] += 1
+        cnt = count.cpu().numpy().astype(np.int64)
+        st["d2h"] += 4 * idx.size
+        cap = _max_rows_reduce(d_cur - 1)
+        big = cnt > cap
+        mo_max = int(cnt[~big].max()) if (~big).any() else 0
+        Ao, bo, mo = fm_emit(cur_A, cur_b, int(col), max(mo_max, 1), m=cur_m, keep=keep, flags=flags, first=first,
+                             abs_tol=abs_tol)
+        st["launches"] += 1
+        mo_h = mo.cpu().numpy().astype(np.int64)
+        st["d2h"] += 4 * idx.size
+        for t in np.nonzero(big)[0]:   # beyond what the fused reduce takes: this step's rows on their own, then the host
+            k = int(idx[t])
+            kp = None if keep is None else keep[t:t + 1]
+            fp = None if flags is None else flags[t:t + 1]
+            Ak, bk, mk = fm_emit(cur_A[t:t + 1], cur_b[t:t + 1], int(col), int(cnt[t]), m=cur_m[t:t + 1], keep=kp,
+                                 flags=fp, first=first, abs_tol=abs_tol)
+            st["launches"] += 1
+            n = int(mk[0])
+            on_host(k, Polytope(Ak[0, :n].cpu().numpy(), bk[0, :n].cpu().numpy(), normalize=False), list(cols[s + 1:]),
+                    "reduce")
+        ok = ~big & (mo_h > 0)
+        for t in np.nonzero(~big & (mo_h <= 0))[0]:
+            out[int(idx[t])] = (PROJ_EMPTY, None, None, False)   # no rows: is_fulldim(Polytope of no rows) is False
+        sel = np.nonzero(ok)[0]
+        if sel.size == 0:
+            idx = sel
+            break
+        keep, flags = _reduce_split(torch, Ao, bo, mo_h, sel, st)
+        fl_h = flags.cpu().numpy()
+        st["d2h"] += 4 * sel.size
+        dead = _fm_flags(fl_h)
+        for t in np.nonzero(dead == 1)[0]:
+            out[int(idx[sel[t]])] = (PROJ_EMPTY, None, None, False)
+        for t in np.nonzero(dead == 3)[0]:
+            out[int(idx[sel[t]])] = (PROJ_LPFAIL, None, None, False)
+        for t in np.nonzero(dead == 2)[0]:
+            k = int(idx[sel[t]])
+            n = int(mo_h[sel[t]])
+            on_host(k, Polytope(Ao[sel[t], :n].cpu().numpy(), bo[sel[t], :n].cpu().numpy(), normalize=False),
+                    list(cols[s + 1:]), "reduce")
+        live = np.nonzero(dead == 0)[0]
+        si = torch.as_tensor(sel[live], device=dev)
+        li = torch.as_tensor(live, device=dev)
+        cur_A, cur_b = Ao.index_select(0, si), bo.index_select(0, si)
+        cur_m = mo.index_select(0, si)
+        keep, flags = keep.index_select(0, li), flags.index_select(0, li)
+        min_h = ((fl_h & _lib.RF_MINREP) != 0)[live]
+        idx = idx[sel[live]]
+        first = False
+        d_cur -= 1
+    if idx.size:
+        # the last reduce's output polytope: its kept rows through the constructor (col < 0: no elimination)
+        st = dict(step="compact", launches=0, d2h=0, t=time.perf_counter())
+        stats.append(st)
+        cnt = fm_count(cur_A, cur_b, -1, m=cur_m, keep=keep, flags=flags, first=first, abs_tol=abs_tol)
+        mo_max = max(int(cnt.max().item()), 1)
+        Ao, bo, mo = fm_emit(cur_A, cur_b, -1, mo_max, m=cur_m, keep=keep, flags=flags, first=first, abs_tol=abs_tol)
+        st["launches"] += 2
+        mo_h = mo.cpu().numpy()
+        Ah, bh = Ao.cpu().numpy(), bo.cpu().numpy()
+        st["d2h"] += 4 * idx.size + 4 + Ah.nbytes + bh.nbytes
+        out.append((idx, Ah, bh, mo_h, min_h))   # the polytopes finished here, packed
+    else:
+        out.append(None)
+    return out
+
+
+def _fm_flags(fl):
+    """reduce_batch flags -> 0 go on, 1 empty (Polytope()), 2 re-examine on the host, 3 reduce() raises (RF_LPFAIL)."""
+    fl = np.asarray(fl)
+    dead = np.zeros(fl.shape, np.int8)
+    dead[(fl & _lib.RF_EMPTY) != 0] = 1
+    dead[(fl & 32) != 0] = 2   # RF_F1OPEN: the verified path of polytope._reduce_many decides
+    dead[(fl & _lib.RF_LPFAIL) != 0] = 3
+    return dead
+
+
+def projection_batch(A, b, dim, m=None, abs_tol=1e-7, minrep=False):
+    """projection(P_k, dim, solver="fm") (polytope/polytope.py:1698-1769, :1911-1952) of B packed polytopes whose rows are
+    what Polytope(...).A / .b hold.  A[B, m_max, d], b[B, m_max], m[B] as numpy arrays or CUDA tensors; `dim`: the
+    coordinates kept, 1-based, as the reference takes them; minrep: the inputs are minimal representations (no first
+    reduce).
+
+    -> dict(A[B, mo, len(dim)], b[B, mo], m[B], status[B], routed, reexamined).  status: 0 the rows of the projection;
+    1 Polytope(); 2 the input returned unchanged (no rows, or len(dim) > d; A / b then hold nothing); 3 the reference
+    raises IndexError here (its first reduce() returned Polytope()); 4 reduce() raises RuntimeError here (RF_LPFAIL).
+    abs_tol is the existence LP's, as in projection(); the eliminations and reductions use the module's 1e-7, as
+    projection_fm does when projection() calls it.  `routed`: polytopes whose step formed more rows than
+    the fused reduce takes and went on through the host's reduce(); `reexamined`: polytopes the fused reduce handed to
+    the verified Chebyshev LP (RF_F1OPEN), which went on on the host likewise.  Numpy in, numpy out; tensors in, tensors
+    out (on A's device).
+    """
+    import torch
+    from . import polytope as _poly
+    numpy_in = not _is_torch(A)
+    if numpy_in:
+        dev = torch.device("cuda", torch.cuda.current_device())
+        At = torch.as_tensor(_np(A), device=dev)
+        bt = torch.as_tensor(_np(b), device=dev)
+    else:
+        dev = A.device
+        At, bt = A.to(torch.float64).contiguous(), b.to(torch.float64).contiguous()
+    if At.ndim != 3:
+        raise ValueError("A must be [B, m_max, d]")
+    B, m_max, d = At.shape
+    bt = bt.reshape(B, m_max)
+    m_h = np.full(B, m_max, np.int64) if m is None else (
+        np.asarray(m.cpu().numpy() if _is_torch(m) else m, dtype=np.int64).reshape(B))
+    dim = np.array(dim).flatten()
+    new_dim = dim - 1
+    del_dim = np.setdiff1d(range(d), new_dim)
+    status = np.full(B, PROJ_INPUT, np.int32)
+    fm_stats.clear()
+    fm_stats["steps"] = []
+    t_exists = time.perf_counter()
+    outs = [None] * B
+    routed, reexamined = [0], [0]
+    live = np.nonzero(m_h > 0)[0] if d >= len(dim) else np.zeros(0, np.int64)
+    block = None
+    if live.size:
+        # fewer rows than dimensions: zero rows up to d (ref :1748-1755)
+        rows = max(m_max, d)
+        li = torch.as_tensor(live, device=dev)
+        A2 = torch.zeros((live.size, rows, d), dtype=torch.float64, device=dev)
+        b2 = torch.zeros((live.size, rows), dtype=torch.float64, device=dev)
+        A2[:, :m_max] = At.index_select(0, li)
+        b2[:, :m_max] = bt.index_select(0, li)
+        m2 = np.maximum(m_h[live], d)
+        short = np.nonzero(m_h[live] < d)[0]
+        if short.size:
+            r = torch.arange(rows, device=dev)[None, :] >= torch.as_tensor(m_h[live][short], device=dev)[:, None]
+            st_ = torch.as_tensor(short, device=dev)
+            A2[st_] = torch.where(r[:, :, None], torch.zeros((), dtype=torch.float64, device=dev), A2[st_])
+            b2[st_] = torch.where(r, torch.zeros((), dtype=torch.float64, device=dev), b2[st_])
+        mt = torch.as_tensor(m2.astype(np.int32), device=dev)
+        # does the projection exist: the Chebyshev-style LP with the reference's norm (squared, and zeroed on the ROWS
+        # del_dim: ref :1757-1766)
+        norm = (A2 * A2).sum(2)
+        norm[:, torch.as_tensor(del_dim, device=dev)] = 0
+        c = torch.zeros((live.size, d + 1), dtype=torch.float64, device=dev)
+        c[:, d] = -1
+        sol = lpsolve_batch(c, torch.cat([A2, norm[:, :, None]], 2).contiguous(), b2, m=mt)
+        lp_st = sol["status"].cpu().numpy()
+        r_h = sol["x"][:, d].cpu().numpy()
+        fm_stats["steps"].append(dict(step="exists", launches=1, d2h=12 * live.size, t=t_exists))
+        empty = (lp_st != 0) | ~(r_h >= abs_tol)
+        status[live[empty]] = PROJ_EMPTY
+        go = np.nonzero(~empty)[0]
+        cols = [int(i) for i in -np.sort(-del_dim)]
+
+        def on_host(k, poly, cols_left, first):
+            kk = int(live[go[k]])
+            if first == "reduce":
+                routed[0] += 1
+            else:
+                reexamined[0] += 1
+            try:
+                q = _poly._fm_host_continue(poly, cols_left, _REDUCE_TOL, first)
+            except IndexError:
+                outs[kk] = (PROJ_RAISES, None, None, False)
+                return
+            except RuntimeError:
+                outs[kk] = (PROJ_LPFAIL, None, None, False)
+                return
+            outs[kk] = (PROJ_OK, q.A, q.b, q.minrep) if q.A.size > 0 else (PROJ_EMPTY, None, None, False)
+        if go.size:
+            gi = torch.as_tensor(go, device=dev)
+            res = _fm_batch(A2.index_select(0, gi), b2.index_select(0, gi), mt.index_select(0, gi), cols, _REDUCE_TOL,
+                            np.full(go.size, bool(minrep)), on_host, fm_stats["steps"])
+            block = res.pop()
+            for t, r in enumerate(res):
+                if r is not None:
+                    outs[int(live[go[t]])] = r
+        for k in range(B):
+            if outs[k] is not None:
+                status[k] = outs[k][0]
+    t_pack = time.perf_counter()
+    dn = len(dim) if d >= len(dim) else d
+    mo = np.zeros(B, np.int32)
+    for k in range(B):
+        if outs[k] is not None and outs[k][0] == PROJ_OK:
+            mo[k] = outs[k][1].shape[0]
+    if block is not None:
+        where = live[go[block[0]]]
+        mo[where] = block[3]
+        status[where] = PROJ_OK
+    mo_max = max(int(mo.max()) if B else 0, 1)
+    Ao = np.zeros((B, mo_max, dn))
+    bo = np.zeros((B, mo_max))
+    if block is not None:
+        w = block[1].shape[1]
+        Ao[where, :w] = block[1]
+        bo[where, :w] = block[2]
+    for k in range(B):
+        if outs[k] is not None and mo[k]:
+            Ao[k, :mo[k]] = outs[k][1]
+            bo[k, :mo[k]] = outs[k][2]
+    res = dict(A=Ao, b=bo, m=mo, status=status, routed=routed[0], reexamined=reexamined[0])
+    # host wall time of each phase (each ends in a device-to-host copy, i.e. a synchronisation): step k runs from its own
+    # start to the next one's; `pack` is the output's assembly on the host
+    steps = fm_stats["steps"]
+    ends = [st_["t"] for st_ in steps[1:]] + [t_pack]
+    for st_, end in zip(steps, ends):
+        st_["ms"] = (end - st_.pop("t")) * 1e3
+    steps.append(dict(step="pack", launches=0, d2h=0, ms=(time.perf_counter() - t_pack) * 1e3))
+    if not numpy_in:
+        for key in ("A", "b", "m", "status"):
+            res[key] = torch.as_tensor(res[key], device=dev)
+    return res

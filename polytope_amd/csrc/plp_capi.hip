@@ -1087,6 +1087,104 @@ int plp_hull_reassign_dev(plp_ctx* ctx, void* stream, int64_t N, int d, const do
     return check_launch("hull_reassign_kernel");
 }
 
+// ------------------------------------------------------------------------------- Fourier-Motzkin step
+namespace {
+int fm_check(plp_ctx* ctx, int64_t B, int m_max, int d, const double* A, const double* b, const uint64_t* keep, int kw,
+             int col) {
+    if (!ctx) return fail(PLP_EINVAL, "ctx is NULL");
+    if (B < 0 || m_max < 0 || d < 1 || (keep && kw < (m_max + 63) / 64)) return fail(PLP_EINVAL, "bad sizes");
+    if (B > 0 && m_max > 0 && (!A || !b)) return fail(PLP_EINVAL, "NULL pointer");
+    if (d > plp::MAX_D) return fail(PLP_EUNSUPPORTED, "d=%d > 16", d);
+    if (col >= d || (col >= 0 && d < 2)) return fail(PLP_EINVAL, "column %d of a polytope in dimension %d", col, d);
+    if (plp::fm_lds_bytes(m_max, d) > 160 * 1024)
+        return fail(PLP_EUNSUPPORTED, "fm: a polytope of %d rows in dimension %d does not fit the LDS of a CU", m_max, d);
+    return PLP_OK;
+}
+}  // namespace
+
+int plp_fm_count_dev(plp_ctx* ctx, void* stream, int64_t B, int m_max, int d, const double* A, const double* b,
+                     const int32_t* m, const uint64_t* keep, int kw, const int32_t* flags, int col, int first,
+                     double abs_tol, int32_t* count) {
+    int rc = fm_check(ctx, B, m_max, d, A, b, keep, kw, col);
+    if (rc) return rc;
+    if (B == 0) return PLP_OK;
+    if (!count) return fail(PLP_EINVAL, "NULL pointer");
+    if (plp::launch_fm(0, B, m_max, d, A, b, m, reinterpret_cast<const unsigned long long*>(keep), kw, flags, col, first,
+                       abs_tol, count, 0, nullptr, nullptr, nullptr, (hipStream_t)stream))
+        return fail(PLP_EUNSUPPORTED, "fm: unsupported size");
+    return check_launch("fm_kernel (count)");
+}
+
+int plp_fm_emit_dev(plp_ctx* ctx, void* stream, int64_t B, int m_max, int d, const double* A, const double* b,
+                    const int32_t* m, const uint64_t* keep, int kw, const int32_t* flags, int col, int first,
+                    double abs_tol, int mo_max, double* A_out, double* b_out, int32_t* m_out) {
+    int rc = fm_check(ctx, B, m_max, d, A, b, keep, kw, col);
+    if (rc) return rc;
+    if (B == 0) return PLP_OK;
+    if (mo_max < 0) return fail(PLP_EINVAL, "bad sizes");
+    if (!m_out || (mo_max > 0 && (!A_out || !b_out))) return fail(PLP_EINVAL, "NULL pointer");
+    if (plp::launch_fm(1, B, m_max, d, A, b, m, reinterpret_cast<const unsigned long long*>(keep), kw, flags, col, first,
+                       abs_tol, nullptr, mo_max, A_out, b_out, m_out, (hipStream_t)stream))
+        return fail(PLP_EUNSUPPORTED, "fm: unsupported size");
+    return check_launch("fm_kernel (emit)");
+}
+
+namespace {
+// the host-pointer pair: inputs staged through the arena, outputs copied back (count: mo_max < 0)
+int fm_host(plp_ctx* ctx, int64_t B, int m_max, int d, const double* A, const double* b, const int32_t* m,
+            const uint64_t* keep, int kw, const int32_t* flags, int col, int first, double abs_tol, int32_t* count,
+            int mo_max, double* A_out, double* b_out, int32_t* m_out) {
+    int rc = fm_check(ctx, B, m_max, d, A, b, keep, kw, col);
+    if (rc) return rc;
+    if (B == 0) return PLP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int dout = col >= 0 ? d - 1 : d;
+    const size_t nA = (size_t)B * m_max * d, nb = (size_t)B * m_max, nk = keep ? (size_t)B * kw : 0;
+    const size_t mo = mo_max > 0 ? (size_t)mo_max : 0;
+    rc = ensure_arena(ctx, pad(nA * 8) + pad(nb * 8) + pad(nk * 8) + pad((size_t)B * 4) * 3 + pad((size_t)B * mo * dout * 8) +
+                               pad((size_t)B * mo * 8) + 4096);
+    if (rc) return rc;
+    Arena a(ctx);
+    double* dA = a.take<double>(nA);
+    double* db = a.take<double>(nb);
+    int32_t* dm = a.take<int32_t>(B);
+    uint64_t* dk = a.take<uint64_t>(nk);
+    int32_t* dfl = a.take<int32_t>(B);
+    int32_t* dout_n = a.take<int32_t>(B);
+    double* dAo = a.take<double>((size_t)B * mo * dout);
+    double* dbo = a.take<double>((size_t)B * mo);
+    hipStream_t st = ctx->stream;
+    rc = copy_in(ctx, st, {{dA, A, nullptr, nA * 8}, {db, b, nullptr, nb * 8}, {dm, m, nullptr, m ? (size_t)B * 4 : 0},
+                           {dk, keep, nullptr, nk * 8}, {dfl, flags, nullptr, flags ? (size_t)B * 4 : 0}});
+    if (rc) return rc;
+    if (count) {
+        rc = plp_fm_count_dev(ctx, st, B, m_max, d, dA, db, m ? dm : nullptr, keep ? dk : nullptr, kw,
+                              flags ? dfl : nullptr, col, first, abs_tol, dout_n);
+        if (rc) return rc;
+        return copy_out(ctx, st, {{dout_n, nullptr, count, (size_t)B * 4}});
+    }
+    rc = plp_fm_emit_dev(ctx, st, B, m_max, d, dA, db, m ? dm : nullptr, keep ? dk : nullptr, kw, flags ? dfl : nullptr,
+                         col, first, abs_tol, mo_max, dAo, dbo, dout_n);
+    if (rc) return rc;
+    return copy_out(ctx, st, {{dAo, nullptr, A_out, (size_t)B * mo * dout * 8}, {dbo, nullptr, b_out, (size_t)B * mo * 8},
+                              {dout_n, nullptr, m_out, (size_t)B * 4}});
+}
+}  // namespace
+
+int plp_fm_count(plp_ctx* ctx, int64_t B, int m_max, int d, const double* A, const double* b, const int32_t* m,
+                 const uint64_t* keep, int kw, const int32_t* flags, int col, int first, double abs_tol, int32_t* count) {
+    if (!count && B > 0) return fail(PLP_EINVAL, "NULL pointer");
+    return fm_host(ctx, B, m_max, d, A, b, m, keep, kw, flags, col, first, abs_tol, count, -1, nullptr, nullptr, nullptr);
+}
+
+int plp_fm_emit(plp_ctx* ctx, int64_t B, int m_max, int d, const double* A, const double* b, const int32_t* m,
+                const uint64_t* keep, int kw, const int32_t* flags, int col, int first, double abs_tol, int mo_max,
+                double* A_out, double* b_out, int32_t* m_out) {
+    if (mo_max < 0) return fail(PLP_EINVAL, "bad sizes");
+    if (B > 0 && (!m_out || (mo_max > 0 && (!A_out || !b_out)))) return fail(PLP_EINVAL, "NULL pointer");
+    return fm_host(ctx, B, m_max, d, A, b, m, keep, kw, flags, col, first, abs_tol, nullptr, mo_max, A_out, b_out, m_out);
+}
+
 }  // extern "C"
 
 struct plp_hull {

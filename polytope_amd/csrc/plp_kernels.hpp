@@ -47,6 +47,12 @@ int launch_cheby_gather_lds(int d, int m_cap, long long nlp, const int* off, con
 
 // fused reduce() of polytopes with more than 64 rows: rows and dictionary in LDS, keep = ceil(m_max / 64) words per
 // polytope (plp_lds.hip); returns 2 when a polytope does not fit the CU's LDS
+// one Fourier-Motzkin elimination step (plp_fm.hip): emit = 0 writes count[] (|N| + |P| |Q| per polytope), emit = 1 the
+// rows into Aout[B][mo_max][d - (col >= 0)], bout, mout (-1: more than mo_max rows).  2: unsupported size
+int launch_fm(int emit, long long B, int m_max, int d, const double* A, const double* b, const int* mrows,
+              const unsigned long long* keep, int kw, const int* flags, int col, int first, double abs_tol, int* count,
+              int mo_max, double* Aout, double* bout, int* mout, hipStream_t st);
+size_t fm_lds_bytes(int m_max, int d);
 int launch_reduce_lds(long long B, int m_max, int d, const double* A, const double* b, const int* mrows, double abs_tol,
                       unsigned long long* keep, int* flags, double* r, double* xc, int* nlp, hipStream_t st);
 

@@ -19,7 +19,9 @@ loop, this module collects them and issues ONE batched call into the HIP engine
 With any other backend name the LPs go through `solvers.lpsolve` one by one, as in the
 reference.  There is no silent fallback between backends.
 
-Out of scope here: projection, rotation, plotting, grid helpers.
+    projection (fm)             Fourier-Motzkin steps on the device, fused with the reduce   (ref :1698-1952)
+
+Out of scope here: rotation, plotting, grid helpers; projection's "esp" solver (needs glpk).
 """
 import logging
 import warnings
@@ -251,6 +253,10 @@ class Polytope(object):
                             "First element of an interval must not be larger than the second.")
         n = intervals.shape[0]
         return cls(np.vstack([np.eye(n), -np.eye(n)]), np.hstack([intervals[:, 1], -intervals[:, 0]]), minrep=True)
+
+    def project(self, dim, solver=None, abs_tol=ABS_TOL, verbose=0):
+        """Projection onto the coordinates `dim` (1-based): see `projection` (ref :356-362)."""
+        return projection(self, dim, solver, abs_tol, verbose)
 
     def scale(self, factor):
         self.b = factor * self.b
@@ -2052,3 +2058,282 @@ def separate(reg1, abs_tol=ABS_TOL):
 def simplices2polytopes(points, triangles):
     """Convert a simplicial mesh to polytopes in H-representation (ref :2419-2439): one qhull per simplex."""
     return [qhull(points[triangle, :]) for triangle in triangles]
+
+
+# ====================================================================================== projection
+def projection(poly1, dim, solver=None, abs_tol=ABS_TOL, verbose=0):
+    """Projection of a polytope onto the coordinates `dim` (1-based), ref :1698-1794.
+
+    Solvers: "fm" (Fourier-Motzkin), "exthull" (vertex projection), "iterhull" (iterative hull), "esp" (needs glpk, which
+    is not available: raises).  Without one (or with an unknown name, which logs a warning) the reference's choice:
+    <= 2 deleted dimensions fm, <= 4 dimensions exthull, else iterhull.  On 'hip' the fm steps run on the device
+    (polytope_amd.batch: the Fourier-Motzkin step kernels and the fused reduce); the existence LP and everything before
+    it (the early return, the zero-padding of a polytope with fewer rows than dimensions, which is written back into
+    `poly1`) as in the reference."""
+    if isinstance(poly1, Region):
+        ret = Polytope()
+        for i in range(len(poly1.list_poly)):
+            p = projection(poly1.list_poly[i], dim, solver=solver, abs_tol=abs_tol)
+            ret = ret + p   # (Polytope has no `+`: TypeError, as in the reference)
+        return ret
+    if (poly1.dim < len(dim)) or is_empty(poly1):
+        return poly1
+    poly_dim = poly1.dim
+    dim = np.array(dim)
+    org_dim = range(poly_dim)
+    new_dim = dim.flatten() - 1
+    del_dim = np.setdiff1d(org_dim, new_dim)
+    mA, nA = poly1.A.shape
+    if mA < poly_dim:
+        logger.warning("fewer rows in A: " + str(mA) + ", than polytope dimension: " + str(poly_dim))
+        A = poly1.A.copy()
+        poly1.A = np.zeros((poly_dim, poly_dim))
+        poly1.A[0:mA, 0:nA] = A
+        poly1.b = np.hstack([poly1.b, np.zeros(poly_dim - mA)])
+    # does the projection exist: a Chebyshev-style LP with the squared norms, zeroed on the ROWS del_dim (ref :1757-1769)
+    norm = np.sum(poly1.A * poly1.A, axis=1).flatten()
+    norm[del_dim] = 0
+    c = np.zeros(len(org_dim) + 1, dtype=float)
+    c[len(org_dim)] = -1
+    G = np.hstack([poly1.A, norm.reshape(norm.size, 1)])
+    h = poly1.b
+    sol = lpsolve(c, G, h)
+    if sol["status"] != 0:
+        return Polytope()
+    if sol["x"][-1] < abs_tol:
+        return Polytope()
+    if solver == "esp":
+        return projection_esp(poly1, new_dim, del_dim)
+    elif solver == "exthull":
+        return projection_exthull(poly1, new_dim)
+    elif solver == "fm":
+        return projection_fm(poly1, new_dim, del_dim)
+    elif solver == "iterhull":
+        return projection_iterhull(poly1, new_dim)
+    elif solver is not None:
+        logger.warning('unrecognized projection solver "' + str(solver) + '".')
+    if len(del_dim) <= 2:
+        return projection_fm(poly1, new_dim, del_dim)
+    elif len(org_dim) <= 4:
+        return projection_exthull(poly1, new_dim)
+    else:
+        return projection_iterhull(poly1, new_dim)
+
+
+def _fm_combine_host(poly, i, abs_tol=ABS_TOL):
+    """One elimination of projection_fm as the reference writes it (ref :1925-1948): P x Q combinations through np.dot."""
+    positive = np.nonzero(poly.A[:, i] > abs_tol)[0]
+    negative = np.nonzero(poly.A[:, i] < -abs_tol)[0]
+    null = np.nonzero(np.abs(poly.A[:, i]) < abs_tol)[0]
+    nr = len(null) + len(positive) * len(negative)
+    nc = np.shape(poly.A)[0]
+    C = np.zeros([nr, nc])
+    A = poly.A[:, i].copy()
+    row = 0
+    for j in positive:
+        for k in negative:
+            C[row, j] = -A[k]
+            C[row, k] = A[j]
+            row += 1
+    for j in null:
+        C[row, j] = 1
+        row += 1
+    keep_dim = np.setdiff1d(range(poly.A.shape[1]), np.array([i]))
+    return Polytope(np.dot(C, poly.A)[:, keep_dim], np.dot(C, poly.b))
+
+
+def _fm_eliminate_dev(poly, i, first, abs_tol=ABS_TOL):
+    """The same elimination on the device (B = 1; csrc/plp_fm.hip) from the rows of `poly` as they stand; `first`: one
+    constructor pass before (the copy() of the first step)."""
+    from .batch import fm_count, fm_emit
+    A = np.ascontiguousarray(poly.A, dtype=float)[None]
+    b = np.ascontiguousarray(poly.b, dtype=float)[None]
+    n = int(fm_count(A, b, int(i), first=first, abs_tol=abs_tol)[0])
+    Ao, bo, mo = fm_emit(A, b, int(i), max(n, 1), first=first, abs_tol=abs_tol)
+    k = int(mo[0])
+    return Polytope(Ao[0, :k], bo[0, :k], normalize=False)
+
+
+def _fm_dev_fits(poly):
+    from .batch import MAX_D
+    return poly.A.ndim == 2 and 2 <= poly.A.shape[1] <= MAX_D and poly.A.shape[0] >= 1 and np.all(np.isfinite(poly.b))
+
+
+def _fm_host_continue(poly, cols, abs_tol, start):
+    """projection_fm from the middle, per polytope: `start` "reduce" -- `poly` is an elimination's output (is_fulldim,
+    reduce, then the columns `cols`); None -- `poly` is the input (reduce, copy, then `cols`).  Eliminations on the
+    device as in the batch, reductions through reduce()."""
+    if start is None:
+        poly = reduce(poly)
+        poly.A[:, cols[0]] if len(cols) else None   # (reduce() returned Polytope(): IndexError, as the reference)
+        first = True
+    else:
+        if not is_fulldim(poly):
+            return Polytope()
+        poly = reduce(poly)
+        first = False
+    for i in cols:
+        poly = _fm_eliminate_dev(poly, i, first, abs_tol)
+        first = False
+        if not is_fulldim(poly):
+            return Polytope()
+        poly = reduce(poly)
+    if first:
+        poly = poly.copy()
+    return poly
+
+
+def projection_fm(poly1, new_dim, del_dim, abs_tol=ABS_TOL):
+    """Fourier-Motzkin elimination of the columns del_dim, the last first (ref :1911-1952).  On 'hip' the steps are the
+    device driver of polytope_amd.batch with one polytope; otherwise the reference's loop over reduce() / is_fulldim()."""
+    del_dim = -np.sort(-np.asarray(del_dim))
+    if not poly1.minrep:
+        poly1 = reduce(poly1)
+    if _use_hip() and _fm_dev_fits(poly1):
+        return _projection_fm_dev(poly1, [int(i) for i in del_dim], abs_tol)
+    poly = poly1.copy()
+    for i in del_dim:
+        poly = _fm_combine_host(poly, i, abs_tol)
+        if not is_fulldim(poly):
+            return Polytope()
+        poly = reduce(poly)
+    return poly
+
+
+def _projection_fm_dev(poly1, cols, abs_tol):
+    import torch
+    from .batch import _fm_batch, PROJ_OK, PROJ_RAISES, PROJ_LPFAIL
+    if not cols:
+        return poly1.copy()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    m, d = poly1.A.shape
+    A = torch.as_tensor(np.ascontiguousarray(poly1.A, dtype=float)[None], device=dev)
+    b = torch.as_tensor(np.ascontiguousarray(poly1.b, dtype=float)[None], device=dev)
+    mt = torch.full((1,), m, dtype=torch.int32, device=dev)
+    host = {}
+
+    def on_host(k, poly, cols_left, start):
+        host[k] = _fm_host_continue(poly, cols_left, abs_tol, start)
+    res = _fm_batch(A, b, mt, cols, abs_tol, [True], on_host)
+    if res[1] is not None:   # finished in the last step
+        _, Ao, bo, mo, minrep = res[1]
+        return Polytope(Ao[0, :mo[0]], bo[0, :mo[0]], minrep=bool(minrep[0]), normalize=False)
+    if res[0] is None:
+        return host[0]
+    st, Ao, bo, minrep = res[0]
+    if st == PROJ_LPFAIL:
+        raise RuntimeError("bounding_box: an LP of the box prefilter of `reduce` ended with status 1 or 4")
+    if st == PROJ_RAISES:
+        raise IndexError("too many indices for array: array is 1-dimensional, but 2 were indexed")
+    if st != PROJ_OK:
+        return Polytope()
+    return Polytope(Ao, bo, minrep=bool(minrep), normalize=False)
+
+
+def projection_exthull(poly1, new_dim):
+    """Vertex projection (ref :1955-1965): the hull of the projected vertices, reduced."""
+    vert = extreme(poly1)
+    if vert is None:
+        return Polytope(fulldim=False, minrep=True)
+    return reduce(qhull(vert[:, new_dim]))
+
+
+def _iterhull_lp_failed(sol):
+    raise RuntimeError(("`polytope.solvers.lpsolve` returned:  {v}\n"
+                        "its docstring describes return values").format(v=sol))
+
+
+def projection_iterhull(poly1, new_dim, max_iter=1000, verbose=0, abs_tol=ABS_TOL):
+    """Iterative hull (ref :1968-2098): the same random directions from np.random in the same order, the same rounded
+    cache keys; the facet LPs of one iteration that the cache does not answer go down as one batch (lpsolve_many), each
+    key once -- what the reference's loop, which fills the cache as it goes, solves."""
+    r, xc = cheby_ball(poly1)
+    org_dim = poly1.A.shape[1]
+    if len(new_dim) == 1:
+        f1 = np.zeros(poly1.A.shape[1])
+        f1[new_dim] = 1
+        sol = lpsolve(f1, poly1.A, poly1.b)
+        if sol["status"] != 0:
+            _iterhull_lp_failed(sol)
+        vert1 = sol["x"]
+        sol = lpsolve(np.negative(f1), poly1.A, poly1.b)
+        if sol["status"] != 0:
+            _iterhull_lp_failed(sol)
+        vert2 = sol["x"]
+        return qhull(np.vstack([vert1, vert2]), abs_tol=abs_tol)
+    OK = False
+    cnt = 0
+    Vert = None
+    while not OK:
+        cnt += 1
+        if cnt > max_iter:
+            raise Exception("iterative_hull: could not find starting simplex")
+        f1 = np.random.rand(len(new_dim)).flatten() - 0.5
+        f = np.zeros(org_dim)
+        f[new_dim] = f1
+        sol = lpsolve(np.negative(f), poly1.A, poly1.b)
+        xopt = np.array(sol["x"]).flatten()
+        if Vert is None:
+            Vert = xopt.reshape(1, xopt.size)
+        else:
+            k = np.nonzero(Vert[:, new_dim[0]] == xopt[new_dim[0]])[0]
+            for j in new_dim[range(1, len(new_dim))]:
+                ii = np.nonzero(Vert[k, j] == xopt[j])[0]
+                k = k[ii]
+                if k.size == 0:
+                    break
+            if k.size == 0:
+                Vert = np.vstack([Vert, xopt])
+        if Vert.shape[0] > len(new_dim):
+            u, s, v = np.linalg.svd(np.transpose(Vert[:, new_dim] - Vert[0, new_dim]))
+            rank = np.sum(s > abs_tol * 10)
+            if rank == len(new_dim):
+                OK = True
+    cnt = 0
+    P1 = qhull(Vert[:, new_dim], abs_tol=abs_tol)
+    HP = None
+    while True:
+        cnt += 1
+        if cnt > max_iter:
+            raise Exception("iterative_hull: maximum number of iterations reached")
+        seen = set() if HP is None else {tuple(row) for row in HP[:, :P1.A.shape[1] + 1]}
+        todo = []   # (f1, f2) of the facets whose key is neither cached nor already asked for in this iteration
+        for ind in range(P1.A.shape[0]):
+            f1 = np.round(P1.A[ind, :] / abs_tol) * abs_tol
+            f2 = np.hstack([np.round(P1.A[ind, :] / abs_tol) * abs_tol, np.round(P1.b[ind] / abs_tol) * abs_tol])
+            key = tuple(f2)
+            if key in seen:
+                continue
+            seen.add(key)
+            todo.append((f1, f2))
+        cs = []
+        for f1, _ in todo:
+            f = np.zeros(poly1.A.shape[1])
+            f[new_dim] = f1
+            cs.append(np.negative(f))
+        sols = solvers.lpsolve_many(cs, [poly1.A] * len(cs), [poly1.b] * len(cs))
+        for (f1, f2), sol in zip(todo, sols):
+            if sol["status"] != 0:
+                logger.error("iterhull: LP failure")
+                seen.discard(tuple(f2))
+                continue
+            xopt = np.array(sol["x"]).flatten()
+            add = np.hstack([f2, np.round(xopt / abs_tol) * abs_tol])
+            HP = add.reshape(1, add.size) if HP is None else np.vstack([HP, add])
+            Vert = np.vstack([Vert, xopt])
+        P2 = qhull(Vert[:, new_dim], abs_tol=abs_tol)
+        OK = 1
+        for i in range(np.shape(Vert)[0]):
+            if not P1.contains(np.transpose([Vert[i, new_dim]]), abs_tol=abs_tol):
+                OK = 0
+                break
+        if OK == 1:
+            return P2
+        P1 = P2
+
+
+def projection_esp(poly1, keep_dim, del_dim):
+    """Equality set projection (ref :2101-2114, esp.py): needs glpk, which this package does not bind."""
+    if "glpk" not in solvers.installed_solvers:
+        raise Exception("projection_esp error: Equality set projection requires `cvxopt.glpk` to run.")
+    raise Exception("projection_esp: not provided")
