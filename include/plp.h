@@ -203,6 +203,31 @@ int plp_fm_emit_dev(plp_ctx *ctx, void *stream, int64_t B, int m_max, int d, con
                     double abs_tol, int mo_max, double *A_out, double *b_out, int32_t *m_out);
 
 /*
+ * The hit counts of volume() (polytope/polytope.py:1529-1594, lines :1586-1591) for B packed polytopes: how many of
+ * the N uniform samples of each polytope's bounding box lie strictly inside it.  The samples are the ones
+ * numpy.random.default_rng(seed).random((d, N)) draws -- PCG64 (XSL-RR 128/64), element (i, j) at stream position
+ * i * N + j -- generated on the device by exact jump-ahead: no sample crosses the bus.
+ * In:  A[B][m_max][d], b[B][m_max], m[B] (NULL = m_max) as for plp_reduce_batch;
+ *      lb[B][d], ub[B][d]: the boxes (plp_bbox_batch);
+ *      state[B][2], inc[B][2]: per polytope the generator's 128-bit state and increment, low word first
+ *      (numpy.random.PCG64(seed).state['state']);
+ *      N: samples per polytope, 1 <= N <= 2^31 - 1 (else PLP_EINVAL).
+ * Out: hits[B]: samples x = lb + r * (ub - lb) (a multiplication, then an addition) with (s - b_i) < 0 for every row i,
+ *      s = a_i0 x_0 and then s = fma(a_ik, x_k, s) for k = 1 .. d - 1: plp_contains' arithmetic with abs_tol = 0, so the
+ *      count is the one plp_contains gives on the uploaded samples.  The volume is prod(ub - lb) * hits / N.
+ *      flags[B]: 0, or PLP_VF_NONFINITE (a bound of the box is inf / nan) | PLP_VF_NOROWS (m = 0): not sampled, hits = 0.
+ * d <= 16 and m_max <= 64, else PLP_EUNSUPPORTED.
+ */
+#define PLP_VF_NONFINITE 1
+#define PLP_VF_NOROWS 2
+int plp_volume_hits(plp_ctx *ctx, int64_t B, int m_max, int d, const double *A, const double *b, const int32_t *m,
+                    const double *lb, const double *ub, const uint64_t *state, const uint64_t *inc, int64_t N,
+                    uint32_t *hits, int32_t *flags);
+int plp_volume_hits_dev(plp_ctx *ctx, void *stream, int64_t B, int m_max, int d, const double *A, const double *b,
+                        const int32_t *m, const double *lb, const double *ub, const uint64_t *state,
+                        const uint64_t *inc, int64_t N, uint32_t *hits, int32_t *flags);
+
+/*
  * Containment of N points in P polytopes:  all_i( A_p[i,:].x - b_p[i] < abs_tol ).
  * Replaces: Polytope.contains (polytope/polytope.py:206-218), Region.contains (:732-746),
  *           is_inside (:1017-1029), __contains__ (:191-204, :723-730).

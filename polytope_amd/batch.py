@@ -347,6 +347,154 @@ def contains_batch(A, b, X, abs_tol=1e-7, m=None, region=True):
     return out
 
 
+# flags of volume_batch (include/plp.h: PLP_VF_*)
+VF_NONFINITE, VF_NOROWS = 1, 2
+_VOLUME_MAX_N = 2 ** 31 - 1
+
+
+def _volume_nsamples(d, nsamples=None):
+    """The number of samples volume() draws in dimension d (ref :1565-1584): 50 / 500 / 3000 / 10000 by dimension unless
+    `nsamples` is given; the reference's two ValueErrors for nsamples < 1 and for a non-integer."""
+    N = {1: 50, 2: 500, 3: 3000}.get(d, 10000)
+    if nsamples is not None and nsamples < 1:
+        raise ValueError("`nsamples` must be >= 1, given:  {v}".format(v=nsamples))
+    if nsamples is not None:
+        N = nsamples
+    if N != int(N):
+        raise ValueError("it appears that a noninteger number of samples has been given, namely:  {v}".format(
+            v=nsamples))
+    return N
+
+
+def _is_int(v):
+    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+
+
+def _volume_seeds(seed, B):
+    """The seed of each polytope: None -> B spawned children of one fresh SeedSequence; an int -> that int B times (every
+    polytope draws the same stream, as B calls of volume(P, seed=seed) do); B ints -> one each."""
+    if seed is None:
+        return list(np.random.SeedSequence().spawn(B))
+    if _is_int(seed):
+        if seed < 0:
+            raise ValueError("`seed` must be a non-negative integer, given:  {v}".format(v=seed))
+        return [int(seed)] * B
+    if isinstance(seed, (str, bytes)) or not hasattr(seed, "__len__"):
+        raise TypeError("`seed` must be None, an int or a sequence of B ints, got %s" % type(seed).__name__)
+    seeds = list(seed)
+    if len(seeds) != B:
+        raise ValueError("`seed`: %d seeds for %d polytopes" % (len(seeds), B))
+    for v in seeds:
+        if not _is_int(v):
+            raise TypeError("`seed` must be None, an int or a sequence of B ints, got an element of type %s"
+                            % type(v).__name__)
+        if v < 0:
+            raise ValueError("`seed` must be a non-negative integer, given:  {v}".format(v=v))
+    return [int(v) for v in seeds]
+
+
+def _pcg64_words(seeds):
+    """state[B, 2], inc[B, 2] (uint64, low word first) of np.random.PCG64(seed) -- what default_rng(seed) starts from."""
+    B = len(seeds)
+    words = np.empty((2, B, 2), np.uint64)
+    memo = {}
+    for k, sd in enumerate(seeds):
+        key = sd if isinstance(sd, int) else id(sd)
+        if key not in memo:
+            st = np.random.PCG64(sd).state["state"]
+            memo[key] = [(st[n] & 0xFFFFFFFFFFFFFFFF, st[n] >> 64) for n in ("state", "inc")]
+        words[0, k], words[1, k] = memo[key]
+    return words[0], words[1]
+
+
+def volume_batch(A, b, m=None, nsamples=None, seed=None, lb=None, ub=None):
+    """Monte-Carlo volume of B polytopes (volume, polytope.py:1529-1594): uniform samples in each polytope's bounding box,
+    fraction strictly inside, times the volume of the box.  The samples are the ones the reference draws --
+    np.random.default_rng(seed).random((d, N)), numpy's PCG64 stream -- generated on the device by jump-ahead, so no sample
+    is uploaded and 4 bytes per polytope come back.
+    `volume_batch(...)['volume'][k] == volume(P_k, nsamples, seed_k)` bit for bit on 'hip'.
+
+    nsamples: None = the reference's table by dimension (50 / 500 / 3000 / 10000), else one N for the call.
+    seed: None (every polytope a spawned child of one fresh np.random.SeedSequence), an int (every polytope draws the SAME
+    stream, as B calls of volume(P, seed=seed) do) or B ints.
+    lb, ub [B, d]: the bounding boxes; without them bbox_batch runs first and its device arrays are handed on.
+
+    -> dict(volume[B], hits[B], nsamples, lb[B, d], ub[B, d], flags[B], seeds): numpy in, numpy out; torch CUDA tensors in,
+    `hits` / `lb` / `ub` / `flags` are CUDA tensors and `volume` a CPU tensor (it is np.prod(ub - lb) * hits / N, the
+    reference's expression, evaluated in numpy on the host: the call waits for the counts).  flags: VF_NONFINITE (a bound
+    of the box is inf / nan, or bbox_batch did not handle the polytope: pass lb / ub) | VF_NOROWS (m = 0): not sampled,
+    hits = 0 and volume = nan.  `seeds`: the seed of each polytope (what np.random.default_rng takes).
+    d <= 16 and m_max <= 64 (UnsupportedSize beyond)."""
+    tin = _is_torch(A)
+    if tin:
+        if A.dim() != 3:
+            raise ValueError("A must be [B, m_max, d]")
+        B, m_max, d = (int(v) for v in A.shape)
+    else:
+        A = _np(A)
+        if A.ndim != 3:
+            raise ValueError("A must be [B, m_max, d]")
+        B, m_max, d = A.shape
+    if d < 1:
+        raise ValueError("A must be [B, m_max, d] with d >= 1")
+    if (lb is None) != (ub is None):
+        raise ValueError("lb and ub come together")
+    for v in (lb, ub):
+        if v is not None and tuple(v.shape) != (B, d):
+            raise ValueError("lb / ub must be [B, d] = [%d, %d], got %s" % (B, d, tuple(v.shape)))
+    N = _volume_nsamples(d, nsamples)
+    if N > _VOLUME_MAX_N:
+        raise ValueError("`nsamples` must be <= 2^31 - 1, given:  {v}".format(v=nsamples))
+    N = int(N)
+    seeds = _volume_seeds(seed, B)
+    lib = _lib.load()
+    state, inc = _pcg64_words(seeds)
+    if tin:
+        torch, ctx, stream = _torch_stream_ctx(A)
+        A = _tprep(torch, A, torch.float64)
+        b = _tprep(torch, b, torch.float64)
+        m = _tprep(torch, m, torch.int32)
+        if lb is None:
+            box = bbox_batch(A, b, m)
+            nan = torch.full((), float("nan"), dtype=torch.float64, device=A.device)
+            ok = (box["status"] == 0)[:, None]
+            lb, ub = torch.where(ok, box["lb"], nan), torch.where(ok, box["ub"], nan)
+        else:
+            if not _is_torch(lb):
+                lb, ub = _np(lb), _np(ub)
+                _count_h2d(lb, ub)
+                lb, ub = torch.as_tensor(lb).to(A.device), torch.as_tensor(ub).to(A.device)
+            lb, ub = _tprep(torch, lb, torch.float64), _tprep(torch, ub, torch.float64)
+        _count_h2d(state, inc)
+        st_t, inc_t = torch.as_tensor(state.view(np.int64)).to(A.device), torch.as_tensor(inc.view(np.int64)).to(A.device)
+        hits = torch.empty((B,), dtype=torch.int32, device=A.device)
+        flags = torch.empty((B,), dtype=torch.int32, device=A.device)
+        _lib.check(lib.plp_volume_hits_dev(ctx.handle, stream, B, m_max, d, _ptr(A), _ptr(b), _ptr(m), _ptr(lb), _ptr(ub),
+                                           _ptr(st_t), _ptr(inc_t), N, _ptr(hits), _ptr(flags)), "plp_volume_hits_dev")
+        h_h, fl_h, lb_h, ub_h = hits.cpu().numpy(), flags.cpu().numpy(), lb.cpu().numpy(), ub.cpu().numpy()
+    else:
+        b = _np(b).reshape(B, m_max)
+        mm = None if m is None else _np(m, np.int32).reshape(B)
+        if lb is None:
+            box = bbox_batch(A, b, mm)
+            ok = (box["status"] == 0)[:, None]
+            lb, ub = np.where(ok, box["lb"], np.nan), np.where(ok, box["ub"], np.nan)
+        lb, ub = _np(lb), _np(ub)
+        hits = np.zeros(B, np.uint32)
+        flags = np.zeros(B, np.int32)
+        _count_h2d(A, b, mm, lb, ub, state, inc)
+        _lib.check(lib.plp_volume_hits(_lib.context().handle, B, m_max, d, _ptr(A), _ptr(b), _ptr(mm), _ptr(lb), _ptr(ub),
+                                       _ptr(state), _ptr(inc), N, _ptr(hits), _ptr(flags)), "plp_volume_hits")
+        h_h, fl_h, lb_h, ub_h = hits, flags, lb, ub
+    # the reference's expression (ref :1592), per polytope: np.prod(u_b - l_b) * aux / N
+    with np.errstate(invalid="ignore"):
+        vol = np.prod(ub_h - lb_h, axis=1) * h_h.astype(np.int64) / N
+    vol[fl_h != 0] = np.nan
+    if tin:
+        vol = torch.from_numpy(vol)
+    return dict(volume=vol, hits=hits, nsamples=N, lb=lb, ub=ub, flags=flags, seeds=seeds)
+
+
 def assign_batch(X, normals, offsets, abs_tol=1e-7):
     """quickhull outside-set assignment + furthest point (quickhull.py:87-102,117-121,224-245).
 

@@ -1185,6 +1185,65 @@ int plp_fm_emit(plp_ctx* ctx, int64_t B, int m_max, int d, const double* A, cons
     return fm_host(ctx, B, m_max, d, A, b, m, keep, kw, flags, col, first, abs_tol, nullptr, mo_max, A_out, b_out, m_out);
 }
 
+// ------------------------------------------------------------------------------- Monte-Carlo volume
+namespace {
+int volume_check(plp_ctx* ctx, int64_t B, int m_max, int d, const double* A, const double* b, const double* lb,
+                 const double* ub, const uint64_t* state, const uint64_t* inc, int64_t N, const uint32_t* hits,
+                 const int32_t* flags) {
+    if (!ctx) return fail(PLP_EINVAL, "ctx is NULL");
+    if (B < 0 || m_max < 0 || d < 1) return fail(PLP_EINVAL, "bad sizes");
+    if (N < 1 || N > 0x7fffffffll) return fail(PLP_EINVAL, "volume: N=%lld samples, need 1 <= N <= 2^31 - 1", (long long)N);
+    if (B > 0 && (!lb || !ub || !state || !inc || !hits || !flags || (m_max > 0 && (!A || !b))))
+        return fail(PLP_EINVAL, "NULL pointer");
+    if (d > plp::MAX_D) return fail(PLP_EUNSUPPORTED, "d=%d > 16", d);
+    if (m_max > plp::MAX_M) return fail(PLP_EUNSUPPORTED, "volume: m_max=%d > 64 rows", m_max);
+    return PLP_OK;
+}
+}  // namespace
+
+int plp_volume_hits_dev(plp_ctx* ctx, void* stream, int64_t B, int m_max, int d, const double* A, const double* b,
+                        const int32_t* m, const double* lb, const double* ub, const uint64_t* state, const uint64_t* inc,
+                        int64_t N, uint32_t* hits, int32_t* flags) {
+    int rc = volume_check(ctx, B, m_max, d, A, b, lb, ub, state, inc, N, hits, flags);
+    if (rc) return rc;
+    if (B == 0) return PLP_OK;
+    if (plp::launch_volume_hits(B, m_max, d, A, b, m, lb, ub, reinterpret_cast<const unsigned long long*>(state),
+                                reinterpret_cast<const unsigned long long*>(inc), N, hits, flags, (hipStream_t)stream))
+        return fail(PLP_EUNSUPPORTED, "volume: unsupported size");
+    return check_launch("volume_hits_kernel");
+}
+
+int plp_volume_hits(plp_ctx* ctx, int64_t B, int m_max, int d, const double* A, const double* b, const int32_t* m,
+                    const double* lb, const double* ub, const uint64_t* state, const uint64_t* inc, int64_t N,
+                    uint32_t* hits, int32_t* flags) {
+    int rc = volume_check(ctx, B, m_max, d, A, b, lb, ub, state, inc, N, hits, flags);
+    if (rc) return rc;
+    if (B == 0) return PLP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t nA = (size_t)B * m_max * d, nb = (size_t)B * m_max, nd = (size_t)B * d;
+    rc = ensure_arena(ctx, pad(nA * 8) + pad(nb * 8) + pad(nd * 8) * 2 + pad((size_t)B * 16) * 2 + pad((size_t)B * 4) * 3 + 4096);
+    if (rc) return rc;
+    Arena a(ctx);
+    double* dA = a.take<double>(nA ? nA : 1);
+    double* db = a.take<double>(nb ? nb : 1);
+    int32_t* dm = a.take<int32_t>(B);
+    double* dlb = a.take<double>(nd);
+    double* dub = a.take<double>(nd);
+    uint64_t* dst = a.take<uint64_t>((size_t)B * 2);
+    uint64_t* din = a.take<uint64_t>((size_t)B * 2);
+    uint32_t* dh = a.take<uint32_t>(B);
+    int32_t* dfl = a.take<int32_t>(B);
+    hipStream_t st = ctx->stream;
+    // (a box may hold +-inf: those polytopes come back flagged, so the arrays are not checked for finiteness here)
+    rc = copy_in(ctx, st, {{dA, A, nullptr, nA * 8}, {db, b, nullptr, nb * 8}, {dm, m, nullptr, m ? (size_t)B * 4 : 0},
+                           {dlb, lb, nullptr, nd * 8}, {dub, ub, nullptr, nd * 8}, {dst, state, nullptr, (size_t)B * 16},
+                           {din, inc, nullptr, (size_t)B * 16}});
+    if (rc) return rc;
+    rc = plp_volume_hits_dev(ctx, st, B, m_max, d, dA, db, m ? dm : nullptr, dlb, dub, dst, din, N, dh, dfl);
+    if (rc) return rc;
+    return copy_out(ctx, st, {{dh, nullptr, hits, (size_t)B * 4}, {dfl, nullptr, flags, (size_t)B * 4}});
+}
+
 }  // extern "C"
 
 struct plp_hull {

@@ -53,6 +53,11 @@ int launch_fm(int emit, long long B, int m_max, int d, const double* A, const do
               const unsigned long long* keep, int kw, const int* flags, int col, int first, double abs_tol, int* count,
               int mo_max, double* Aout, double* bout, int* mout, hipStream_t st);
 size_t fm_lds_bytes(int m_max, int d);
+// Monte-Carlo volume (plp_volume.hip): hits[B] = samples of default_rng's PCG64 stream (state / inc: two words per polytope,
+// low first) in the box [lb, ub] that lie strictly inside; flags[B]: vol::VF_*.  Zeroes hits and flags on `st`.  2: unsupported size
+int launch_volume_hits(long long B, int m_max, int d, const double* A, const double* b, const int* mrows, const double* lb,
+                       const double* ub, const unsigned long long* state, const unsigned long long* inc, long long N,
+                       unsigned* hits, int* flags, hipStream_t st);
 int launch_reduce_lds(long long B, int m_max, int d, const double* A, const double* b, const int* mrows, double abs_tol,
                       unsigned long long* keep, int* flags, double* r, double* xc, int* nlp, hipStream_t st);
 

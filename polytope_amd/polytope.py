@@ -1873,32 +1873,97 @@ class _DiffSearch:
 
 
 # ====================================================================================== volume
-def volume(polyreg, nsamples=None, seed=None):
-    """Monte-Carlo volume: uniform samples in the bounding box, fraction strictly inside
-    (ref :1529-1594).  Region: sum over its members."""
-    if not is_fulldim(polyreg):
-        return 0.0
-    if isinstance(polyreg, Region):
-        bounding_box(polyreg)  # the members' boxes in one batch of 2d LPs each, cached for the calls below
-        tot = 0.0
-        for p in polyreg.list_poly:
-            tot += volume(p)
-        polyreg._set_volume(tot)
-        return tot
+def _volume_by_samples(polyreg, nsamples=None, seed=None):
+    """volume() of a Polytope with the samples drawn on the host and uploaded: the path of every backend but 'hip', and of
+    'hip' where the volume kernel does not apply (more than 64 rows, a box that is not finite, a seed that is neither None
+    nor an int)."""
+    from .batch import _volume_nsamples
     n = polyreg.A.shape[1]
-    N = {1: 50, 2: 500, 3: 3000}.get(n, 10000)
-    if nsamples is not None and nsamples < 1:
-        raise ValueError("`nsamples` must be >= 1, given:  {v}".format(v=nsamples))
-    if nsamples is not None:
-        N = nsamples
-    if N != int(N):
-        raise ValueError("it appears that a noninteger number of samples has been given, namely:  {v}".format(
-            v=nsamples))
+    N = _volume_nsamples(n, nsamples)   # (the reference's table by dimension and its two ValueErrors, ref :1565-1584)
     l_b, u_b = polyreg.bounding_box
     x = np.tile(l_b, (1, N)) + np.random.default_rng(seed).random((n, N)) * np.tile(u_b - l_b, (1, N))
     # all(A x - b < 0) per sample (ref :1590-1591) == contains(x, abs_tol=0): the containment kernel
     hits = int(np.count_nonzero(_contains_many([polyreg], x, 0.0)))
     vol = np.prod(u_b - l_b) * hits / N
+    polyreg._set_volume(vol)
+    return vol
+
+
+def _volume_on_device(poly, nsamples, seed):
+    """True when the volume kernel takes this Polytope (polytope_amd.batch.volume_batch): 'hip', within the fused point
+    kernels' limits, an integer sample count the kernel holds, a seed that is None or a non-negative int, a finite box.
+    Everything else -- the two ValueErrors for `nsamples` among it -- is _volume_by_samples' business."""
+    from .batch import _is_int
+    if not _use_hip() or not _fits(poly.A.shape[0], poly.A.shape[1]) or poly.A.shape[0] < 1:
+        return False
+    if nsamples is not None and not (_is_int(nsamples) and 1 <= nsamples <= 2 ** 31 - 1):
+        return False
+    if seed is not None and not (_is_int(seed) and seed >= 0):
+        return False
+    l_b, u_b = poly.bounding_box
+    return bool(np.all(np.isfinite(l_b)) and np.all(np.isfinite(u_b)))
+
+
+def _volume_region_hip(region):
+    """volume(Region) on 'hip': the members that pass the reference's own gate (is_fulldim(member), ref :1551-1552) and
+    that the volume kernel takes go through ONE volume_batch call on the Region's resident rows; the others as before."""
+    from . import batch
+    members = region.list_poly
+    _cheby_fill(members)
+    vols = [None] * len(members)
+    sel = []
+    for k, p in enumerate(members):
+        if not is_fulldim(p):
+            vols[k] = 0.0          # (its `_volume` stays as it is, as in the reference)
+        elif _volume_on_device(p, None, None):
+            sel.append(k)
+        else:
+            vols[k] = _volume_by_samples(p)
+    if sel:
+        polys = [members[k] for k in sel]
+        At, bt, mt = _table_of(polys, region if len(sel) == len(members) else None).dev()
+        lb = np.array([p.bbox[0].ravel() for p in polys])
+        ub = np.array([p.bbox[1].ravel() for p in polys])
+        res = batch.volume_batch(At, bt, m=mt, lb=lb, ub=ub)
+        got = res["volume"]
+        got = got if isinstance(got, np.ndarray) else got.numpy()
+        for k, p, v in zip(sel, polys, got):
+            p._set_volume(v)
+            vols[k] = v
+    tot = 0.0
+    for v in vols:
+        tot += v
+    region._set_volume(tot)
+    return tot
+
+
+def volume(polyreg, nsamples=None, seed=None):
+    """Monte-Carlo volume: uniform samples in the bounding box, fraction strictly inside
+    (ref :1529-1594).  Region: sum over its members (with the default `nsamples` and `seed=None`, as in the reference).
+
+    On 'hip' the samples -- the ones np.random.default_rng(seed).random((d, N)) draws -- are generated on the device
+    (polytope_amd.batch.volume_batch): for a given seed the result is the float the sample-upload path returns.  With
+    `seed=None` the members of a Region draw from the spawned children of ONE fresh np.random.SeedSequence, and a single
+    Polytope from the one child `np.random.SeedSequence().spawn(1)[0]` -- fresh entropy either way, though not the stream
+    np.random.default_rng(None) itself would start."""
+    if not is_fulldim(polyreg):
+        return 0.0
+    if isinstance(polyreg, Region):
+        bounding_box(polyreg)  # the members' boxes in one batch of 2d LPs each, cached for the calls below
+        if _use_hip():
+            return _volume_region_hip(polyreg)
+        tot = 0.0
+        for p in polyreg.list_poly:
+            tot += volume(p)
+        polyreg._set_volume(tot)
+        return tot
+    if not _volume_on_device(polyreg, nsamples, seed):
+        return _volume_by_samples(polyreg, nsamples, seed)
+    from . import batch
+    l_b, u_b = polyreg.bounding_box
+    res = batch.volume_batch(polyreg.A[np.newaxis], polyreg.b[np.newaxis], nsamples=nsamples, seed=seed,
+                             lb=l_b.reshape(1, -1), ub=u_b.reshape(1, -1))
+    vol = res["volume"][0]
     polyreg._set_volume(vol)
     return vol
 
