@@ -8,6 +8,7 @@ on torch's current stream, results come back as CUDA tensors, nothing synchronis
 Packing: A[B, m_max, d], b[B, m_max], optional int32 m[B] (rows used per polytope).
 """
 import ctypes as C
+import sys
 import time
 
 import numpy as np
@@ -68,6 +69,71 @@ def _tprep(torch, t, dtype):
     return t
 
 
+_SCALARS = (int, float)
+_TORCH_DTYPE = {}
+
+
+def _torch_dtypes(torch):
+    """numpy dtype -> torch dtype.  torch has no unsigned words: keep masks and hit counts are the same bits in the signed type."""
+    if not _TORCH_DTYPE:
+        _TORCH_DTYPE.update({np.float64: torch.float64, np.int32: torch.int32, np.int64: torch.int64, np.uint8: torch.uint8,
+                             np.uint32: torch.int32, np.uint64: torch.int64})
+    return _TORCH_DTYPE
+
+
+class _Backend:
+    """Where the arrays of one call live, chosen from its first array: numpy (the host-pointer entry point `name`, which
+    copies in and out on the context's stream and blocks) or torch CUDA tensors (`name + "_dev"` on torch's current stream;
+    nothing synchronises).  A public function states its shapes, dtypes and argument order once, in terms of this object."""
+
+    def __init__(self, first):
+        # (nothing of the library is touched before call(): argument errors are raised without it)
+        self.torch = None
+        if _is_torch(first):
+            self.torch = sys.modules["torch"]
+            self.first, self.device, self.dtypes = first, first.device, _torch_dtypes(self.torch)
+
+    def arr(self, a, dtype=np.float64, shape=None):
+        """An input, contiguous and of `dtype` (None stays None); a numpy input is also brought to `shape`."""
+        if a is None:
+            return None
+        if self.torch is not None:
+            return _tprep(self.torch, a, self.dtypes[dtype])
+        a = _np(a, dtype)
+        return a if shape is None else a.reshape(shape)
+
+    def out(self, shape, dtype=np.float64, zero=False):
+        """An output.  `zero`: a numpy output the library may leave unwritten (an empty call returns before any copy)."""
+        if self.torch is not None:
+            return self.torch.empty(shape, dtype=self.dtypes[dtype], device=self.device)
+        return (np.zeros if zero else np.empty)(shape, dtype)
+
+    def call(self, name, *args, h2d=()):
+        """The entry point `name` of this backend with `args` (arrays as pointers) behind the context (and the stream).
+        `h2d`: the numpy inputs whose upload the debug counter is to see."""
+        lib = _lib.load()
+        if self.torch is not None:   # (sizes and tolerances go as they are)
+            name += "_dev"
+            _, ctx, stream = _torch_stream_ctx(self.first)
+            args = [a if a.__class__ in _SCALARS else None if a is None else C.c_void_p(a.data_ptr()) for a in args]
+            rc = getattr(lib, name)(ctx.handle, stream, *args)
+        else:
+            _count_h2d(*h2d)
+            args = [a if a.__class__ in _SCALARS else None if a is None else C.c_void_p(a.ctypes.data) for a in args]
+            rc = getattr(lib, name)(_lib.context().handle, *args)
+        if rc:
+            _lib.check(rc, name)
+
+
+def _packed(be, A, b, m, name="A"):
+    """The packed table every batch takes -> A[B, m_max, d], b[B, m_max], m int32[B] or None, (B, m_max, d)."""
+    A = be.arr(A)
+    if len(A.shape) != 3:
+        raise ValueError("%s must be [B, m_max, %s]" % (name, "n" if name == "G" else "d"))
+    B, m_max, d = A.shape
+    return A, be.arr(b, shape=(B, m_max)), be.arr(m, np.int32, (B,)), (B, m_max, d)
+
+
 # --------------------------------------------------------------------------------------
 def lpsolve_batch(c, G, h, m=None):
     """B independent LPs  min c'x s.t. Gx <= h, x free  (solvers.py:76-106 semantics per LP).
@@ -75,36 +141,13 @@ def lpsolve_batch(c, G, h, m=None):
     c[B,n], G[B,m_max,n], h[B,m_max] -> dict(status int32[B], x[B,n], fun[B], iters int32[B]);
     x/fun are NaN where status != 0.
     """
-    lib = _lib.load()
-    if _is_torch(G):
-        torch, ctx, stream = _torch_stream_ctx(G)
-        G = _tprep(torch, G, torch.float64)
-        c = _tprep(torch, c, torch.float64)
-        h = _tprep(torch, h, torch.float64)
-        m = _tprep(torch, m, torch.int32)
-        B, m_max, n = G.shape
-        x = torch.empty((B, n), dtype=torch.float64, device=G.device)
-        fun = torch.empty((B,), dtype=torch.float64, device=G.device)
-        status = torch.empty((B,), dtype=torch.int32, device=G.device)
-        iters = torch.empty((B,), dtype=torch.int32, device=G.device)
-        _lib.check(lib.plp_lp_solve_batch_dev(ctx.handle, stream, B, m_max, n, _ptr(c), _ptr(G), _ptr(h), _ptr(m),
-                                              _ptr(x), _ptr(fun), _ptr(status), _ptr(iters)), "plp_lp_solve_batch_dev")
-        return dict(status=status, x=x, fun=fun, iters=iters)
-    G = _np(G)
-    if G.ndim != 3:
-        raise ValueError("G must be [B, m_max, n]")
-    B, m_max, n = G.shape
-    c = _np(c).reshape(B, n)
-    h = _np(h).reshape(B, m_max)
-    mm = None if m is None else _np(m, np.int32).reshape(B)
-    # (inf / nan in the inputs: ValueError from the library, which checks them while staging -- plp_ctx_set_check_finite)
-    x = np.empty((B, n))
-    fun = np.empty(B)
-    status = np.empty(B, np.int32)
-    iters = np.empty(B, np.int32)
-    _count_h2d(c, G, h, mm)
-    _lib.check(lib.plp_lp_solve_batch(_lib.context().handle, B, m_max, n, _ptr(c), _ptr(G), _ptr(h), _ptr(mm),
-                                      _ptr(x), _ptr(fun), _ptr(status), _ptr(iters)), "plp_lp_solve_batch")
+    be = _Backend(G)
+    G, h, m, (B, m_max, n) = _packed(be, G, h, m, "G")
+    c = be.arr(c, shape=(B, n))
+    # (inf / nan in numpy inputs: ValueError from the library, which checks them while staging -- plp_ctx_set_check_finite)
+    x, fun = be.out((B, n)), be.out((B,))
+    status, iters = be.out((B,), np.int32), be.out((B,), np.int32)
+    be.call("plp_lp_solve_batch", B, m_max, n, c, G, h, m, x, fun, status, iters, h2d=(c, G, h, m))
     return dict(status=status, x=x, fun=fun, iters=iters)
 
 
@@ -114,32 +157,11 @@ def cheby_ball_batch(A, b, m=None):
     -> dict(r[B] raw x[-1], xc[B,d], status[B]).  cheby_ball's own post-processing
     (status != 0 or r < 0 -> (0, None), :1289-1297) is left to the caller.
     """
-    lib = _lib.load()
-    if _is_torch(A):
-        torch, ctx, stream = _torch_stream_ctx(A)
-        A = _tprep(torch, A, torch.float64)
-        b = _tprep(torch, b, torch.float64)
-        m = _tprep(torch, m, torch.int32)
-        B, m_max, d = A.shape
-        r = torch.empty((B,), dtype=torch.float64, device=A.device)
-        xc = torch.empty((B, d), dtype=torch.float64, device=A.device)
-        status = torch.empty((B,), dtype=torch.int32, device=A.device)
-        _lib.check(lib.plp_cheby_batch_dev(ctx.handle, stream, B, m_max, d, _ptr(A), _ptr(b), _ptr(m), _ptr(r),
-                                           _ptr(xc), _ptr(status)), "plp_cheby_batch_dev")
-        return dict(r=r, xc=xc, status=status)
-    A = _np(A)
-    if A.ndim != 3:
-        raise ValueError("A must be [B, m_max, d]")
-    B, m_max, d = A.shape
-    b = _np(b).reshape(B, m_max)
-    mm = None if m is None else _np(m, np.int32).reshape(B)
-    # (inf / nan in the inputs: ValueError from the library, which checks them while staging -- plp_ctx_set_check_finite)
-    r = np.empty(B)
-    xc = np.empty((B, d))
-    status = np.empty(B, np.int32)
-    _count_h2d(A, b, mm)
-    _lib.check(lib.plp_cheby_batch(_lib.context().handle, B, m_max, d, _ptr(A), _ptr(b), _ptr(mm), _ptr(r),
-                                   _ptr(xc), _ptr(status)), "plp_cheby_batch")
+    be = _Backend(A)
+    A, b, m, (B, m_max, d) = _packed(be, A, b, m)
+    # (inf / nan in numpy inputs: ValueError from the library, which checks them while staging -- plp_ctx_set_check_finite)
+    r, xc, status = be.out((B,)), be.out((B, d)), be.out((B,), np.int32)
+    be.call("plp_cheby_batch", B, m_max, d, A, b, m, r, xc, status, h2d=(A, b, m))
     return dict(r=r, xc=xc, status=status)
 
 
@@ -150,32 +172,11 @@ def bbox_batch(A, b, m=None):
     -> dict(lb[B,d], ub[B,d], status[B]): status 0 = box valid (+-inf where unbounded), 1 = polytope not handled
     here (no centre with r >= 1e-6, or a Bland case): the caller solves the 2d generic LPs for it.
     """
-    lib = _lib.load()
-    if _is_torch(A):
-        torch, ctx, stream = _torch_stream_ctx(A)
-        A = _tprep(torch, A, torch.float64)
-        b = _tprep(torch, b, torch.float64)
-        m = _tprep(torch, m, torch.int32)
-        B, m_max, d = A.shape
-        lb = torch.empty((B, d), dtype=torch.float64, device=A.device)
-        ub = torch.empty((B, d), dtype=torch.float64, device=A.device)
-        status = torch.empty((B,), dtype=torch.int32, device=A.device)
-        _lib.check(lib.plp_bbox_batch_dev(ctx.handle, stream, B, m_max, d, _ptr(A), _ptr(b), _ptr(m), _ptr(lb),
-                                          _ptr(ub), _ptr(status)), "plp_bbox_batch_dev")
-        return dict(lb=lb, ub=ub, status=status)
-    A = _np(A)
-    if A.ndim != 3:
-        raise ValueError("A must be [B, m_max, d]")
-    B, m_max, d = A.shape
-    b = _np(b).reshape(B, m_max)
-    mm = None if m is None else _np(m, np.int32).reshape(B)
-    # (inf / nan in the inputs: ValueError from the library, which checks them while staging -- plp_ctx_set_check_finite)
-    lb = np.empty((B, d))
-    ub = np.empty((B, d))
-    status = np.empty(B, np.int32)
-    _count_h2d(A, b, mm)
-    _lib.check(lib.plp_bbox_batch(_lib.context().handle, B, m_max, d, _ptr(A), _ptr(b), _ptr(mm), _ptr(lb),
-                                  _ptr(ub), _ptr(status)), "plp_bbox_batch")
+    be = _Backend(A)
+    A, b, m, (B, m_max, d) = _packed(be, A, b, m)
+    # (inf / nan in numpy inputs: ValueError from the library, which checks them while staging -- plp_ctx_set_check_finite)
+    lb, ub, status = be.out((B, d)), be.out((B, d)), be.out((B,), np.int32)
+    be.call("plp_bbox_batch", B, m_max, d, A, b, m, lb, ub, status, h2d=(A, b, m))
     return dict(lb=lb, ub=ub, status=status)
 
 
@@ -190,62 +191,38 @@ def reduce_batch(A, b, m=None, abs_tol=1e-7, out=None):
     int32[B], r float64[B], xc float64[B,d], nlp int32[B] to write into (e.g. views of one exchange buffer,
     polytope_amd.dist.ResultBuffer).
     """
-    lib = _lib.load()
-    if _is_torch(A):
-        torch, ctx, stream = _torch_stream_ctx(A)
-        A = _tprep(torch, A, torch.float64)
-        b = _tprep(torch, b, torch.float64)
-        m = _tprep(torch, m, torch.int32)
-        B, m_max, d = A.shape
-        if m_max > 64:
-            if out is not None:
-                raise ValueError("reduce_batch: `out` is for polytopes of up to 64 rows (one keep word each)")
-            W = (m_max + 63) // 64
-            keep = torch.empty((B, W), dtype=torch.int64, device=A.device)
-            flags = torch.empty((B,), dtype=torch.int32, device=A.device)
-            r = torch.empty((B,), dtype=torch.float64, device=A.device)
-            xc = torch.empty((B, d), dtype=torch.float64, device=A.device)
-            nlp = torch.empty((B,), dtype=torch.int32, device=A.device)
-            _lib.check(lib.plp_reduce_wide_batch_dev(ctx.handle, stream, B, m_max, d, _ptr(A), _ptr(b), _ptr(m),
-                                                     float(abs_tol), _ptr(keep), _ptr(flags), _ptr(r), _ptr(xc), _ptr(nlp)),
-                       "plp_reduce_wide_batch_dev")
-            return dict(keep=keep, flags=flags, r=r, xc=xc, nlp=nlp)
-        if out is not None:
-            keep, flags, r, xc, nlp = out["keep"], out["flags"], out["r"], out["xc"], out["nlp"]
-            want = ((keep, torch.int64, (B,)), (flags, torch.int32, (B,)), (r, torch.float64, (B,)),
-                    (xc, torch.float64, (B, d)), (nlp, torch.int32, (B,)))
-            for t, dt, shp in want:
-                if t.dtype != dt or tuple(t.shape) != shp or not t.is_contiguous() or t.device != A.device:
-                    raise ValueError("reduce_batch: `out` tensors must be contiguous CUDA tensors of the documented "
-                                     "dtype and shape")
-        else:
-            keep = torch.empty((B,), dtype=torch.int64, device=A.device)
-            flags = torch.empty((B,), dtype=torch.int32, device=A.device)
-            r = torch.empty((B,), dtype=torch.float64, device=A.device)
-            xc = torch.empty((B, d), dtype=torch.float64, device=A.device)
-            nlp = torch.empty((B,), dtype=torch.int32, device=A.device)
-        _lib.check(lib.plp_reduce_batch_dev(ctx.handle, stream, B, m_max, d, _ptr(A), _ptr(b), _ptr(m), float(abs_tol),
-                                            _ptr(keep), _ptr(flags), _ptr(r), _ptr(xc), _ptr(nlp)),
-                   "plp_reduce_batch_dev")
-        return dict(keep=keep, flags=flags, r=r, xc=xc, nlp=nlp)
-    A = _np(A)
-    if A.ndim != 3:
-        raise ValueError("A must be [B, m_max, d]")
-    B, m_max, d = A.shape
-    b = _np(b).reshape(B, m_max)
-    mm = None if m is None else _np(m, np.int32).reshape(B)
-    # (inf / nan in the inputs: ValueError from the library, which checks them while staging -- plp_ctx_set_check_finite)
+    be = _Backend(A)
+    A, b, m, (B, m_max, d) = _packed(be, A, b, m)
+    # (inf / nan in numpy inputs: ValueError from the library, which checks them while staging -- plp_ctx_set_check_finite)
     wide = m_max > 64
-    keep = np.empty((B, (m_max + 63) // 64) if wide else B, np.uint64)
-    flags = np.empty(B, np.int32)
-    r = np.empty(B)
-    xc = np.empty((B, d))
-    nlp = np.empty(B, np.int32)
-    fn, name = (lib.plp_reduce_wide_batch, "plp_reduce_wide_batch") if wide else (lib.plp_reduce_batch, "plp_reduce_batch")
-    _count_h2d(A, b, mm)
-    _lib.check(fn(_lib.context().handle, B, m_max, d, _ptr(A), _ptr(b), _ptr(mm), float(abs_tol),
-                  _ptr(keep), _ptr(flags), _ptr(r), _ptr(xc), _ptr(nlp)), name)
-    return dict(keep=keep, flags=flags, r=r, xc=xc, nlp=nlp)
+    want = (("keep", np.uint64, (B, (m_max + 63) // 64) if wide else (B,)), ("flags", np.int32, (B,)),
+            ("r", np.float64, (B,)), ("xc", np.float64, (B, d)), ("nlp", np.int32, (B,)))
+    if be.torch is None or out is None:
+        res = {k: be.out(shp, dt) for k, dt, shp in want}
+    elif wide:
+        raise ValueError("reduce_batch: `out` is for polytopes of up to 64 rows (one keep word each)")
+    else:
+        res = {k: out[k] for k, _, _ in want}
+        for k, dt, shp in want:
+            t = res[k]
+            if (t.dtype != be.dtypes[dt] or tuple(t.shape) != shp or not t.is_contiguous()
+                    or t.device != A.device):
+                raise ValueError("reduce_batch: `out` tensors must be contiguous CUDA tensors of the documented "
+                                 "dtype and shape")
+    be.call("plp_reduce_wide_batch" if wide else "plp_reduce_batch", B, m_max, d, A, b, m, float(abs_tol),
+            res["keep"], res["flags"], res["r"], res["xc"], res["nlp"], h2d=(A, b, m))
+    return res
+
+
+def _ctx_and_stream(device, stream):
+    """The context of `device` and the stream handle a counter query runs on: `stream` (a torch stream), by default torch's
+    current stream when torch is loaded with a GPU, else NULL (the HIP default stream)."""
+    ctx = _lib.context(device)
+    if stream is None:
+        torch = sys.modules.get("torch")
+        if torch is not None and torch.cuda.is_available():
+            stream = torch.cuda.current_stream(ctx.device)
+    return ctx, C.c_void_p(stream.cuda_stream) if stream is not None else None
 
 
 def reduce_simplex_runs(device=None, reset=False, stream=None):
@@ -254,13 +231,7 @@ def reduce_simplex_runs(device=None, reset=False, stream=None):
     the presolve settles a part without a simplex run.  The first call switches the counting on and returns 0.
     `stream`: a torch stream (default: torch's current stream when torch is loaded with a GPU, else the HIP default)."""
     lib = _lib.load()
-    ctx = _lib.context(device)
-    if stream is None:
-        import sys
-        torch = sys.modules.get("torch")
-        if torch is not None and torch.cuda.is_available():
-            stream = torch.cuda.current_stream(ctx.device)
-    sp = C.c_void_p(stream.cuda_stream) if stream is not None else None
+    ctx, sp = _ctx_and_stream(device, stream)
     out = C.c_uint64(0)
     _lib.check(lib.plp_reduce_counters(ctx.handle, sp, C.cast(C.byref(out), C.c_void_p), 1 if reset else 0),
                "plp_reduce_counters")
@@ -273,13 +244,7 @@ def verify_careful_lps(device=None, stream=None):
     plp_verify_counters).  `stream`: a torch stream (default: torch's current stream when torch is loaded with a GPU; calls
     with numpy arrays run on the context's own stream, which the library falls back to).  Blocks until that batch is done."""
     lib = _lib.load()
-    ctx = _lib.context(device)
-    if stream is None:
-        import sys
-        torch = sys.modules.get("torch")
-        if torch is not None and torch.cuda.is_available():
-            stream = torch.cuda.current_stream(ctx.device)
-    sp = C.c_void_p(stream.cuda_stream) if stream is not None else None
+    ctx, sp = _ctx_and_stream(device, stream)
     out = C.c_int64(0)
     _lib.check(lib.plp_verify_counters(ctx.handle, sp, C.cast(C.byref(out), C.c_void_p)), "plp_verify_counters")
     return int(out.value)
@@ -316,34 +281,14 @@ def contains_batch(A, b, X, abs_tol=1e-7, m=None, region=True):
     region=True  -> uint8[N]    OR over the polytopes (Region.contains; all P*N tests evaluated)
     region=False -> uint8[P, N] one row per polytope (Polytope.contains)
     """
-    lib = _lib.load()
-    mode = 0 if region else 1
-    if _is_torch(X):
-        torch, ctx, stream = _torch_stream_ctx(X)
-        A = _tprep(torch, A, torch.float64)
-        b = _tprep(torch, b, torch.float64)
-        X = _tprep(torch, X, torch.float64)
-        m = _tprep(torch, m, torch.int32)
-        P, m_max, d = A.shape
-        if X.shape[0] != d:
-            raise ValueError("points should be column vectors")
-        N = X.shape[1]
-        out = torch.empty((N,) if region else (P, N), dtype=torch.uint8, device=X.device)
-        _lib.check(lib.plp_contains_dev(ctx.handle, stream, P, m_max, d, _ptr(A), _ptr(b), _ptr(m), N, _ptr(X),
-                                        float(abs_tol), mode, _ptr(out)), "plp_contains_dev")
-        return out
-    A = _np(A)
-    P, m_max, d = A.shape
-    b = _np(b).reshape(P, m_max)
-    X = _np(X)
-    if X.ndim != 2 or X.shape[0] != d:
+    be = _Backend(X)
+    A, b, m, (P, m_max, d) = _packed(be, A, b, m)
+    X = be.arr(X)
+    if len(X.shape) != 2 or X.shape[0] != d:
         raise ValueError("points should be column vectors")
     N = X.shape[1]
-    mm = None if m is None else _np(m, np.int32).reshape(P)
-    out = np.zeros((N,) if region else (P, N), np.uint8)
-    _count_h2d(A, b, mm, X)
-    _lib.check(lib.plp_contains(_lib.context().handle, P, m_max, d, _ptr(A), _ptr(b), _ptr(mm), N, _ptr(X),
-                                float(abs_tol), mode, _ptr(out)), "plp_contains")
+    out = be.out((N,) if region else (P, N), np.uint8, zero=True)
+    be.call("plp_contains", P, m_max, d, A, b, m, N, X, float(abs_tol), 0 if region else 1, out, h2d=(A, b, m, X))
     return out
 
 
@@ -425,16 +370,8 @@ def volume_batch(A, b, m=None, nsamples=None, seed=None, lb=None, ub=None):
     of the box is inf / nan, or bbox_batch did not handle the polytope: pass lb / ub) | VF_NOROWS (m = 0): not sampled,
     hits = 0 and volume = nan.  `seeds`: the seed of each polytope (what np.random.default_rng takes).
     d <= 16 and m_max <= 64 (UnsupportedSize beyond)."""
-    tin = _is_torch(A)
-    if tin:
-        if A.dim() != 3:
-            raise ValueError("A must be [B, m_max, d]")
-        B, m_max, d = (int(v) for v in A.shape)
-    else:
-        A = _np(A)
-        if A.ndim != 3:
-            raise ValueError("A must be [B, m_max, d]")
-        B, m_max, d = A.shape
+    be = _Backend(A)
+    A, b, m, (B, m_max, d) = _packed(be, A, b, m)
     if d < 1:
         raise ValueError("A must be [B, m_max, d] with d >= 1")
     if (lb is None) != (ub is None):
@@ -447,50 +384,35 @@ def volume_batch(A, b, m=None, nsamples=None, seed=None, lb=None, ub=None):
         raise ValueError("`nsamples` must be <= 2^31 - 1, given:  {v}".format(v=nsamples))
     N = int(N)
     seeds = _volume_seeds(seed, B)
-    lib = _lib.load()
     state, inc = _pcg64_words(seeds)
-    if tin:
-        torch, ctx, stream = _torch_stream_ctx(A)
-        A = _tprep(torch, A, torch.float64)
-        b = _tprep(torch, b, torch.float64)
-        m = _tprep(torch, m, torch.int32)
-        if lb is None:
-            box = bbox_batch(A, b, m)
+    torch = be.torch
+    if lb is None:
+        box = bbox_batch(A, b, m)
+        ok = (box["status"] == 0)[:, None]
+        if torch is not None:
             nan = torch.full((), float("nan"), dtype=torch.float64, device=A.device)
-            ok = (box["status"] == 0)[:, None]
             lb, ub = torch.where(ok, box["lb"], nan), torch.where(ok, box["ub"], nan)
         else:
-            if not _is_torch(lb):
-                lb, ub = _np(lb), _np(ub)
-                _count_h2d(lb, ub)
-                lb, ub = torch.as_tensor(lb).to(A.device), torch.as_tensor(ub).to(A.device)
-            lb, ub = _tprep(torch, lb, torch.float64), _tprep(torch, ub, torch.float64)
+            lb, ub = np.where(ok, box["lb"], np.nan), np.where(ok, box["ub"], np.nan)
+    if torch is not None:   # the boxes (when they came as numpy arrays) and the generator words go to the device here
+        if not _is_torch(lb):
+            lb, ub = _np(lb), _np(ub)
+            _count_h2d(lb, ub)
+            lb, ub = torch.as_tensor(lb).to(A.device), torch.as_tensor(ub).to(A.device)
         _count_h2d(state, inc)
-        st_t, inc_t = torch.as_tensor(state.view(np.int64)).to(A.device), torch.as_tensor(inc.view(np.int64)).to(A.device)
-        hits = torch.empty((B,), dtype=torch.int32, device=A.device)
-        flags = torch.empty((B,), dtype=torch.int32, device=A.device)
-        _lib.check(lib.plp_volume_hits_dev(ctx.handle, stream, B, m_max, d, _ptr(A), _ptr(b), _ptr(m), _ptr(lb), _ptr(ub),
-                                           _ptr(st_t), _ptr(inc_t), N, _ptr(hits), _ptr(flags)), "plp_volume_hits_dev")
+        state, inc = torch.as_tensor(state.view(np.int64)).to(A.device), torch.as_tensor(inc.view(np.int64)).to(A.device)
+    lb, ub = be.arr(lb), be.arr(ub)
+    hits, flags = be.out((B,), np.uint32, zero=True), be.out((B,), np.int32, zero=True)
+    be.call("plp_volume_hits", B, m_max, d, A, b, m, lb, ub, state, inc, N, hits, flags, h2d=(A, b, m, lb, ub, state, inc))
+    if torch is not None:
         h_h, fl_h, lb_h, ub_h = hits.cpu().numpy(), flags.cpu().numpy(), lb.cpu().numpy(), ub.cpu().numpy()
     else:
-        b = _np(b).reshape(B, m_max)
-        mm = None if m is None else _np(m, np.int32).reshape(B)
-        if lb is None:
-            box = bbox_batch(A, b, mm)
-            ok = (box["status"] == 0)[:, None]
-            lb, ub = np.where(ok, box["lb"], np.nan), np.where(ok, box["ub"], np.nan)
-        lb, ub = _np(lb), _np(ub)
-        hits = np.zeros(B, np.uint32)
-        flags = np.zeros(B, np.int32)
-        _count_h2d(A, b, mm, lb, ub, state, inc)
-        _lib.check(lib.plp_volume_hits(_lib.context().handle, B, m_max, d, _ptr(A), _ptr(b), _ptr(mm), _ptr(lb), _ptr(ub),
-                                       _ptr(state), _ptr(inc), N, _ptr(hits), _ptr(flags)), "plp_volume_hits")
         h_h, fl_h, lb_h, ub_h = hits, flags, lb, ub
     # the reference's expression (ref :1592), per polytope: np.prod(u_b - l_b) * aux / N
     with np.errstate(invalid="ignore"):
         vol = np.prod(ub_h - lb_h, axis=1) * h_h.astype(np.int64) / N
     vol[fl_h != 0] = np.nan
-    if tin:
+    if torch is not None:
         vol = torch.from_numpy(vol)
     return dict(volume=vol, hits=hits, nsamples=N, lb=lb, ub=ub, flags=flags, seeds=seeds)
 
@@ -501,33 +423,15 @@ def assign_batch(X, normals, offsets, abs_tol=1e-7):
     X[N, d] points (rows), normals[F, d], offsets[F]
     -> dict(facet int32[N] (-1 inside), dist[N], argmax int64[F] (-1 none), maxd[F])
     """
-    lib = _lib.load()
-    if _is_torch(X):
-        torch, ctx, stream = _torch_stream_ctx(X)
-        X = _tprep(torch, X, torch.float64)
-        normals = _tprep(torch, normals, torch.float64)
-        offsets = _tprep(torch, offsets, torch.float64)
-        N, d = X.shape
-        F = normals.shape[0]
-        fop = torch.empty((N,), dtype=torch.int32, device=X.device)
-        dist = torch.empty((N,), dtype=torch.float64, device=X.device)
-        am = torch.empty((F,), dtype=torch.int64, device=X.device)
-        mx = torch.empty((F,), dtype=torch.float64, device=X.device)
-        _lib.check(lib.plp_assign_dev(ctx.handle, stream, N, d, _ptr(X), F, _ptr(normals), _ptr(offsets),
-                                      float(abs_tol), _ptr(fop), _ptr(dist), _ptr(am), _ptr(mx)), "plp_assign_dev")
-        return dict(facet=fop, dist=dist, argmax=am, maxd=mx)
-    X = _np(X)
+    be = _Backend(X)
+    X = be.arr(X)
     N, d = X.shape
-    normals = _np(normals).reshape(-1, d)
+    normals = be.arr(normals, shape=(-1, d))
     F = normals.shape[0]
-    offsets = _np(offsets).reshape(F)
-    fop = np.empty(N, np.int32)
-    dist = np.empty(N)
-    am = np.empty(F, np.int64)
-    mx = np.empty(F)
-    _count_h2d(X, normals, offsets)
-    _lib.check(lib.plp_assign(_lib.context().handle, N, d, _ptr(X), F, _ptr(normals), _ptr(offsets), float(abs_tol),
-                              _ptr(fop), _ptr(dist), _ptr(am), _ptr(mx)), "plp_assign")
+    offsets = be.arr(offsets, shape=(F,))
+    fop, dist = be.out((N,), np.int32), be.out((N,))
+    am, mx = be.out((F,), np.int64), be.out((F,))
+    be.call("plp_assign", N, d, X, F, normals, offsets, float(abs_tol), fop, dist, am, mx, h2d=(X, normals, offsets))
     return dict(facet=fop, dist=dist, argmax=am, maxd=mx)
 
 
@@ -604,30 +508,23 @@ def hull_reassign_dev(X, owner, dist, dead, new_id0, normals, offsets, abs_tol=1
     return dict(count=cnt, argmax=am, maxd=mx)
 
 
+def _cells(what, A, b, m):
+    """The table of the pair operations: cells A[n, m_max, d], b[n, m_max], m -> (backend, A, b, m, n, m_max, d); numpy
+    inputs are checked for inf / nan here."""
+    be = _Backend(A)
+    A, b, m, (n, m_max, d) = _packed(be, A, b, m)
+    if be.torch is None:
+        _finite_or_raise(what, A, b)
+    return be, A, b, m, n, m_max, d
+
+
 def adjacent_pairs(A, b, m=None, abs_tol=1e-7):
     """Adjacency matrix of n single-polytope cells (prop2partition.py:46-63 over polytope.py:1843-1866):
     uint8[n, n], symmetric, ones on the diagonal.  A[n, m_max, d], b[n, m_max]; 2*m_max <= 64, d <= 16.
     The n(n-1)/2 stacked, abs_tol-inflated pair LPs are formed on the device."""
-    lib = _lib.load()
-    if _is_torch(A):
-        torch, ctx, stream = _torch_stream_ctx(A)
-        A = _tprep(torch, A, torch.float64)
-        b = _tprep(torch, b, torch.float64)
-        m = _tprep(torch, m, torch.int32)
-        n, m_max, d = A.shape
-        adj = torch.empty((n, n), dtype=torch.uint8, device=A.device)
-        _lib.check(lib.plp_adjacent_pairs_dev(ctx.handle, stream, n, m_max, d, _ptr(A), _ptr(b), _ptr(m),
-                                              float(abs_tol), _ptr(adj)), "plp_adjacent_pairs_dev")
-        return adj
-    A = _np(A)
-    n, m_max, d = A.shape
-    b = _np(b).reshape(n, m_max)
-    mm = None if m is None else _np(m, np.int32).reshape(n)
-    _finite_or_raise("adjacent_pairs", A, b)
-    adj = np.zeros((n, n), np.uint8)
-    _count_h2d(A, b, mm)
-    _lib.check(lib.plp_adjacent_pairs(_lib.context().handle, n, m_max, d, _ptr(A), _ptr(b), _ptr(mm), float(abs_tol),
-                                      _ptr(adj)), "plp_adjacent_pairs")
+    be, A, b, m, n, m_max, d = _cells("adjacent_pairs", A, b, m)
+    adj = be.out((n, n), np.uint8, zero=True)
+    be.call("plp_adjacent_pairs", n, m_max, d, A, b, m, float(abs_tol), adj, h2d=(A, b, m))
     return adj
 
 
@@ -635,26 +532,9 @@ def overlap_pairs(A, b, m=None, abs_tol=1e-7):
     """uint8[n, n]: 1 where the intersection of cells i and j is full-dimensional (Chebyshev radius of the
     stacked rows > abs_tol) -- the pair test of Partition.are_disjoint (prop2partition.py:146-149); ones
     on the diagonal.  A[n, m_max, d], b[n, m_max]; 2*m_max <= 64, d <= 16."""
-    lib = _lib.load()
-    if _is_torch(A):
-        torch, ctx, stream = _torch_stream_ctx(A)
-        A = _tprep(torch, A, torch.float64)
-        b = _tprep(torch, b, torch.float64)
-        m = _tprep(torch, m, torch.int32)
-        n, m_max, d = A.shape
-        out = torch.empty((n, n), dtype=torch.uint8, device=A.device)
-        _lib.check(lib.plp_overlap_pairs_dev(ctx.handle, stream, n, m_max, d, _ptr(A), _ptr(b), _ptr(m),
-                                             float(abs_tol), _ptr(out)), "plp_overlap_pairs_dev")
-        return out
-    A = _np(A)
-    n, m_max, d = A.shape
-    b = _np(b).reshape(n, m_max)
-    mm = None if m is None else _np(m, np.int32).reshape(n)
-    _finite_or_raise("overlap_pairs", A, b)
-    out = np.zeros((n, n), np.uint8)
-    _count_h2d(A, b, mm)
-    _lib.check(lib.plp_overlap_pairs(_lib.context().handle, n, m_max, d, _ptr(A), _ptr(b), _ptr(mm), float(abs_tol),
-                                     _ptr(out)), "plp_overlap_pairs")
+    be, A, b, m, n, m_max, d = _cells("overlap_pairs", A, b, m)
+    out = be.out((n, n), np.uint8, zero=True)
+    be.call("plp_overlap_pairs", n, m_max, d, A, b, m, float(abs_tol), out, h2d=(A, b, m))
     return out
 
 
@@ -662,54 +542,20 @@ def overlap_cross(A, b, n1, m=None, thresh=1e-7):
     """uint8[n1, n - n1]: 1 where the stack [cell a; cell c] of cell a < n1 of the table and cell c >= n1 has a Chebyshev
     radius > thresh -- the opening scan of region_diff (polytope.py:2148-2158) for every (minuend member, subtrahend
     cell) pair at once.  A[n, m_max, d], b[n, m_max]; 2 * m_max <= 64, d <= 16."""
-    lib = _lib.load()
     n1 = int(n1)
-    if _is_torch(A):
-        torch, ctx, stream = _torch_stream_ctx(A)
-        A = _tprep(torch, A, torch.float64)
-        b = _tprep(torch, b, torch.float64)
-        m = _tprep(torch, m, torch.int32)
-        n, m_max, d = A.shape
-        out = torch.empty((n1, n - n1), dtype=torch.uint8, device=A.device)
-        _lib.check(lib.plp_overlap_cross_dev(ctx.handle, stream, n1, n - n1, m_max, d, _ptr(A), _ptr(b), _ptr(m),
-                                             float(thresh), _ptr(out)), "plp_overlap_cross_dev")
-        return out
-    A = _np(A)
-    n, m_max, d = A.shape
-    b = _np(b).reshape(n, m_max)
-    mm = None if m is None else _np(m, np.int32).reshape(n)
-    _finite_or_raise("overlap_cross", A, b)
-    out = np.zeros((n1, n - n1), np.uint8)
-    _count_h2d(A, b, mm)
-    _lib.check(lib.plp_overlap_cross(_lib.context().handle, n1, n - n1, m_max, d, _ptr(A), _ptr(b), _ptr(mm), float(thresh),
-                                     _ptr(out)), "plp_overlap_cross")
+    be, A, b, m, n, m_max, d = _cells("overlap_cross", A, b, m)
+    out = be.out((n1, n - n1), np.uint8, zero=True)
+    be.call("plp_overlap_cross", n1, n - n1, m_max, d, A, b, m, float(thresh), out, h2d=(A, b, m))
     return out
 
 
 def adjacent_pairs_range(A, b, pair_lo, pair_hi, m=None, abs_tol=1e-7):
     """Adjacency of the cell pairs pair_lo <= p < pair_hi (p = i (i - 1) / 2 + j, j < i) -> uint8[pair_hi - pair_lo];
     one rank's shard of the O(n^2) loop of find_adjacent_regions (prop2partition.py:57-61)."""
-    lib = _lib.load()
     lo, hi = int(pair_lo), int(pair_hi)
-    if _is_torch(A):
-        torch, ctx, stream = _torch_stream_ctx(A)
-        A = _tprep(torch, A, torch.float64)
-        b = _tprep(torch, b, torch.float64)
-        m = _tprep(torch, m, torch.int32)
-        n, m_max, d = A.shape
-        out = torch.empty((max(hi - lo, 0),), dtype=torch.uint8, device=A.device)
-        _lib.check(lib.plp_adjacent_pairs_range_dev(ctx.handle, stream, n, m_max, d, _ptr(A), _ptr(b), _ptr(m),
-                                                    float(abs_tol), lo, hi, _ptr(out)), "plp_adjacent_pairs_range_dev")
-        return out
-    A = _np(A)
-    n, m_max, d = A.shape
-    b = _np(b).reshape(n, m_max)
-    mm = None if m is None else _np(m, np.int32).reshape(n)
-    _finite_or_raise("adjacent_pairs_range", A, b)
-    out = np.zeros(max(hi - lo, 0), np.uint8)
-    _count_h2d(A, b, mm)
-    _lib.check(lib.plp_adjacent_pairs_range(_lib.context().handle, n, m_max, d, _ptr(A), _ptr(b), _ptr(mm),
-                                            float(abs_tol), lo, hi, _ptr(out)), "plp_adjacent_pairs_range")
+    be, A, b, m, n, m_max, d = _cells("adjacent_pairs_range", A, b, m)
+    out = be.out((max(hi - lo, 0),), np.uint8, zero=True)
+    be.call("plp_adjacent_pairs_range", n, m_max, d, A, b, m, float(abs_tol), lo, hi, out, h2d=(A, b, m))
     return out
 
 
@@ -810,52 +656,20 @@ def quickhull_run(X0, simplex, abs_tol=1e-7):
 
 # ------------------------------------------------------------------------------------- projection (Fourier-Motzkin)
 def _fm_call(emit, A, b, col, m=None, keep=None, flags=None, first=False, abs_tol=1e-7, mo_max=0):
-    lib = _lib.load()
-    if _is_torch(A):
-        torch, ctx, stream = _torch_stream_ctx(A)
-        A = _tprep(torch, A, torch.float64)
-        b = _tprep(torch, b, torch.float64)
-        m = _tprep(torch, m, torch.int32)
-        flags = _tprep(torch, flags, torch.int32)
-        if keep is not None:
-            keep = _tprep(torch, keep.reshape(keep.shape[0], -1), torch.int64)
-        B, m_max, d = A.shape
-        kw = 0 if keep is None else int(keep.shape[1])
-        dout = d - 1 if col >= 0 else d
-        if not emit:
-            count = torch.empty((B,), dtype=torch.int32, device=A.device)
-            _lib.check(lib.plp_fm_count_dev(ctx.handle, stream, B, m_max, d, _ptr(A), _ptr(b), _ptr(m), _ptr(keep), kw,
-                                            _ptr(flags), int(col), int(bool(first)), float(abs_tol), _ptr(count)),
-                       "plp_fm_count_dev")
-            return count
-        Ao = torch.empty((B, mo_max, dout), dtype=torch.float64, device=A.device)
-        bo = torch.empty((B, mo_max), dtype=torch.float64, device=A.device)
-        mo = torch.empty((B,), dtype=torch.int32, device=A.device)
-        _lib.check(lib.plp_fm_emit_dev(ctx.handle, stream, B, m_max, d, _ptr(A), _ptr(b), _ptr(m), _ptr(keep), kw,
-                                       _ptr(flags), int(col), int(bool(first)), float(abs_tol), int(mo_max), _ptr(Ao),
-                                       _ptr(bo), _ptr(mo)), "plp_fm_emit_dev")
-        return Ao, bo, mo
-    A = _np(A)
-    if A.ndim != 3:
-        raise ValueError("A must be [B, m_max, d]")
-    B, m_max, d = A.shape
-    b = _np(b).reshape(B, m_max)
-    mm = None if m is None else _np(m, np.int32).reshape(B)
-    fl = None if flags is None else _np(flags, np.int32).reshape(B)
-    kp = None if keep is None else _np(keep, np.uint64).reshape(B, -1)
-    kw = 0 if kp is None else kp.shape[1]
-    dout = d - 1 if col >= 0 else d
+    be = _Backend(A)
+    A, b, m, (B, m_max, d) = _packed(be, A, b, m)
+    flags = be.arr(flags, np.int32, (B,))
+    if keep is not None:
+        keep = be.arr(keep.reshape(keep.shape[0], -1) if be.torch is not None else keep, np.uint64, (B, -1))
+    kw = 0 if keep is None else int(keep.shape[1])
+    head = (B, m_max, d, A, b, m, keep, kw, flags, int(col), int(bool(first)), float(abs_tol))
     if not emit:
-        count = np.empty(B, np.int32)
-        _lib.check(lib.plp_fm_count(_lib.context().handle, B, m_max, d, _ptr(A), _ptr(b), _ptr(mm), _ptr(kp), kw, _ptr(fl),
-                                    int(col), int(bool(first)), float(abs_tol), _ptr(count)), "plp_fm_count")
+        count = be.out((B,), np.int32)
+        be.call("plp_fm_count", *head, count)
         return count
-    Ao = np.empty((B, mo_max, dout))
-    bo = np.empty((B, mo_max))
-    mo = np.empty(B, np.int32)
-    _lib.check(lib.plp_fm_emit(_lib.context().handle, B, m_max, d, _ptr(A), _ptr(b), _ptr(mm), _ptr(kp), kw, _ptr(fl),
-                               int(col), int(bool(first)), float(abs_tol), int(mo_max), _ptr(Ao), _ptr(bo), _ptr(mo)),
-               "plp_fm_emit")
+    Ao, bo = be.out((B, mo_max, d - 1 if col >= 0 else d)), be.out((B, mo_max))
+    mo = be.out((B,), np.int32)
+    be.call("plp_fm_emit", *head, int(mo_max), Ao, bo, mo)
     return Ao, bo, mo
 
 

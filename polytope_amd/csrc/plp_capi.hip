@@ -1,395 +1,9 @@
 // plp_capi.hip -- extern "C" boundary of libplp_hip.so (declared in include/plp.h).
 // Host-pointer entry points stage through a grow-only device scratch arena owned by the
 // context, call the *_dev entry point on the context's stream and synchronise.
-#include <stdarg.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <chrono>
-#include <algorithm>
-#include <initializer_list>
-#include <string>
-#include <utility>
-#include <unordered_map>
-#include <vector>
-
-#include "../../include/plp.h"
-#include "plp_kernels.hpp"
-#include "plp_stage.hpp"
+#include "plp_hostcall.hpp"
 
 namespace {
-
-thread_local char g_err[512] = "";
-
-int fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess) return fail(PLP_EHIP, "%s: %s", #expr, hipGetErrorString(e_));   \
-    } while (0)
-
-}  // namespace
-
-namespace plp {
-size_t verify_scratch_bytes(long long nlp, int m_max);
-bool verify_enabled();
-int launch_verify_lp(long long B, int m_max, int n, const double* c, const double* G, const double* h, const int* mrows,
-                     double* x, double* fun, int* status, void* scratch, int parity, hipStream_t st);
-int launch_verify_cheby(long long B, int m_max, int d, const double* A, const double* b, const int* mrows, double* r,
-                        double* xc, int* status, void* scratch, int parity, hipStream_t st);
-int launch_verify_box(long long B, int m_max, int d, const double* A, const double* b, const int* mrows, double* lb, double* ub,
-                      int* status, const signed char* basis8, const double* centre, const double* xfin, void* scratch,
-                      int parity, hipStream_t st);
-}  // namespace plp
-
-struct plp_ctx {
-    int device;
-    hipStream_t stream;
-    char* arena;
-    size_t arena_bytes;
-    char* pin;  // pinned host mirror of the first SMALL_XFER bytes of the arena (small calls: one copy each way)
-    // region_diff search (kept across calls: a pinned allocation costs more than a small search)
-    char* rd_pin = nullptr;      // host-mapped block [index block | radii | sequence word]
-    char* rd_pin_dev = nullptr;
-    double* rd_out = nullptr;    // radii of a batch (device)
-    double* rd_tab = nullptr;    // the constraint table A | b (device)
-    size_t rd_tab_bytes = 0;
-    unsigned long long rd_seq = 0;
-    // the search's resident LP server (plp_rdiff.hip: rdiff_server_kernel): host-mapped mailbox / records / results block,
-    // its device view, the device-side state words, the sequence number of the last batch
-    char* rd_srv = nullptr;
-    char* rd_srv_dev = nullptr;
-    unsigned long long* rd_srv_state = nullptr;
-    unsigned long long rd_srv_seq = 0;    // batches issued so far
-    unsigned long long rd_srv_word = 0;   // mailbox word of the last batch that was answered
-    unsigned long long rd_srv_init[4] = {0, 0, 0, 0};
-    // containment: per-row thresholds of the comparison form (plp_points.hip), a grow-only buffer
-    void* mf_buf = nullptr;
-    size_t mf_bytes = 0;
-    hipEvent_t mf_ev = nullptr;  // recorded after every launch that uses mf_buf: the next user (any stream) waits on it
-    bool mf_used = false;
-    // device / pinned buffers of the last quickhull session that ended (plp_hull_destroy parks them here, plp_hull_create
-    // takes them when they are large enough): hipMalloc / hipFree of five buffers cost more than a 100 000-point hull
-    struct HullSpare {
-        double* X = nullptr; int32_t* owner = nullptr; double* dist = nullptr; uint8_t* dead = nullptr;
-        char* io = nullptr; char* pin = nullptr;
-        size_t X_bytes = 0, owner_bytes = 0, dist_bytes = 0, dead_cap = 0, io_bytes = 0;
-        bool full = false;
-    } hull_spare;
-    // large host-pointer batches (plp_stage.hpp): staging threads, pinned staging buffer, copy stream, one event per chunk
-    plp::StagePool* pool = nullptr;
-    char* stage = nullptr;
-    size_t stage_bytes = 0;
-    hipStream_t copy_stream = nullptr;
-    hipEvent_t stage_ev[16] = {};
-    int stage_nev = 0;
-    bool check_finite = false;  // plp_ctx_set_check_finite
-    // plp_reduce_counters: device word the fused reduce kernels add their simplex-run count to (lazily allocated; the
-    // kernels get nullptr until the first plp_reduce_counters call of the context, and then it costs one atomic per tile)
-    unsigned long long* reduce_ctr = nullptr;
-    // fused reduce: one word per call in flight (a ring of 64) that the fast kernels raise to the call's number when they
-    // hand a polytope to the general kernel, so that its second pass can leave on one load (plp_reduce.hip)
-    unsigned long long* retry_ring = nullptr;
-    unsigned long long reduce_epoch = 0;
-    // plp_assign_dev (few facets): the workgroups' (max, index) partials, one grow-only buffer PER STREAM -- calls on
-    // different streams never share one, so nothing has to order them (a handful of streams per context in practice;
-    // beyond 16 the table is emptied after a device synchronisation)
-    struct StreamBuf { void* p = nullptr; size_t bytes = 0; unsigned calls = 0; };
-    std::unordered_map<void*, StreamBuf> as_scratch;
-    // the verifier behind the LP / Chebyshev / bounding-box batches (plp_verify.hip): fail list + the careful engine's
-    // dictionaries, one grow-only buffer per stream like as_scratch; bounding boxes: the engines' bases and centres
-    std::unordered_map<void*, StreamBuf> vf_scratch;
-    std::unordered_map<void*, StreamBuf> vf_basis;
-};
-
-namespace {
-
-struct Arena {
-    plp_ctx* ctx;
-    size_t off;
-    explicit Arena(plp_ctx* c) : ctx(c), off(0) {}
-    template <typename T>
-    T* take(size_t count) {
-        T* p = reinterpret_cast<T*>(ctx->arena + off);
-        off += (count * sizeof(T) + 255) & ~(size_t)255;
-        return p;
-    }
-};
-
-size_t pad(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-
-// a grow-only device buffer of this stream (see plp_ctx::as_scratch); nullptr: allocation failed
-void* stream_buf(std::unordered_map<void*, plp_ctx::StreamBuf>& table, void* stream, size_t need) {
-    if (table.size() >= 16 && !table.count(stream)) {
-        (void)hipDeviceSynchronize();
-        for (auto& kv : table) if (kv.second.p) (void)hipFree(kv.second.p);
-        table.clear();
-    }
-    plp_ctx::StreamBuf& sb = table[stream];
-    if (need > sb.bytes) {
-        if (sb.p) { (void)hipStreamSynchronize((hipStream_t)stream); (void)hipFree(sb.p); }  // (its last user ran on this stream)
-        sb.p = nullptr;
-        sb.bytes = 0;
-        if (hipMalloc(&sb.p, need + need / 4) == hipSuccess) {
-            sb.bytes = need + need / 4;
-            sb.calls = 0;
-            (void)hipMemsetAsync(sb.p, 0, 256, (hipStream_t)stream);   // (the verifier's list counters start at zero)
-        } else {
-            (void)hipGetLastError();
-        }
-    }
-    return sb.p;
-}
-
-int ensure_arena(plp_ctx* ctx, size_t bytes) {
-    if (bytes <= ctx->arena_bytes) return PLP_OK;
-    if (ctx->arena) HIP_TRY(hipFree(ctx->arena));
-    ctx->arena = nullptr;
-    ctx->arena_bytes = 0;
-    size_t want = bytes + bytes / 4;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&ctx->arena), want));
-    ctx->arena_bytes = want;
-    return PLP_OK;
-}
-
-// Host-pointer calls whose buffers fit SMALL_XFER move them through the pinned mirror: the inputs are
-// gathered into it and cross PCIe as ONE copy, likewise the outputs.  A pageable hipMemcpyAsync of a few
-// hundred bytes costs 10-20 us, and the set operations issue hundreds of small batches (region_diff: one
-// per search level), so six copies per call were most of such a call.  Large calls copy each array directly.
-constexpr size_t SMALL_XFER = 1u << 20;
-
-struct Span {
-    void* dev;
-    const void* host_in;  // copy_in source (or nullptr)
-    void* host_out;       // copy_out destination (or nullptr)
-    size_t bytes;
-};
-
-int ensure_pin(plp_ctx* ctx) {
-    if (ctx->pin) return PLP_OK;
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&ctx->pin), SMALL_XFER, hipHostMallocDefault));
-    return PLP_OK;
-}
-
-bool fits_small(plp_ctx* ctx, std::initializer_list<Span> spans) {
-    for (const Span& sp : spans) {
-        if (!sp.bytes) continue;
-        const size_t end = (size_t)(static_cast<char*>(sp.dev) - ctx->arena) + sp.bytes;
-        if (end > SMALL_XFER) return false;
-    }
-    return true;
-}
-
-int copy_in(plp_ctx* ctx, hipStream_t st, std::initializer_list<Span> spans) {
-    if (fits_small(ctx, spans) && ensure_pin(ctx) == PLP_OK) {
-        size_t lo = SMALL_XFER, hi = 0;
-        for (const Span& sp : spans) {
-            if (!sp.bytes || !sp.host_in) continue;
-            const size_t off = (size_t)(static_cast<char*>(sp.dev) - ctx->arena);
-            memcpy(ctx->pin + off, sp.host_in, sp.bytes);
-            lo = off < lo ? off : lo;
-            hi = off + sp.bytes > hi ? off + sp.bytes : hi;
-        }
-        if (hi > lo) HIP_TRY(hipMemcpyAsync(ctx->arena + lo, ctx->pin + lo, hi - lo, hipMemcpyHostToDevice, st));
-        return PLP_OK;
-    }
-    for (const Span& sp : spans)
-        if (sp.bytes && sp.host_in) HIP_TRY(hipMemcpyAsync(sp.dev, sp.host_in, sp.bytes, hipMemcpyHostToDevice, st));
-    return PLP_OK;
-}
-
-// Large host-pointer batch: the per-unit input arrays go to the device chunk by chunk (plp_stage.hpp) and `launch(lo, hi)`
-// enqueues the kernels of units [lo, hi) on `st` behind the arrival of their chunk.  *staged = false: not applicable
-// (small batch, PLP_STAGE=0, or a resource could not be had) and nothing was done -- the caller copies as before.
-struct StageArray {
-    const void* host;
-    void* dev;
-    size_t unit_bytes;
-    bool f64 = false;  // doubles (checked for inf / nan when the context asks for it)
-};
-
-const char* const NONFINITE_MSG = "input must not contain values inf, nan, or None";
-
-// plp_ctx_set_check_finite, inputs that are not staged chunk-wise: one pass over each array
-int finite_or_fail(plp_ctx* ctx, std::initializer_list<std::pair<const double*, size_t>> arrays) {
-    if (!ctx->check_finite) return PLP_OK;
-    for (const auto& a : arrays)
-        if (a.first && a.second && plp::any_nonfinite_f64(reinterpret_cast<const char*>(a.first), a.second * 8))
-            return fail(PLP_ENONFINITE, "%s", NONFINITE_MSG);
-    return PLP_OK;
-}
-
-// The arrays' device regions (neighbours in the arena, `blk` .. `blk + blk_bytes`) are used as ONE block in which every
-// chunk's pieces sit back to back -- the layout of the staging buffer -- so that a chunk crosses PCIe as one copy;
-// `launch(lo, hi, ptrs)` gets the device address of each array's rows lo.. (ptrs[i] for arrays[i], NULL where host is).
-template <typename F>
-int staged_run(plp_ctx* ctx, hipStream_t st, int64_t B, int64_t align, std::initializer_list<StageArray> arrays, char* blk,
-               size_t blk_bytes, F launch, bool* staged) {
-    *staged = false;
-    size_t unit = 0;
-    for (const StageArray& a : arrays)
-        if (a.host) unit += a.unit_bytes;
-    const size_t total = unit * (size_t)B;
-    const char* off = getenv("PLP_STAGE");
-    if ((off && off[0] == '0') || total < (8u << 20) || B < 4 * align || total > blk_bytes || arrays.size() > 8) return PLP_OK;
-    if (!ctx->pool) {
-        const char* nt = getenv("PLP_STAGE_THREADS");
-        unsigned hw = std::thread::hardware_concurrency();
-        int n = nt ? atoi(nt) : (hw >= 16 ? 7 : (hw >= 4 ? (int)hw / 2 - 1 : 1));
-        if (n < 1) n = 1;
-        if (n > 32) n = 32;
-        try {
-            ctx->pool = new plp::StagePool(n);
-        } catch (...) {  // no threads to be had: the caller copies as before
-            ctx->pool = nullptr;
-            return PLP_OK;
-        }
-    }
-    if (!ctx->copy_stream && hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking) != hipSuccess) {
-        (void)hipGetLastError();
-        ctx->copy_stream = nullptr;
-        return PLP_OK;
-    }
-    while (ctx->stage_nev < 16) {
-        if (hipEventCreateWithFlags(&ctx->stage_ev[ctx->stage_nev], hipEventDisableTiming) != hipSuccess) {
-            (void)hipGetLastError();
-            return PLP_OK;
-        }
-        ++ctx->stage_nev;
-    }
-    if (total > ctx->stage_bytes) {
-        if (ctx->stage) (void)hipHostFree(ctx->stage);
-        ctx->stage = nullptr;
-        ctx->stage_bytes = 0;
-        if (hipHostMalloc(reinterpret_cast<void**>(&ctx->stage), total + total / 4, hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError();
-            return PLP_OK;
-        }
-        ctx->stage_bytes = total + total / 4;
-    }
-    int64_t nch = (int64_t)(total / (4u << 20));
-    nch = nch < 2 ? 2 : (nch > 16 ? 16 : nch);
-    int64_t per = (B + nch - 1) / nch;
-    per = (per + align - 1) / align * align;
-    nch = (B + per - 1) / per;
-    std::vector<std::vector<plp::StagePiece>> chunks;
-    try {
-        chunks.resize((size_t)nch);
-        for (auto& c : chunks) c.reserve(arrays.size());
-    } catch (...) {
-        return PLP_OK;
-    }
-    size_t so = 0;  // (unit sizes are multiples of 4 and chunk lengths multiples of `align` >= 16: every piece 8-byte aligned)
-    for (int64_t c = 0; c < nch; ++c) {
-        const int64_t lo = c * per, hi = lo + per < B ? lo + per : B;
-        for (const StageArray& a : arrays) {
-            if (!a.host) continue;
-            const size_t bytes = (size_t)(hi - lo) * a.unit_bytes;
-            chunks[(size_t)c].push_back({static_cast<const char*>(a.host) + (size_t)lo * a.unit_bytes, ctx->stage + so, blk + so,
-                                         bytes, a.f64 && ctx->check_finite});
-            so += bytes;
-        }
-    }
-    // the copy stream must not overwrite device inputs an earlier call on `st` may still be reading
-    HIP_TRY(hipEventRecord(ctx->stage_ev[15], st));
-    HIP_TRY(hipStreamWaitEvent(ctx->copy_stream, ctx->stage_ev[15], 0));
-    const bool timing = getenv("PLP_STAGE_TIMING") != nullptr;
-    const auto t0 = std::chrono::steady_clock::now();
-    auto us = [&] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); };
-    ctx->pool->start(chunks);
-    *staged = true;
-    int rc = PLP_OK;
-    for (int64_t c = 0; c < nch && rc == PLP_OK; ++c) {
-        ctx->pool->wait((int)c);
-        if (timing) fprintf(stderr, "[stage] chunk %d staged at %.0f us\n", (int)c, us());
-        if (ctx->pool->nonfinite()) break;  // (set only when the context checks its inputs)
-        void* ptrs[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        {
-            const std::vector<plp::StagePiece>& pc = chunks[(size_t)c];
-            size_t bytes = 0, k = 0, i = 0;
-            for (const StageArray& a : arrays) {
-                if (a.host) { ptrs[i] = pc[k].dev; bytes += pc[k].bytes; ++k; }
-                ++i;
-            }
-            const hipError_t e = hipMemcpyAsync(pc[0].dev, pc[0].dst, bytes, hipMemcpyHostToDevice, ctx->copy_stream);
-            if (e != hipSuccess) rc = fail(PLP_EHIP, "staged upload: %s", hipGetErrorString(e));
-        }
-        if (rc == PLP_OK && (hipEventRecord(ctx->stage_ev[c % 15], ctx->copy_stream) != hipSuccess ||
-                             hipStreamWaitEvent(st, ctx->stage_ev[c % 15], 0) != hipSuccess))
-            rc = fail(PLP_EHIP, "staged upload: event");
-        const int64_t lo = c * per, hi = lo + per < B ? lo + per : B;
-        if (rc == PLP_OK) rc = launch(lo, hi, ptrs);
-    }
-    ctx->pool->finish();
-    if (timing) {
-        fprintf(stderr, "[stage] all enqueued at %.0f us\n", us());
-        (void)hipStreamSynchronize(ctx->copy_stream);
-        fprintf(stderr, "[stage] copies done at %.0f us\n", us());
-        (void)hipStreamSynchronize(st);
-        fprintf(stderr, "[stage] kernels done at %.0f us (%d chunks, %zu bytes)\n", us(), (int)nch, total);
-    }
-    if (rc == PLP_OK && ctx->pool->nonfinite()) rc = fail(PLP_ENONFINITE, "%s", NONFINITE_MSG);
-    if (rc != PLP_OK) {  // nothing of this call may still be in flight when the caller sees the error
-        (void)hipStreamSynchronize(ctx->copy_stream);
-        (void)hipStreamSynchronize(st);
-    }
-    return rc;
-}
-
-// copies the outputs to the host and synchronises the stream
-int copy_out(plp_ctx* ctx, hipStream_t st, std::initializer_list<Span> spans) {
-    // after a staged upload (plp_stage.hpp): the outputs (neighbours in the arena) come back as ONE copy into the pinned
-    // staging buffer and the staging threads hand them out -- five pageable D2H copies of a C2 batch cost 1.5 ms
-    if (ctx->pool && ctx->stage) {
-        size_t lo = ~(size_t)0, hi = 0;
-        for (const Span& sp : spans) {
-            if (!sp.bytes || !sp.host_out) continue;
-            const size_t off = (size_t)(static_cast<char*>(sp.dev) - ctx->arena);
-            lo = off < lo ? off : lo;
-            hi = off + sp.bytes > hi ? off + sp.bytes : hi;
-        }
-        if (hi > lo && hi - lo >= SMALL_XFER && hi - lo <= ctx->stage_bytes) {
-            HIP_TRY(hipMemcpyAsync(ctx->stage, ctx->arena + lo, hi - lo, hipMemcpyDeviceToHost, st));
-            std::vector<std::vector<plp::StagePiece>> one(1);
-            for (const Span& sp : spans)
-                if (sp.bytes && sp.host_out)
-                    one[0].push_back({ctx->stage + ((size_t)(static_cast<char*>(sp.dev) - ctx->arena) - lo),
-                                      static_cast<char*>(sp.host_out), nullptr, sp.bytes});
-            HIP_TRY(hipStreamSynchronize(st));
-            ctx->pool->start(one);
-            ctx->pool->wait(0);
-            ctx->pool->finish();
-            return PLP_OK;
-        }
-    }
-    if (fits_small(ctx, spans) && ensure_pin(ctx) == PLP_OK) {
-        size_t lo = SMALL_XFER, hi = 0;
-        for (const Span& sp : spans) {
-            if (!sp.bytes || !sp.host_out) continue;
-            const size_t off = (size_t)(static_cast<char*>(sp.dev) - ctx->arena);
-            lo = off < lo ? off : lo;
-            hi = off + sp.bytes > hi ? off + sp.bytes : hi;
-        }
-        if (hi > lo) HIP_TRY(hipMemcpyAsync(ctx->pin + lo, ctx->arena + lo, hi - lo, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        for (const Span& sp : spans)
-            if (sp.bytes && sp.host_out)
-                memcpy(sp.host_out, ctx->pin + (size_t)(static_cast<char*>(sp.dev) - ctx->arena), sp.bytes);
-        return PLP_OK;
-    }
-    for (const Span& sp : spans)
-        if (sp.bytes && sp.host_out) HIP_TRY(hipMemcpyAsync(sp.host_out, sp.dev, sp.bytes, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return PLP_OK;
-}
 
 int check_launch(const char* what) {
     hipError_t e = hipGetLastError();
@@ -530,20 +144,30 @@ int plp_verify_counters(plp_ctx* ctx, void* stream, int64_t* careful_lps) {
     return PLP_OK;
 }
 
+// Each operation below: its argument checks, shared by the device-pointer entry point and its host-pointer twin (sizes,
+// NULL pointers, then the envelope: all before a host buffer is read; rc == PLP_OK with an empty batch means "nothing to
+// do"), the device-pointer entry point, and the host-pointer one on a HostCall.
 // ------------------------------------------------------------------------------- lp_solve
-int plp_lp_solve_batch_dev(plp_ctx* ctx, void* stream, int64_t B, int m_max, int n, const double* c,
-                           const double* G, const double* h, const int32_t* m, double* x, double* fun,
-                           int32_t* status, int32_t* iters) {
+static int check_lp(plp_ctx* ctx, int64_t B, int m_max, int n, const double* c, const double* G, const double* h,
+                    const double* x, const double* fun, const int32_t* status) {
     if (!ctx) return fail(PLP_EINVAL, "ctx is NULL");
     if (B < 0 || m_max < 0 || n < 1) return fail(PLP_EINVAL, "bad sizes B=%lld m_max=%d n=%d", (long long)B, m_max, n);
     if (B == 0) return PLP_OK;
     if (!c || !h || !x || !fun || !status || (!G && m_max > 0)) return fail(PLP_EINVAL, "NULL pointer");
     if (n > plp::MAX_D + 1 || (m_max > plp::MAX_M && !plp::lds_lp_bytes(m_max, n + 1)))
         return fail(PLP_EUNSUPPORTED, "m_max=%d n=%d outside envelope (n<=17; rows: the dictionary must fit 160 KB of LDS)", m_max, n);
+    return PLP_OK;
+}
+
+int plp_lp_solve_batch_dev(plp_ctx* ctx, void* stream, int64_t B, int m_max, int n, const double* c,
+                           const double* G, const double* h, const int32_t* m, double* x, double* fun,
+                           int32_t* status, int32_t* iters) {
+    int rc = check_lp(ctx, B, m_max, n, c, G, h, x, fun, status);
+    if (rc || B == 0) return rc;
     hipStream_t st = (hipStream_t)stream;  // NULL = the HIP default stream
     if (plp::launch_lp(B, m_max, n, c, G, h, m, x, fun, status, iters, st))
         return fail(PLP_EUNSUPPORTED, "lp kernel: unsupported size");
-    int rc = check_launch("lp_kernel");
+    rc = check_launch("lp_kernel");
     if (rc) return rc;
     return verify_lp_answers(ctx, st, B, m_max, n, c, G, h, m, x, fun, status);
 }
@@ -551,141 +175,118 @@ int plp_lp_solve_batch_dev(plp_ctx* ctx, void* stream, int64_t B, int m_max, int
 int plp_lp_solve_batch(plp_ctx* ctx, int64_t B, int m_max, int n, const double* c, const double* G,
                        const double* h, const int32_t* m, double* x, double* fun, int32_t* status,
                        int32_t* iters) {
-    if (!ctx) return fail(PLP_EINVAL, "ctx is NULL");
-    if (B < 0 || m_max < 0 || n < 1) return fail(PLP_EINVAL, "bad sizes");
-    if (B == 0) return PLP_OK;
-    if (!c || !h || !x || !fun || !status || (!G && m_max > 0)) return fail(PLP_EINVAL, "NULL pointer");
-    if (n > plp::MAX_D + 1 || (m_max > plp::MAX_M && !plp::lds_lp_bytes(m_max, n + 1)))  // before any buffer is read
-        return fail(PLP_EUNSUPPORTED, "m_max=%d n=%d outside envelope (n<=17; rows: the dictionary must fit 160 KB of LDS)", m_max, n);
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t nc = (size_t)B * n, nG = (size_t)B * m_max * n, nh = (size_t)B * m_max;
-    size_t need = pad(nc * 8) * 2 + pad(nG * 8) + pad(nh * 8) + pad(B * 8) + pad(B * 4) * 3 + 4096;
-    int rc = ensure_arena(ctx, need);
+    int rc = check_lp(ctx, B, m_max, n, c, G, h, x, fun, status);
+    if (rc || B == 0) return rc;
+    const size_t nc = (size_t)B * n, mn = (size_t)m_max * n;
+    double *dc, *dG, *dh, *dx, *dfun;
+    int32_t *dm, *dst, *dit;
+    HostCall hc(ctx);
+    hc.in(dc, c, nc, n, true);
+    hc.in(dG, G, (size_t)B * mn, mn, true);
+    hc.in(dh, h, (size_t)B * m_max, m_max, true);
+    hc.in(dm, m, B, 1);
+    hc.out(dx, x, nc);
+    hc.out(dfun, fun, B);
+    hc.out(dst, status, B);
+    hc.out(dit, iters, B);
+    rc = hc.reserve();
     if (rc) return rc;
-    Arena a(ctx);
-    double* dc = a.take<double>(nc);
-    double* dG = a.take<double>(nG ? nG : 1);
-    double* dh = a.take<double>(nh ? nh : 1);
-    int32_t* dm = a.take<int32_t>(B);
-    double* dx = a.take<double>(nc);
-    double* dfun = a.take<double>(B);
-    int32_t* dst = a.take<int32_t>(B);
-    int32_t* dit = a.take<int32_t>(B);
-    hipStream_t st = ctx->stream;
+    hipStream_t st = hc.st;
     bool staged = false;  // large batches: chunked upload, kernels of earlier chunks running meanwhile (plp_stage.hpp)
     int more = 0;
-    const size_t mn = (size_t)m_max * n;
-    rc = staged_run(ctx, st, B, 64,
-                    {{c, dc, (size_t)n * 8, true}, {G, dG, mn * 8, true}, {h, dh, (size_t)m_max * 8, true}, {m, dm, 4}},
-                    reinterpret_cast<char*>(dc), (size_t)(reinterpret_cast<char*>(dm + B) - reinterpret_cast<char*>(dc)),
-                    [&](int64_t lo, int64_t hi, void* const* q) {
-                        return plp_lp_solve_batch_dev(ctx, st, hi - lo, m_max, n, static_cast<double*>(q[0]),
-                                                      static_cast<double*>(q[1]), static_cast<double*>(q[2]),
-                                                      static_cast<int32_t*>(q[3]), dx + (size_t)lo * n, dfun + lo, dst + lo,
-                                                      dit + lo);
-                    },
-                    &staged);
+    rc = hc.upload_staged(B, 64,
+                          [&](int64_t lo, int64_t hi) {
+                              return plp_lp_solve_batch_dev(ctx, st, hi - lo, m_max, n, dc, dG, dh, dm, dx + (size_t)lo * n,
+                                                            dfun + lo, dst + lo, dit + lo);
+                          },
+                          &staged);
     if (rc) return rc;
     if (!staged) {
-        rc = finite_or_fail(ctx, {{c, nc}, {G, nG}, {h, nh}});
-        if (rc) return rc;
-        rc = copy_in(ctx, st, {{dc, c, nullptr, nc * 8}, {dG, G, nullptr, nG * 8}, {dh, h, nullptr, nh * 8},
-                               {dm, m, nullptr, m ? (size_t)B * 4 : 0}});
+        rc = hc.upload();
         if (rc) return rc;
         // small batches: the fast kernels now; the general kernel only if a status, host-visible below anyway, asks for it
         if (B <= 16384 && !plp::verify_enabled()) {
-            if (plp::launch_lp_phase(B, m_max, n, dc, dG, dh, m ? dm : nullptr, dx, dfun, dst, dit, st, 1, &more))
+            if (plp::launch_lp_phase(B, m_max, n, dc, dG, dh, dm, dx, dfun, dst, dit, st, 1, &more))
                 return fail(PLP_EUNSUPPORTED, "lp kernel: unsupported size");
             rc = check_launch("lp_kernel");
         } else {  // (with the verifier behind the engines both passes are launched: it has to see final answers)
-            rc = plp_lp_solve_batch_dev(ctx, st, B, m_max, n, dc, dG, dh, m ? dm : nullptr, dx, dfun, dst, dit);
+            rc = plp_lp_solve_batch_dev(ctx, st, B, m_max, n, dc, dG, dh, dm, dx, dfun, dst, dit);
         }
         if (rc) return rc;
     }
-    rc = copy_out(ctx, st, {{dx, nullptr, x, nc * 8}, {dfun, nullptr, fun, (size_t)B * 8},
-                            {dst, nullptr, status, (size_t)B * 4}, {dit, nullptr, iters, iters ? (size_t)B * 4 : 0}});
+    rc = hc.download();
     if (rc || !more) return rc;
     bool again = false;
     for (int64_t k = 0; k < B && !again; ++k) again = status[k] == plp::ST_RETRY;
     if (!again) return PLP_OK;
-    if (plp::launch_lp_phase(B, m_max, n, dc, dG, dh, m ? dm : nullptr, dx, dfun, dst, dit, st, 2, nullptr))
+    if (plp::launch_lp_phase(B, m_max, n, dc, dG, dh, dm, dx, dfun, dst, dit, st, 2, nullptr))
         return fail(PLP_EUNSUPPORTED, "lp kernel: unsupported size");
     rc = check_launch("lp_kernel");
     if (rc) return rc;
-    return copy_out(ctx, st, {{dx, nullptr, x, nc * 8}, {dfun, nullptr, fun, (size_t)B * 8},
-                              {dst, nullptr, status, (size_t)B * 4}, {dit, nullptr, iters, iters ? (size_t)B * 4 : 0}});
+    return hc.download();
 }
 
 // ------------------------------------------------------------------------------- cheby
-int plp_cheby_batch_dev(plp_ctx* ctx, void* stream, int64_t B, int m_max, int d, const double* A,
-                        const double* b, const int32_t* m, double* r, double* xc, int32_t* status) {
+// (cheby, bbox and reduce take the same inputs: `outs_ok` is the operation's own "no output pointer is NULL")
+static int check_Abm(plp_ctx* ctx, int64_t B, int m_max, int d, const double* A, const double* b, bool outs_ok) {
     if (!ctx) return fail(PLP_EINVAL, "ctx is NULL");
     if (B < 0 || m_max < 0 || d < 1) return fail(PLP_EINVAL, "bad sizes");
-    if (B == 0) return PLP_OK;
-    if (!r || !xc || !status || ((!A || !b) && m_max > 0)) return fail(PLP_EINVAL, "NULL pointer");
+    if (B > 0 && (!outs_ok || ((!A || !b) && m_max > 0))) return fail(PLP_EINVAL, "NULL pointer");
+    return PLP_OK;
+}
+
+static int check_cheby(plp_ctx* ctx, int64_t B, int m_max, int d, const double* A, const double* b, const double* r,
+                       const double* xc, const int32_t* status) {
+    int rc = check_Abm(ctx, B, m_max, d, A, b, r && xc && status);
+    if (rc || B == 0) return rc;
     if (d > plp::MAX_D || (m_max > plp::MAX_M && !plp::lds_lp_bytes(m_max, d + 1)))
         return fail(PLP_EUNSUPPORTED, "m_max=%d d=%d outside envelope (d<=16; rows: the dictionary must fit 160 KB of LDS)", m_max, d);
+    return PLP_OK;
+}
+
+int plp_cheby_batch_dev(plp_ctx* ctx, void* stream, int64_t B, int m_max, int d, const double* A,
+                        const double* b, const int32_t* m, double* r, double* xc, int32_t* status) {
+    int rc = check_cheby(ctx, B, m_max, d, A, b, r, xc, status);
+    if (rc || B == 0) return rc;
     hipStream_t st = (hipStream_t)stream;  // NULL = the HIP default stream
     if (plp::launch_cheby(B, m_max, d, A, b, m, r, xc, status, st))
         return fail(PLP_EUNSUPPORTED, "cheby kernel: unsupported size");
-    int rc = check_launch("cheby_kernel");
+    rc = check_launch("cheby_kernel");
     if (rc) return rc;
     return verify_cheby_answers(ctx, st, B, m_max, d, A, b, m, r, xc, status);
 }
 
 int plp_cheby_batch(plp_ctx* ctx, int64_t B, int m_max, int d, const double* A, const double* b,
                     const int32_t* m, double* r, double* xc, int32_t* status) {
-    if (!ctx) return fail(PLP_EINVAL, "ctx is NULL");
-    if (B < 0 || m_max < 0 || d < 1) return fail(PLP_EINVAL, "bad sizes");
-    if (B == 0) return PLP_OK;
-    if (!r || !xc || !status || ((!A || !b) && m_max > 0)) return fail(PLP_EINVAL, "NULL pointer");
-    if (d > plp::MAX_D || (m_max > plp::MAX_M && !plp::lds_lp_bytes(m_max, d + 1)))
-        return fail(PLP_EUNSUPPORTED, "m_max=%d d=%d outside envelope (d<=16; rows: the dictionary must fit 160 KB of LDS)", m_max, d);
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t nA = (size_t)B * m_max * d, nb = (size_t)B * m_max, nx = (size_t)B * d;
-    int rc = ensure_arena(ctx, pad(nA * 8) + pad(nb * 8) + pad(nx * 8) + pad(B * 8) + pad(B * 4) * 2 + 4096);
-    if (rc) return rc;
-    Arena a(ctx);
-    double* dA = a.take<double>(nA ? nA : 1);
-    double* db = a.take<double>(nb ? nb : 1);
-    int32_t* dm = a.take<int32_t>(B);
-    double* dr = a.take<double>(B);
-    double* dxc = a.take<double>(nx);
-    int32_t* dst = a.take<int32_t>(B);
-    hipStream_t st = ctx->stream;
-    bool staged = false;  // large batches: chunked upload, kernels of earlier chunks running meanwhile (plp_stage.hpp)
-    const size_t md = (size_t)m_max * d;
-    rc = staged_run(ctx, st, B, 64, {{A, dA, md * 8, true}, {b, db, (size_t)m_max * 8, true}, {m, dm, 4}},
-                    reinterpret_cast<char*>(dA), (size_t)(reinterpret_cast<char*>(dm + B) - reinterpret_cast<char*>(dA)),
-                    [&](int64_t lo, int64_t hi, void* const* q) {
-                        return plp_cheby_batch_dev(ctx, st, hi - lo, m_max, d, static_cast<double*>(q[0]),
-                                                   static_cast<double*>(q[1]), static_cast<int32_t*>(q[2]), dr + lo,
-                                                   dxc + (size_t)lo * d, dst + lo);
-                    },
-                    &staged);
-    if (rc) return rc;
-    if (!staged) {
-        rc = finite_or_fail(ctx, {{A, nA}, {b, nb}});
-        if (rc) return rc;
-        rc = copy_in(ctx, st, {{dA, A, nullptr, nA * 8}, {db, b, nullptr, nb * 8}, {dm, m, nullptr, m ? (size_t)B * 4 : 0}});
-        if (rc) return rc;
-        rc = plp_cheby_batch_dev(ctx, st, B, m_max, d, dA, db, m ? dm : nullptr, dr, dxc, dst);
-        if (rc) return rc;
-    }
-    return copy_out(ctx, st, {{dr, nullptr, r, (size_t)B * 8}, {dxc, nullptr, xc, nx * 8},
-                              {dst, nullptr, status, (size_t)B * 4}});
+    int rc = check_cheby(ctx, B, m_max, d, A, b, r, xc, status);
+    if (rc || B == 0) return rc;
+    double *dA, *db, *dr, *dxc;
+    int32_t *dm, *dst;
+    HostCall hc(ctx);
+    declare_Abm(hc, B, m_max, d, dA, A, db, b, dm, m);
+    hc.out(dr, r, B);
+    hc.out(dxc, xc, (size_t)B * d);
+    hc.out(dst, status, B);
+    return run_Abm(hc, B, 64, [&](int64_t lo, int64_t hi) {
+        return plp_cheby_batch_dev(ctx, hc.st, hi - lo, m_max, d, dA, db, dm, dr + lo, dxc + (size_t)lo * d, dst + lo);
+    });
 }
 
 // ------------------------------------------------------------------------------- bounding box
-int plp_bbox_batch_dev(plp_ctx* ctx, void* stream, int64_t B, int m_max, int d, const double* A, const double* b,
-                       const int32_t* m, double* lb, double* ub, int32_t* status) {
-    if (!ctx) return fail(PLP_EINVAL, "ctx is NULL");
-    if (B < 0 || m_max < 0 || d < 1) return fail(PLP_EINVAL, "bad sizes");
-    if (B == 0) return PLP_OK;
-    if (!lb || !ub || !status || ((!A || !b) && m_max > 0)) return fail(PLP_EINVAL, "NULL pointer");
+static int check_bbox(plp_ctx* ctx, int64_t B, int m_max, int d, const double* A, const double* b, const double* lb,
+                      const double* ub, const int32_t* status) {
+    int rc = check_Abm(ctx, B, m_max, d, A, b, lb && ub && status);
+    if (rc || B == 0) return rc;
     if (m_max > plp::MAX_M || d > plp::MAX_D)
         return fail(PLP_EUNSUPPORTED, "m_max=%d d=%d outside envelope (m<=64, d<=16)", m_max, d);
     if (m_max < 1) return fail(PLP_EUNSUPPORTED, "bbox kernel: m_max=%d (needs m_max >= 1)", m_max);
+    return PLP_OK;
+}
+
+int plp_bbox_batch_dev(plp_ctx* ctx, void* stream, int64_t B, int m_max, int d, const double* A, const double* b,
+                       const int32_t* m, double* lb, double* ub, int32_t* status) {
+    int rc = check_bbox(ctx, B, m_max, d, A, b, lb, ub, status);
+    if (rc || B == 0) return rc;
     hipStream_t st = (hipStream_t)stream;  // NULL = the HIP default stream
     // the verifier behind the fused kernels (plp_verify.hip): they hand over each box LP's final basis + the centre, or the
     // point the LP ended on; one buffer per stream: [bases 2 d d bytes | centres d doubles | points 2 d d doubles] per polytope
@@ -704,7 +305,7 @@ int plp_bbox_batch_dev(plp_ctx* ctx, void* stream, int64_t B, int m_max, int d, 
     }
     if (plp::launch_bbox(B, m_max, d, A, b, m, lb, ub, status, st, &ho))
         return fail(PLP_EUNSUPPORTED, "bbox kernel: unsupported size");
-    int rc = check_launch("bbox_r_kernel");
+    rc = check_launch("bbox_r_kernel");
     if (rc || !ho.mode) return rc;
     if (plp::launch_verify_box(B, m_max, d, A, b, m, lb, ub, status, ho.mode == 1 ? ho.basis8 : nullptr,
                                ho.mode == 1 ? ho.centre : nullptr, ho.mode == 2 ? ho.xfin : nullptr, vsc,
@@ -715,54 +316,36 @@ int plp_bbox_batch_dev(plp_ctx* ctx, void* stream, int64_t B, int m_max, int d, 
 
 int plp_bbox_batch(plp_ctx* ctx, int64_t B, int m_max, int d, const double* A, const double* b, const int32_t* m,
                    double* lb, double* ub, int32_t* status) {
-    if (!ctx) return fail(PLP_EINVAL, "ctx is NULL");
-    if (B < 0 || m_max < 0 || d < 1) return fail(PLP_EINVAL, "bad sizes");
-    if (B == 0) return PLP_OK;
-    if (!lb || !ub || !status || ((!A || !b) && m_max > 0)) return fail(PLP_EINVAL, "NULL pointer");
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t nA = (size_t)B * m_max * d, nb = (size_t)B * m_max, nx = (size_t)B * d;
-    int rc = ensure_arena(ctx, pad(nA * 8) + pad(nb * 8) + pad(nx * 8) * 2 + pad(B * 4) * 2 + 4096);
-    if (rc) return rc;
-    Arena a(ctx);
-    double* dA = a.take<double>(nA ? nA : 1);
-    double* db = a.take<double>(nb ? nb : 1);
-    int32_t* dm = a.take<int32_t>(B);
-    double* dlb = a.take<double>(nx);
-    double* dub = a.take<double>(nx);
-    int32_t* dst = a.take<int32_t>(B);
-    hipStream_t st = ctx->stream;
-    bool staged = false;  // large batches: chunked upload, kernels of earlier chunks running meanwhile (plp_stage.hpp)
-    const size_t md = (size_t)m_max * d;
-    rc = staged_run(ctx, st, B, 64, {{A, dA, md * 8, true}, {b, db, (size_t)m_max * 8, true}, {m, dm, 4}},
-                    reinterpret_cast<char*>(dA), (size_t)(reinterpret_cast<char*>(dm + B) - reinterpret_cast<char*>(dA)),
-                    [&](int64_t lo, int64_t hi, void* const* q) {
-                        return plp_bbox_batch_dev(ctx, st, hi - lo, m_max, d, static_cast<double*>(q[0]),
-                                                  static_cast<double*>(q[1]), static_cast<int32_t*>(q[2]),
-                                                  dlb + (size_t)lo * d, dub + (size_t)lo * d, dst + lo);
-                    },
-                    &staged);
-    if (rc) return rc;
-    if (!staged) {
-        rc = finite_or_fail(ctx, {{A, nA}, {b, nb}});
-        if (rc) return rc;
-        rc = copy_in(ctx, st, {{dA, A, nullptr, nA * 8}, {db, b, nullptr, nb * 8}, {dm, m, nullptr, m ? (size_t)B * 4 : 0}});
-        if (rc) return rc;
-        rc = plp_bbox_batch_dev(ctx, st, B, m_max, d, dA, db, m ? dm : nullptr, dlb, dub, dst);
-        if (rc) return rc;
-    }
-    return copy_out(ctx, st, {{dlb, nullptr, lb, nx * 8}, {dub, nullptr, ub, nx * 8}, {dst, nullptr, status, (size_t)B * 4}});
+    int rc = check_bbox(ctx, B, m_max, d, A, b, lb, ub, status);
+    if (rc || B == 0) return rc;
+    double *dA, *db, *dlb, *dub;
+    int32_t *dm, *dst;
+    HostCall hc(ctx);
+    declare_Abm(hc, B, m_max, d, dA, A, db, b, dm, m);
+    hc.out(dlb, lb, (size_t)B * d);
+    hc.out(dub, ub, (size_t)B * d);
+    hc.out(dst, status, B);
+    return run_Abm(hc, B, 64, [&](int64_t lo, int64_t hi) {
+        return plp_bbox_batch_dev(ctx, hc.st, hi - lo, m_max, d, dA, db, dm, dlb + (size_t)lo * d, dub + (size_t)lo * d,
+                                  dst + lo);
+    });
 }
 
 // ------------------------------------------------------------------------------- reduce
+static int check_reduce(plp_ctx* ctx, int64_t B, int m_max, int d, const double* A, const double* b, const uint64_t* keep,
+                        const int32_t* flags, const double* r, const double* xc, const int32_t* nlp) {
+    int rc = check_Abm(ctx, B, m_max, d, A, b, keep && flags && r && xc && nlp);
+    if (rc || B == 0) return rc;
+    if (m_max > plp::MAX_M || d > plp::MAX_D)
+        return fail(PLP_EUNSUPPORTED, "m_max=%d d=%d outside envelope (m<=64, d<=16)", m_max, d);
+    return PLP_OK;
+}
+
 int plp_reduce_batch_dev(plp_ctx* ctx, void* stream, int64_t B, int m_max, int d, const double* A,
                          const double* b, const int32_t* m, double abs_tol, uint64_t* keep, int32_t* flags,
                          double* r, double* xc, int32_t* nlp) {
-    if (!ctx) return fail(PLP_EINVAL, "ctx is NULL");
-    if (B < 0 || m_max < 0 || d < 1) return fail(PLP_EINVAL, "bad sizes");
-    if (B == 0) return PLP_OK;
-    if (!keep || !flags || !r || !xc || !nlp || ((!A || !b) && m_max > 0)) return fail(PLP_EINVAL, "NULL pointer");
-    if (m_max > plp::MAX_M || d > plp::MAX_D)
-        return fail(PLP_EUNSUPPORTED, "m_max=%d d=%d outside envelope (m<=64, d<=16)", m_max, d);
+    int rc = check_reduce(ctx, B, m_max, d, A, b, keep, flags, r, xc, nlp);
+    if (rc || B == 0) return rc;
     hipStream_t st = (hipStream_t)stream;  // NULL = the HIP default stream
     if (!ctx->retry_ring) {
         if (hipMalloc(reinterpret_cast<void**>(&ctx->retry_ring), 64 * 8) == hipSuccess) {
@@ -803,61 +386,46 @@ int plp_reduce_counters(plp_ctx* ctx, void* stream, uint64_t* simplex_runs, int 
 int plp_reduce_batch(plp_ctx* ctx, int64_t B, int m_max, int d, const double* A, const double* b,
                      const int32_t* m, double abs_tol, uint64_t* keep, int32_t* flags, double* r, double* xc,
                      int32_t* nlp) {
-    if (!ctx) return fail(PLP_EINVAL, "ctx is NULL");
-    if (B < 0 || m_max < 0 || d < 1) return fail(PLP_EINVAL, "bad sizes");
-    if (B == 0) return PLP_OK;
-    if (!keep || !flags || !r || !xc || !nlp || ((!A || !b) && m_max > 0)) return fail(PLP_EINVAL, "NULL pointer");
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t nA = (size_t)B * m_max * d, nb = (size_t)B * m_max, nx = (size_t)B * d;
-    int rc = ensure_arena(ctx, pad(nA * 8) + pad(nb * 8) + pad(nx * 8) + pad(B * 8) * 2 + pad(B * 4) * 3 + 4096);
+    int rc = check_reduce(ctx, B, m_max, d, A, b, keep, flags, r, xc, nlp);
+    if (rc || B == 0) return rc;
+    double *dA, *db, *dr, *dxc;
+    int32_t *dm, *dfl, *dnlp;
+    uint64_t* dkeep;
+    HostCall hc(ctx);
+    declare_Abm(hc, B, m_max, d, dA, A, db, b, dm, m);
+    declare_reduce_outs(hc, B, d, 1, dkeep, keep, dfl, flags, dr, r, dxc, xc, dnlp, nlp);
+    rc = hc.reserve();
     if (rc) return rc;
-    Arena a(ctx);
-    double* dA = a.take<double>(nA ? nA : 1);
-    double* db = a.take<double>(nb ? nb : 1);
-    int32_t* dm = a.take<int32_t>(B);
-    uint64_t* dkeep = a.take<uint64_t>(B);
-    int32_t* dfl = a.take<int32_t>(B);
-    double* dr = a.take<double>(B);
-    double* dxc = a.take<double>(nx);
-    int32_t* dnlp = a.take<int32_t>(B);
-    hipStream_t st = ctx->stream;
+    hipStream_t st = hc.st;
     // large batches: chunked upload with the kernels of earlier chunks running meanwhile (tiles hold 16 polytopes)
     bool staged = false;
-    const size_t md = (size_t)m_max * d;
-    rc = staged_run(ctx, st, B, 16,
-                    {{A, dA, md * 8, true}, {b, db, (size_t)m_max * 8, true}, {m, dm, 4}},
-                    reinterpret_cast<char*>(dA), (size_t)(reinterpret_cast<char*>(dm + B) - reinterpret_cast<char*>(dA)),
-                    [&](int64_t lo, int64_t hi, void* const* q) {
-                        return plp_reduce_batch_dev(ctx, st, hi - lo, m_max, d, static_cast<double*>(q[0]),
-                                                    static_cast<double*>(q[1]), static_cast<int32_t*>(q[2]), abs_tol,
-                                                    dkeep + lo, dfl + lo, dr + lo, dxc + (size_t)lo * d, dnlp + lo);
-                    },
-                    &staged);
+    rc = hc.upload_staged(B, 16,
+                          [&](int64_t lo, int64_t hi) {
+                              return plp_reduce_batch_dev(ctx, st, hi - lo, m_max, d, dA, db, dm, abs_tol, dkeep + lo, dfl + lo,
+                                                          dr + lo, dxc + (size_t)lo * d, dnlp + lo);
+                          },
+                          &staged);
     if (rc) return rc;
     bool two_step = false;
     // (the two-step path counts no simplex runs and uses no retry word: null counter and word)
-    const plp::ReduceArgs args{B, m_max, dA, db, m ? dm : nullptr, abs_tol, reinterpret_cast<unsigned long long*>(dkeep), dfl, dr,
+    const plp::ReduceArgs args{B, m_max, dA, db, dm, abs_tol, reinterpret_cast<unsigned long long*>(dkeep), dfl, dr,
                                dxc, dnlp, nullptr, nullptr, 0ull};
     if (!staged) {
-        rc = finite_or_fail(ctx, {{A, nA}, {b, nb}});
-        if (rc) return rc;
-        rc = copy_in(ctx, st, {{dA, A, nullptr, nA * 8}, {db, b, nullptr, nb * 8}, {dm, m, nullptr, m ? (size_t)B * 4 : 0}});
+        rc = hc.upload();
         if (rc) return rc;
         // small batches: only the first launch now; the pass that redoes polytopes flagged for the general engine runs
         // when the flags, host-visible below anyway, ask for it (it is a launch that normally finds nothing to do)
-        two_step = B <= 16384 && m_max <= plp::MAX_M && d <= plp::MAX_D;
+        two_step = B <= 16384;
         if (two_step) {
             if (plp::launch_reduce(d, args, 1, st))
                 return fail(PLP_EUNSUPPORTED, "reduce kernel: unsupported size");
             rc = check_launch("reduce_kernel");
         } else {
-            rc = plp_reduce_batch_dev(ctx, st, B, m_max, d, dA, db, m ? dm : nullptr, abs_tol, dkeep, dfl, dr, dxc, dnlp);
+            rc = plp_reduce_batch_dev(ctx, st, B, m_max, d, dA, db, dm, abs_tol, dkeep, dfl, dr, dxc, dnlp);
         }
         if (rc) return rc;
     }
-    rc = copy_out(ctx, st, {{dkeep, nullptr, keep, (size_t)B * 8}, {dfl, nullptr, flags, (size_t)B * 4},
-                            {dr, nullptr, r, (size_t)B * 8}, {dxc, nullptr, xc, nx * 8},
-                            {dnlp, nullptr, nlp, (size_t)B * 4}});
+    rc = hc.download();
     if (rc || !two_step) return rc;
     bool again = false;
     for (int64_t k = 0; k < B && !again; ++k) again = (flags[k] & plp::RF_RETRY) != 0;
@@ -866,25 +434,30 @@ int plp_reduce_batch(plp_ctx* ctx, int64_t B, int m_max, int d, const double* A,
         return fail(PLP_EUNSUPPORTED, "reduce kernel: unsupported size");
     rc = check_launch("reduce_kernel");
     if (rc) return rc;
-    return copy_out(ctx, st, {{dkeep, nullptr, keep, (size_t)B * 8}, {dfl, nullptr, flags, (size_t)B * 4},
-                              {dr, nullptr, r, (size_t)B * 8}, {dxc, nullptr, xc, nx * 8},
-                              {dnlp, nullptr, nlp, (size_t)B * 4}});
+    return hc.download();
 }
 
 // ------------------------------------------------------------------------------- reduce beyond 64 rows
-int plp_reduce_wide_batch_dev(plp_ctx* ctx, void* stream, int64_t B, int m_max, int d, const double* A,
-                              const double* b, const int32_t* m, double abs_tol, uint64_t* keep, int32_t* flags,
-                              double* r, double* xc, int32_t* nlp) {
+static int check_reduce_wide(plp_ctx* ctx, int64_t B, int m_max, int d, const double* A, const double* b,
+                             const uint64_t* keep, const int32_t* flags, const double* r, const double* xc,
+                             const int32_t* nlp) {
     if (!ctx) return fail(PLP_EINVAL, "ctx is NULL");
     if (B < 0 || m_max < 1 || d < 1) return fail(PLP_EINVAL, "bad sizes");
     if (B == 0) return PLP_OK;
     if (!keep || !flags || !r || !xc || !nlp || !A || !b) return fail(PLP_EINVAL, "NULL pointer");
     if (d > plp::MAX_D) return fail(PLP_EUNSUPPORTED, "d=%d > 16", d);
-    hipStream_t st = (hipStream_t)stream;  // NULL = the HIP default stream
+    return PLP_OK;
+}
+
+int plp_reduce_wide_batch_dev(plp_ctx* ctx, void* stream, int64_t B, int m_max, int d, const double* A,
+                              const double* b, const int32_t* m, double abs_tol, uint64_t* keep, int32_t* flags,
+                              double* r, double* xc, int32_t* nlp) {
+    int rc = check_reduce_wide(ctx, B, m_max, d, A, b, keep, flags, r, xc, nlp);
+    if (rc || B == 0) return rc;
     if (m_max <= plp::MAX_M)  // one word per polytope: the register-resident kernels
         return plp_reduce_batch_dev(ctx, stream, B, m_max, d, A, b, m, abs_tol, keep, flags, r, xc, nlp);
     if (plp::launch_reduce_lds(B, m_max, d, A, b, m, abs_tol, reinterpret_cast<unsigned long long*>(keep), flags, r, xc,
-                               nlp, st))
+                               nlp, (hipStream_t)stream))  // NULL = the HIP default stream
         return fail(PLP_EUNSUPPORTED, "reduce: a polytope of %d rows in dimension %d does not fit the LDS of a CU", m_max, d);
     return check_launch("reduce_lds_kernel");
 }
@@ -892,45 +465,42 @@ int plp_reduce_wide_batch_dev(plp_ctx* ctx, void* stream, int64_t B, int m_max, 
 int plp_reduce_wide_batch(plp_ctx* ctx, int64_t B, int m_max, int d, const double* A, const double* b,
                           const int32_t* m, double abs_tol, uint64_t* keep, int32_t* flags, double* r, double* xc,
                           int32_t* nlp) {
-    if (!ctx) return fail(PLP_EINVAL, "ctx is NULL");
-    if (B < 0 || m_max < 1 || d < 1) return fail(PLP_EINVAL, "bad sizes");
-    if (B == 0) return PLP_OK;
-    if (!keep || !flags || !r || !xc || !nlp || !A || !b) return fail(PLP_EINVAL, "NULL pointer");
+    int rc = check_reduce_wide(ctx, B, m_max, d, A, b, keep, flags, r, xc, nlp);
+    if (rc || B == 0) return rc;
     if (m_max <= plp::MAX_M) return plp_reduce_batch(ctx, B, m_max, d, A, b, m, abs_tol, keep, flags, r, xc, nlp);
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t W = (size_t)(m_max + 63) / 64;
-    const size_t nA = (size_t)B * m_max * d, nb = (size_t)B * m_max, nx = (size_t)B * d;
-    int rc = ensure_arena(ctx, pad(nA * 8) + pad(nb * 8) + pad(nx * 8) + pad(B * W * 8) + pad(B * 8) + pad(B * 4) * 3 + 4096);
+    double *dA, *db, *dr, *dxc;
+    int32_t *dm, *dfl, *dnlp;
+    uint64_t* dkeep;
+    HostCall hc(ctx);
+    const size_t md = (size_t)m_max * d;
+    hc.in(dA, A, (size_t)B * md, 0, true);  // (not staged: the LDS kernel's batches are small)
+    hc.in(db, b, (size_t)B * m_max, 0, true);
+    hc.in(dm, m, B);
+    declare_reduce_outs(hc, B, d, (size_t)(m_max + 63) / 64, dkeep, keep, dfl, flags, dr, r, dxc, xc, dnlp, nlp);
+    rc = hc.reserve();
     if (rc) return rc;
-    rc = finite_or_fail(ctx, {{A, nA}, {b, nb}});
+    rc = hc.upload();
     if (rc) return rc;
-    Arena a(ctx);
-    double* dA = a.take<double>(nA);
-    double* db = a.take<double>(nb);
-    int32_t* dm = a.take<int32_t>(B);
-    uint64_t* dkeep = a.take<uint64_t>(B * W);
-    int32_t* dfl = a.take<int32_t>(B);
-    double* dr = a.take<double>(B);
-    double* dxc = a.take<double>(nx);
-    int32_t* dnlp = a.take<int32_t>(B);
-    hipStream_t st = ctx->stream;
-    rc = copy_in(ctx, st, {{dA, A, nullptr, nA * 8}, {db, b, nullptr, nb * 8}, {dm, m, nullptr, m ? (size_t)B * 4 : 0}});
+    rc = plp_reduce_wide_batch_dev(ctx, hc.st, B, m_max, d, dA, db, dm, abs_tol, dkeep, dfl, dr, dxc, dnlp);
     if (rc) return rc;
-    rc = plp_reduce_wide_batch_dev(ctx, st, B, m_max, d, dA, db, m ? dm : nullptr, abs_tol, dkeep, dfl, dr, dxc, dnlp);
-    if (rc) return rc;
-    return copy_out(ctx, st, {{dkeep, nullptr, keep, (size_t)B * W * 8}, {dfl, nullptr, flags, (size_t)B * 4},
-                              {dr, nullptr, r, (size_t)B * 8}, {dxc, nullptr, xc, nx * 8},
-                              {dnlp, nullptr, nlp, (size_t)B * 4}});
+    return hc.download();
 }
 
 // ------------------------------------------------------------------------------- contains
-int plp_contains_dev(plp_ctx* ctx, void* stream, int P, int m_max, int d, const double* A, const double* b,
-                     const int32_t* m, int64_t N, const double* X, double abs_tol, int mode, uint8_t* out) {
+static int check_contains(plp_ctx* ctx, int P, int m_max, int d, const double* A, const double* b, int64_t N,
+                          const double* X, int mode, const uint8_t* out) {
     if (!ctx) return fail(PLP_EINVAL, "ctx is NULL");
     if (P < 0 || m_max < 0 || d < 1 || N < 0 || (mode != 0 && mode != 1)) return fail(PLP_EINVAL, "bad sizes/mode");
     if (N == 0) return PLP_OK;
     if (!X || !out || ((!A || !b) && P > 0 && m_max > 0)) return fail(PLP_EINVAL, "NULL pointer");
     if (d > plp::MAX_D) return fail(PLP_EUNSUPPORTED, "d=%d > 16", d);
+    return PLP_OK;
+}
+
+int plp_contains_dev(plp_ctx* ctx, void* stream, int P, int m_max, int d, const double* A, const double* b,
+                     const int32_t* m, int64_t N, const double* X, double abs_tol, int mode, uint8_t* out) {
+    int rc = check_contains(ctx, P, m_max, d, A, b, N, X, mode, out);
+    if (rc || N == 0) return rc;
     hipStream_t st = (hipStream_t)stream;  // NULL = the HIP default stream
     // per-row thresholds: a grow-only buffer of the context, handed from stream to stream in order
     void* scratch = nullptr;
@@ -963,7 +533,7 @@ int plp_contains_dev(plp_ctx* ctx, void* stream, int P, int m_max, int d, const 
     }
     if (plp::launch_contains(P, m_max, d, A, b, m, N, X, abs_tol, mode, out, scratch, st))
         return fail(PLP_EUNSUPPORTED, "contains kernel: unsupported size");
-    int rc = check_launch("contains_kernel");
+    rc = check_launch("contains_kernel");
     if (scratch && rc == PLP_OK) {
         ctx->mf_used = true;
         if (ctx->mf_ev) HIP_TRY(hipEventRecord(ctx->mf_ev, st));
@@ -973,100 +543,76 @@ int plp_contains_dev(plp_ctx* ctx, void* stream, int P, int m_max, int d, const 
 
 int plp_contains(plp_ctx* ctx, int P, int m_max, int d, const double* A, const double* b, const int32_t* m,
                  int64_t N, const double* X, double abs_tol, int mode, uint8_t* out) {
-    if (!ctx) return fail(PLP_EINVAL, "ctx is NULL");
-    if (P < 0 || m_max < 0 || d < 1 || N < 0 || (mode != 0 && mode != 1)) return fail(PLP_EINVAL, "bad sizes/mode");
-    if (N == 0) return PLP_OK;
-    if (!X || !out || ((!A || !b) && P > 0 && m_max > 0)) return fail(PLP_EINVAL, "NULL pointer");
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t nA = (size_t)P * m_max * d, nb = (size_t)P * m_max, nX = (size_t)N * d;
-    const size_t nout = mode == 1 ? (size_t)P * N : (size_t)N;
-    int rc = ensure_arena(ctx, pad(nA * 8) + pad(nb * 8) + pad(nX * 8) + pad(nout) + pad((size_t)P * 4) + 4096);
+    int rc = check_contains(ctx, P, m_max, d, A, b, N, X, mode, out);
+    if (rc || N == 0) return rc;
+    double *dA, *db, *dX;
+    int32_t* dm;
+    uint8_t* dout;
+    HostCall hc(ctx);
+    hc.in(dA, A, (size_t)P * m_max * d);
+    hc.in(db, b, (size_t)P * m_max);
+    hc.in(dm, m, P);
+    hc.in(dX, X, (size_t)N * d);
+    hc.out(dout, out, mode == 1 ? (size_t)P * N : (size_t)N);
+    hc.direct_out = true;
+    rc = hc.reserve();
     if (rc) return rc;
-    Arena a(ctx);
-    double* dA = a.take<double>(nA ? nA : 1);
-    double* db = a.take<double>(nb ? nb : 1);
-    int32_t* dm = a.take<int32_t>(P ? P : 1);
-    double* dX = a.take<double>(nX);
-    uint8_t* dout = a.take<uint8_t>(nout ? nout : 1);
-    hipStream_t st = ctx->stream;
-    if (nA) HIP_TRY(hipMemcpyAsync(dA, A, nA * 8, hipMemcpyHostToDevice, st));
-    if (nb) HIP_TRY(hipMemcpyAsync(db, b, nb * 8, hipMemcpyHostToDevice, st));
-    if (m && P) HIP_TRY(hipMemcpyAsync(dm, m, (size_t)P * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(dX, X, nX * 8, hipMemcpyHostToDevice, st));
-    rc = plp_contains_dev(ctx, st, P, m_max, d, dA, db, m ? dm : nullptr, N, dX, abs_tol, mode, dout);
+    rc = hc.upload();
     if (rc) return rc;
-    if (nout) HIP_TRY(hipMemcpyAsync(out, dout, nout, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return PLP_OK;
+    rc = plp_contains_dev(ctx, hc.st, P, m_max, d, dA, db, dm, N, dX, abs_tol, mode, dout);
+    if (rc) return rc;
+    return hc.download();
 }
 
 // ------------------------------------------------------------------------------- assign
-int plp_assign_dev(plp_ctx* ctx, void* stream, int64_t N, int d, const double* X, int F, const double* normals,
-                   const double* offsets, double abs_tol, int32_t* fop, double* dist, int64_t* argmax,
-                   double* maxd) {
+static int check_assign(plp_ctx* ctx, int64_t N, int d, const double* X, int F, const double* normals,
+                        const double* offsets, double abs_tol, const int32_t* fop, const double* dist,
+                        const int64_t* argmax, const double* maxd) {
     if (!ctx) return fail(PLP_EINVAL, "ctx is NULL");
     if (N < 0 || d < 1 || F < 1 || !(abs_tol >= 0.0)) return fail(PLP_EINVAL, "bad sizes (need F>=1, abs_tol>=0)");
     if (!normals || !offsets || !argmax || !maxd || (N > 0 && (!X || !fop || !dist)))
         return fail(PLP_EINVAL, "NULL pointer");
     if (d > plp::MAX_D) return fail(PLP_EUNSUPPORTED, "d=%d > 16", d);
-    hipStream_t st = (hipStream_t)stream;  // NULL = the HIP default stream
-    void* scratch = nullptr;
+    return PLP_OK;
+}
+
+int plp_assign_dev(plp_ctx* ctx, void* stream, int64_t N, int d, const double* X, int F, const double* normals,
+                   const double* offsets, double abs_tol, int32_t* fop, double* dist, int64_t* argmax,
+                   double* maxd) {
+    int rc = check_assign(ctx, N, d, X, F, normals, offsets, abs_tol, fop, dist, argmax, maxd);
+    if (rc) return rc;
+    // few facets: the workgroups' partials (plp_ctx::as_scratch); without the buffer the general kernel takes the call
     const size_t need = plp::assign_scratch_bytes(N, F);
-    if (need) {
-        if (ctx->as_scratch.size() >= 16 && !ctx->as_scratch.count(stream)) {
-            (void)hipDeviceSynchronize();
-            for (auto& kv : ctx->as_scratch) if (kv.second.p) (void)hipFree(kv.second.p);
-            ctx->as_scratch.clear();
-        }
-        plp_ctx::StreamBuf& sb = ctx->as_scratch[stream];
-        if (need > sb.bytes) {
-            if (sb.p) { (void)hipStreamSynchronize(st); (void)hipFree(sb.p); }   // (its last user ran on this stream)
-            sb.p = nullptr;
-            sb.bytes = 0;
-            if (hipMalloc(&sb.p, need + need / 2) == hipSuccess) sb.bytes = need + need / 2;
-            else (void)hipGetLastError();   // no scratch: the general kernel takes the call
-        }
-        scratch = sb.p;
-    }
+    void* scratch = need ? stream_buf(ctx->as_scratch, stream, need) : nullptr;
     if (plp::launch_assign(N, d, X, F, normals, offsets, abs_tol, fop, dist, reinterpret_cast<long long*>(argmax),
-                           maxd, scratch, scratch ? ctx->as_scratch[stream].bytes : 0, st))
+                           maxd, scratch, scratch ? ctx->as_scratch[stream].bytes : 0, (hipStream_t)stream))
         return fail(PLP_EUNSUPPORTED, "assign kernel: unsupported size");
     return check_launch("assign_kernel");
 }
 
 int plp_assign(plp_ctx* ctx, int64_t N, int d, const double* X, int F, const double* normals,
                const double* offsets, double abs_tol, int32_t* fop, double* dist, int64_t* argmax, double* maxd) {
-    if (!ctx) return fail(PLP_EINVAL, "ctx is NULL");
-    if (N < 0 || d < 1 || F < 1 || !(abs_tol >= 0.0)) return fail(PLP_EINVAL, "bad sizes (need F>=1, abs_tol>=0)");
-    if (!normals || !offsets || !argmax || !maxd || (N > 0 && (!X || !fop || !dist)))
-        return fail(PLP_EINVAL, "NULL pointer");
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t nX = (size_t)N * d, nF = (size_t)F * d;
-    int rc = ensure_arena(ctx, pad(nX * 8) + pad(nF * 8) + pad((size_t)F * 8) * 3 + pad((size_t)N * 4) +
-                                   pad((size_t)N * 8) + 4096);
+    int rc = check_assign(ctx, N, d, X, F, normals, offsets, abs_tol, fop, dist, argmax, maxd);
     if (rc) return rc;
-    Arena a(ctx);
-    double* dX = a.take<double>(nX ? nX : 1);
-    double* dn = a.take<double>(nF);
-    double* dof = a.take<double>(F);
-    int32_t* dfop = a.take<int32_t>(N ? N : 1);
-    double* ddist = a.take<double>(N ? N : 1);
-    int64_t* dam = a.take<int64_t>(F);
-    double* dmx = a.take<double>(F);
-    hipStream_t st = ctx->stream;
-    if (nX) HIP_TRY(hipMemcpyAsync(dX, X, nX * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(dn, normals, nF * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(dof, offsets, (size_t)F * 8, hipMemcpyHostToDevice, st));
-    rc = plp_assign_dev(ctx, st, N, d, dX, F, dn, dof, abs_tol, dfop, ddist, dam, dmx);
+    double *dX, *dn, *dof, *ddist, *dmx;
+    int32_t* dfop;
+    int64_t* dam;
+    HostCall hc(ctx);
+    hc.in(dX, X, (size_t)N * d);
+    hc.in(dn, normals, (size_t)F * d);
+    hc.in(dof, offsets, F);
+    hc.out(dfop, fop, N);
+    hc.out(ddist, dist, N);
+    hc.out(dam, argmax, F);
+    hc.out(dmx, maxd, F);
+    hc.direct_out = true;
+    rc = hc.reserve();
     if (rc) return rc;
-    if (N) {
-        HIP_TRY(hipMemcpyAsync(fop, dfop, (size_t)N * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(dist, ddist, (size_t)N * 8, hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(hipMemcpyAsync(argmax, dam, (size_t)F * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(maxd, dmx, (size_t)F * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return PLP_OK;
+    rc = hc.upload();
+    if (rc) return rc;
+    rc = plp_assign_dev(ctx, hc.st, N, d, dX, F, dn, dof, abs_tol, dfop, ddist, dam, dmx);
+    if (rc) return rc;
+    return hc.download();
 }
 
 // ------------------------------------------------------------------------------- hull session
@@ -1137,37 +683,30 @@ int fm_host(plp_ctx* ctx, int64_t B, int m_max, int d, const double* A, const do
     int rc = fm_check(ctx, B, m_max, d, A, b, keep, kw, col);
     if (rc) return rc;
     if (B == 0) return PLP_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
     const int dout = col >= 0 ? d - 1 : d;
-    const size_t nA = (size_t)B * m_max * d, nb = (size_t)B * m_max, nk = keep ? (size_t)B * kw : 0;
     const size_t mo = mo_max > 0 ? (size_t)mo_max : 0;
-    rc = ensure_arena(ctx, pad(nA * 8) + pad(nb * 8) + pad(nk * 8) + pad((size_t)B * 4) * 3 + pad((size_t)B * mo * dout * 8) +
-                               pad((size_t)B * mo * 8) + 4096);
-    if (rc) return rc;
-    Arena a(ctx);
-    double* dA = a.take<double>(nA);
-    double* db = a.take<double>(nb);
-    int32_t* dm = a.take<int32_t>(B);
-    uint64_t* dk = a.take<uint64_t>(nk);
-    int32_t* dfl = a.take<int32_t>(B);
-    int32_t* dout_n = a.take<int32_t>(B);
-    double* dAo = a.take<double>((size_t)B * mo * dout);
-    double* dbo = a.take<double>((size_t)B * mo);
-    hipStream_t st = ctx->stream;
-    rc = copy_in(ctx, st, {{dA, A, nullptr, nA * 8}, {db, b, nullptr, nb * 8}, {dm, m, nullptr, m ? (size_t)B * 4 : 0},
-                           {dk, keep, nullptr, nk * 8}, {dfl, flags, nullptr, flags ? (size_t)B * 4 : 0}});
-    if (rc) return rc;
-    if (count) {
-        rc = plp_fm_count_dev(ctx, st, B, m_max, d, dA, db, m ? dm : nullptr, keep ? dk : nullptr, kw,
-                              flags ? dfl : nullptr, col, first, abs_tol, dout_n);
-        if (rc) return rc;
-        return copy_out(ctx, st, {{dout_n, nullptr, count, (size_t)B * 4}});
+    double *dA, *db, *dAo = nullptr, *dbo = nullptr;
+    int32_t *dm, *dfl, *dout_n;
+    uint64_t* dk;
+    HostCall hc(ctx);
+    hc.in(dA, A, (size_t)B * m_max * d);
+    hc.in(db, b, (size_t)B * m_max);
+    hc.in(dm, m, B);
+    hc.in(dk, keep, keep ? (size_t)B * kw : 0);
+    hc.in(dfl, flags, B);
+    hc.out(dout_n, count ? count : m_out, B);
+    if (!count) {
+        hc.out(dAo, A_out, (size_t)B * mo * dout);
+        hc.out(dbo, b_out, (size_t)B * mo);
     }
-    rc = plp_fm_emit_dev(ctx, st, B, m_max, d, dA, db, m ? dm : nullptr, keep ? dk : nullptr, kw, flags ? dfl : nullptr,
-                         col, first, abs_tol, mo_max, dAo, dbo, dout_n);
+    rc = hc.reserve();
     if (rc) return rc;
-    return copy_out(ctx, st, {{dAo, nullptr, A_out, (size_t)B * mo * dout * 8}, {dbo, nullptr, b_out, (size_t)B * mo * 8},
-                              {dout_n, nullptr, m_out, (size_t)B * 4}});
+    rc = hc.upload();
+    if (rc) return rc;
+    if (count) rc = plp_fm_count_dev(ctx, hc.st, B, m_max, d, dA, db, dm, dk, kw, dfl, col, first, abs_tol, dout_n);
+    else rc = plp_fm_emit_dev(ctx, hc.st, B, m_max, d, dA, db, dm, dk, kw, dfl, col, first, abs_tol, mo_max, dAo, dbo, dout_n);
+    if (rc) return rc;
+    return hc.download();
 }
 }  // namespace
 
@@ -1219,29 +758,29 @@ int plp_volume_hits(plp_ctx* ctx, int64_t B, int m_max, int d, const double* A, 
     int rc = volume_check(ctx, B, m_max, d, A, b, lb, ub, state, inc, N, hits, flags);
     if (rc) return rc;
     if (B == 0) return PLP_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t nA = (size_t)B * m_max * d, nb = (size_t)B * m_max, nd = (size_t)B * d;
-    rc = ensure_arena(ctx, pad(nA * 8) + pad(nb * 8) + pad(nd * 8) * 2 + pad((size_t)B * 16) * 2 + pad((size_t)B * 4) * 3 + 4096);
-    if (rc) return rc;
-    Arena a(ctx);
-    double* dA = a.take<double>(nA ? nA : 1);
-    double* db = a.take<double>(nb ? nb : 1);
-    int32_t* dm = a.take<int32_t>(B);
-    double* dlb = a.take<double>(nd);
-    double* dub = a.take<double>(nd);
-    uint64_t* dst = a.take<uint64_t>((size_t)B * 2);
-    uint64_t* din = a.take<uint64_t>((size_t)B * 2);
-    uint32_t* dh = a.take<uint32_t>(B);
-    int32_t* dfl = a.take<int32_t>(B);
-    hipStream_t st = ctx->stream;
+    const size_t nd = (size_t)B * d;
+    double *dA, *db, *dlb, *dub;
+    int32_t *dm, *dfl;
+    uint64_t *dst, *din;
+    uint32_t* dh;
+    HostCall hc(ctx);
     // (a box may hold +-inf: those polytopes come back flagged, so the arrays are not checked for finiteness here)
-    rc = copy_in(ctx, st, {{dA, A, nullptr, nA * 8}, {db, b, nullptr, nb * 8}, {dm, m, nullptr, m ? (size_t)B * 4 : 0},
-                           {dlb, lb, nullptr, nd * 8}, {dub, ub, nullptr, nd * 8}, {dst, state, nullptr, (size_t)B * 16},
-                           {din, inc, nullptr, (size_t)B * 16}});
+    hc.in(dA, A, (size_t)B * m_max * d);
+    hc.in(db, b, (size_t)B * m_max);
+    hc.in(dm, m, B);
+    hc.in(dlb, lb, nd);
+    hc.in(dub, ub, nd);
+    hc.in(dst, state, (size_t)B * 2);
+    hc.in(din, inc, (size_t)B * 2);
+    hc.out(dh, hits, B);
+    hc.out(dfl, flags, B);
+    rc = hc.reserve();
     if (rc) return rc;
-    rc = plp_volume_hits_dev(ctx, st, B, m_max, d, dA, db, m ? dm : nullptr, dlb, dub, dst, din, N, dh, dfl);
+    rc = hc.upload();
     if (rc) return rc;
-    return copy_out(ctx, st, {{dh, nullptr, hits, (size_t)B * 4}, {dfl, nullptr, flags, (size_t)B * 4}});
+    rc = plp_volume_hits_dev(ctx, hc.st, B, m_max, d, dA, db, dm, dlb, dub, dst, din, N, dh, dfl);
+    if (rc) return rc;
+    return hc.download();
 }
 
 }  // extern "C"
@@ -1455,105 +994,31 @@ int plp_hull_read(plp_hull* h, int32_t* owner, double* dist) {
 extern "C" {
 
 // ------------------------------------------------------------------------------- adjacency
-int plp_adjacent_pairs_dev(plp_ctx* ctx, void* stream, int n, int m_max, int d, const double* A, const double* b,
-                           const int32_t* m, double abs_tol, uint8_t* adj) {
+// The four pair operations share their checks (`bad_counts` / `empty`: the operation's own conditions on its cell counts)
+static int check_pairs(plp_ctx* ctx, bool bad_counts, bool empty, int m_max, int d, const double* A, const double* b,
+                       const uint8_t* out) {
     if (!ctx) return fail(PLP_EINVAL, "ctx is NULL");
-    if (n < 0 || m_max < 1 || d < 1) return fail(PLP_EINVAL, "bad sizes");
-    if (n == 0) return PLP_OK;
-    if (!A || !b || !adj) return fail(PLP_EINVAL, "NULL pointer");
-    if (2 * m_max > plp::MAX_M || d > plp::MAX_D)
-        return fail(PLP_EUNSUPPORTED, "m_max=%d d=%d outside envelope (2*m_max<=64, d<=16)", m_max, d);
-    if (plp::launch_adjacent(n, m_max, d, A, b, m, abs_tol, abs_tol / 10, adj, 0, 0, nullptr, (hipStream_t)stream))
-        return fail(PLP_EUNSUPPORTED, "adjacent kernel: unsupported size");
-    return check_launch("adjacent_r_kernel");
-}
-
-int plp_overlap_pairs_dev(plp_ctx* ctx, void* stream, int n, int m_max, int d, const double* A, const double* b,
-                          const int32_t* m, double abs_tol, uint8_t* out) {
-    if (!ctx) return fail(PLP_EINVAL, "ctx is NULL");
-    if (n < 0 || m_max < 1 || d < 1) return fail(PLP_EINVAL, "bad sizes");
-    if (n == 0) return PLP_OK;
+    if (bad_counts || m_max < 1 || d < 1) return fail(PLP_EINVAL, "bad sizes");
+    if (empty) return PLP_OK;
     if (!A || !b || !out) return fail(PLP_EINVAL, "NULL pointer");
     if (2 * m_max > plp::MAX_M || d > plp::MAX_D)
         return fail(PLP_EUNSUPPORTED, "m_max=%d d=%d outside envelope (2*m_max<=64, d<=16)", m_max, d);
-    if (plp::launch_adjacent(n, m_max, d, A, b, m, 0.0, abs_tol, out, 0, 0, nullptr, (hipStream_t)stream))
-        return fail(PLP_EUNSUPPORTED, "adjacent kernel: unsupported size");
-    return check_launch("adjacent_r_kernel");
-}
-
-int plp_overlap_pairs(plp_ctx* ctx, int n, int m_max, int d, const double* A, const double* b, const int32_t* m,
-                      double abs_tol, uint8_t* out) {
-    if (!ctx) return fail(PLP_EINVAL, "ctx is NULL");
-    if (n < 0 || m_max < 1 || d < 1) return fail(PLP_EINVAL, "bad sizes");
-    if (n == 0) return PLP_OK;
-    if (!A || !b || !out) return fail(PLP_EINVAL, "NULL pointer");
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t nA = (size_t)n * m_max * d, nb = (size_t)n * m_max, nout = (size_t)n * n;
-    int rc = ensure_arena(ctx, pad(nA * 8) + pad(nb * 8) + pad((size_t)n * 4) + pad(nout) + 4096);
-    if (rc) return rc;
-    Arena a(ctx);
-    double* dA = a.take<double>(nA);
-    double* db = a.take<double>(nb);
-    int32_t* dm = a.take<int32_t>(n);
-    uint8_t* dout = a.take<uint8_t>(nout);
-    hipStream_t st = ctx->stream;
-    HIP_TRY(hipMemcpyAsync(dA, A, nA * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(db, b, nb * 8, hipMemcpyHostToDevice, st));
-    if (m) HIP_TRY(hipMemcpyAsync(dm, m, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    rc = plp_overlap_pairs_dev(ctx, st, n, m_max, d, dA, db, m ? dm : nullptr, abs_tol, dout);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out, dout, nout, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
     return PLP_OK;
 }
 
-int plp_overlap_cross_dev(plp_ctx* ctx, void* stream, int n1, int n2, int m_max, int d, const double* A, const double* b,
-                          const int32_t* m, double thresh, uint8_t* out) {
-    if (!ctx) return fail(PLP_EINVAL, "ctx is NULL");
-    if (n1 < 0 || n2 < 0 || m_max < 1 || d < 1) return fail(PLP_EINVAL, "bad sizes");
-    if (n1 == 0 || n2 == 0) return PLP_OK;
-    if (!A || !b || !out) return fail(PLP_EINVAL, "NULL pointer");
-    if (2 * m_max > plp::MAX_M || d > plp::MAX_D)
-        return fail(PLP_EUNSUPPORTED, "m_max=%d d=%d outside envelope (2*m_max<=64, d<=16)", m_max, d);
-    if ((long long)n1 + n2 > 2147483647ll) return fail(PLP_EUNSUPPORTED, "too many cells");
-    if (plp::launch_adjacent(n1 + n2, m_max, d, A, b, m, 0.0, thresh, nullptr, 0, (long long)n1 * n2, out,
-                             (hipStream_t)stream, n1))
-        return fail(PLP_EUNSUPPORTED, "adjacent kernel: unsupported size");
-    return check_launch("adjacent_r_kernel");
+static int check_cross(plp_ctx* ctx, int n1, int n2, int m_max, int d, const double* A, const double* b, const uint8_t* out) {
+    int rc = check_pairs(ctx, n1 < 0 || n2 < 0, n1 == 0 || n2 == 0, m_max, d, A, b, out);
+    if (rc == PLP_OK && (long long)n1 + n2 > 2147483647ll) return fail(PLP_EUNSUPPORTED, "too many cells");
+    return rc;
 }
 
-int plp_overlap_cross(plp_ctx* ctx, int n1, int n2, int m_max, int d, const double* A, const double* b, const int32_t* m,
-                      double thresh, uint8_t* out) {
-    if (!ctx) return fail(PLP_EINVAL, "ctx is NULL");
-    if (n1 < 0 || n2 < 0 || m_max < 1 || d < 1) return fail(PLP_EINVAL, "bad sizes");
-    if (n1 == 0 || n2 == 0) return PLP_OK;
-    if (!A || !b || !out) return fail(PLP_EINVAL, "NULL pointer");
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t n = (size_t)n1 + n2;
-    const size_t nA = n * m_max * d, nb = n * m_max, nout = (size_t)n1 * n2;
-    int rc = ensure_arena(ctx, pad(nA * 8) + pad(nb * 8) + pad(n * 4) + pad(nout) + 4096);
-    if (rc) return rc;
-    Arena a(ctx);
-    double* dA = a.take<double>(nA);
-    double* db = a.take<double>(nb);
-    int32_t* dm = a.take<int32_t>(n);
-    uint8_t* dout = a.take<uint8_t>(nout);
-    hipStream_t st = ctx->stream;
-    HIP_TRY(hipMemcpyAsync(dA, A, nA * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(db, b, nb * 8, hipMemcpyHostToDevice, st));
-    if (m) HIP_TRY(hipMemcpyAsync(dm, m, n * 4, hipMemcpyHostToDevice, st));
-    rc = plp_overlap_cross_dev(ctx, st, n1, n2, m_max, d, dA, db, m ? dm : nullptr, thresh, dout);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out, dout, nout, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return PLP_OK;
-}
-
-int plp_adjacent_pairs_range_dev(plp_ctx* ctx, void* stream, int n, int m_max, int d, const double* A,
-                                 const double* b, const int32_t* m, double abs_tol, int64_t pair_lo,
-                                 int64_t pair_hi, uint8_t* out) {
+// (`validate_empty`: the device-pointer call checks an empty range against the pair count like any other; the host-pointer
+// call accepts it wherever it lies, it reads nothing)
+static int check_pair_range(plp_ctx* ctx, int n, int m_max, int d, const double* A, const double* b, int64_t pair_lo,
+                            int64_t pair_hi, const uint8_t* out, bool validate_empty) {
     if (!ctx) return fail(PLP_EINVAL, "ctx is NULL");
     if (n < 0 || m_max < 1 || d < 1) return fail(PLP_EINVAL, "bad sizes");
+    if (pair_lo == pair_hi && !validate_empty) return PLP_OK;
     const int64_t npairs = (int64_t)n * (n - 1) / 2;
     if (pair_lo < 0 || pair_hi > npairs || pair_lo > pair_hi)
         return fail(PLP_EINVAL, "pair range [%lld, %lld) outside [0, %lld)", (long long)pair_lo, (long long)pair_hi,
@@ -1562,80 +1027,102 @@ int plp_adjacent_pairs_range_dev(plp_ctx* ctx, void* stream, int n, int m_max, i
     if (!A || !b || !out) return fail(PLP_EINVAL, "NULL pointer");
     if (2 * m_max > plp::MAX_M || d > plp::MAX_D)
         return fail(PLP_EUNSUPPORTED, "m_max=%d d=%d outside envelope (2*m_max<=64, d<=16)", m_max, d);
+    return PLP_OK;
+}
+
+int plp_adjacent_pairs_dev(plp_ctx* ctx, void* stream, int n, int m_max, int d, const double* A, const double* b,
+                           const int32_t* m, double abs_tol, uint8_t* adj) {
+    int rc = check_pairs(ctx, n < 0, n == 0, m_max, d, A, b, adj);
+    if (rc || n == 0) return rc;
+    if (plp::launch_adjacent(n, m_max, d, A, b, m, abs_tol, abs_tol / 10, adj, 0, 0, nullptr, (hipStream_t)stream))
+        return fail(PLP_EUNSUPPORTED, "adjacent kernel: unsupported size");
+    return check_launch("adjacent_r_kernel");
+}
+
+int plp_overlap_pairs_dev(plp_ctx* ctx, void* stream, int n, int m_max, int d, const double* A, const double* b,
+                          const int32_t* m, double abs_tol, uint8_t* out) {
+    int rc = check_pairs(ctx, n < 0, n == 0, m_max, d, A, b, out);
+    if (rc || n == 0) return rc;
+    if (plp::launch_adjacent(n, m_max, d, A, b, m, 0.0, abs_tol, out, 0, 0, nullptr, (hipStream_t)stream))
+        return fail(PLP_EUNSUPPORTED, "adjacent kernel: unsupported size");
+    return check_launch("adjacent_r_kernel");
+}
+
+int plp_overlap_cross_dev(plp_ctx* ctx, void* stream, int n1, int n2, int m_max, int d, const double* A, const double* b,
+                          const int32_t* m, double thresh, uint8_t* out) {
+    int rc = check_cross(ctx, n1, n2, m_max, d, A, b, out);
+    if (rc || n1 == 0 || n2 == 0) return rc;
+    if (plp::launch_adjacent(n1 + n2, m_max, d, A, b, m, 0.0, thresh, nullptr, 0, (long long)n1 * n2, out,
+                             (hipStream_t)stream, n1))
+        return fail(PLP_EUNSUPPORTED, "adjacent kernel: unsupported size");
+    return check_launch("adjacent_r_kernel");
+}
+
+int plp_adjacent_pairs_range_dev(plp_ctx* ctx, void* stream, int n, int m_max, int d, const double* A,
+                                 const double* b, const int32_t* m, double abs_tol, int64_t pair_lo,
+                                 int64_t pair_hi, uint8_t* out) {
+    int rc = check_pair_range(ctx, n, m_max, d, A, b, pair_lo, pair_hi, out, true);
+    if (rc || pair_lo == pair_hi) return rc;
     if (plp::launch_adjacent(n, m_max, d, A, b, m, abs_tol, abs_tol / 10, nullptr, pair_lo, pair_hi, out,
                              (hipStream_t)stream))
         return fail(PLP_EUNSUPPORTED, "adjacent kernel: unsupported size");
     return check_launch("adjacent_r_kernel");
 }
 
-int plp_adjacent_pairs_range(plp_ctx* ctx, int n, int m_max, int d, const double* A, const double* b,
-                             const int32_t* m, double abs_tol, int64_t pair_lo, int64_t pair_hi, uint8_t* out) {
-    if (!ctx) return fail(PLP_EINVAL, "ctx is NULL");
-    if (n < 0 || m_max < 1 || d < 1) return fail(PLP_EINVAL, "bad sizes");
-    if (pair_lo == pair_hi) return PLP_OK;
-    if (!A || !b || !out) return fail(PLP_EINVAL, "NULL pointer");
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t nA = (size_t)n * m_max * d, nb = (size_t)n * m_max;
-    const size_t nout = pair_hi > pair_lo ? (size_t)(pair_hi - pair_lo) : 0;
-    int rc = ensure_arena(ctx, pad(nA * 8) + pad(nb * 8) + pad((size_t)n * 4) + pad(nout) + 4096);
-    if (rc) return rc;
-    Arena a(ctx);
-    double* dA = a.take<double>(nA);
-    double* db = a.take<double>(nb);
-    int32_t* dm = a.take<int32_t>(n);
-    uint8_t* dout = a.take<uint8_t>(nout ? nout : 1);
-    hipStream_t st = ctx->stream;
-    HIP_TRY(hipMemcpyAsync(dA, A, nA * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(db, b, nb * 8, hipMemcpyHostToDevice, st));
-    if (m) HIP_TRY(hipMemcpyAsync(dm, m, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    rc = plp_adjacent_pairs_range_dev(ctx, st, n, m_max, d, dA, db, m ? dm : nullptr, abs_tol, pair_lo, pair_hi, dout);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out, dout, nout, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return PLP_OK;
-}
-
 int plp_adjacent_pairs(plp_ctx* ctx, int n, int m_max, int d, const double* A, const double* b, const int32_t* m,
                        double abs_tol, uint8_t* adj) {
-    if (!ctx) return fail(PLP_EINVAL, "ctx is NULL");
-    if (n < 0 || m_max < 1 || d < 1) return fail(PLP_EINVAL, "bad sizes");
-    if (n == 0) return PLP_OK;
-    if (!A || !b || !adj) return fail(PLP_EINVAL, "NULL pointer");
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t nA = (size_t)n * m_max * d, nb = (size_t)n * m_max, nadj = (size_t)n * n;
-    int rc = ensure_arena(ctx, pad(nA * 8) + pad(nb * 8) + pad((size_t)n * 4) + pad(nadj) + 4096);
-    if (rc) return rc;
-    Arena a(ctx);
-    double* dA = a.take<double>(nA);
-    double* db = a.take<double>(nb);
-    int32_t* dm = a.take<int32_t>(n);
-    uint8_t* dadj = a.take<uint8_t>(nadj);
-    hipStream_t st = ctx->stream;
-    HIP_TRY(hipMemcpyAsync(dA, A, nA * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(db, b, nb * 8, hipMemcpyHostToDevice, st));
-    if (m) HIP_TRY(hipMemcpyAsync(dm, m, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    rc = plp_adjacent_pairs_dev(ctx, st, n, m_max, d, dA, db, m ? dm : nullptr, abs_tol, dadj);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(adj, dadj, nadj, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return PLP_OK;
+    int rc = check_pairs(ctx, n < 0, n == 0, m_max, d, A, b, adj);
+    if (rc || n == 0) return rc;
+    return pairs_host(ctx, n, m_max, d, A, b, m, adj, (size_t)n * n,
+                      [&](hipStream_t st, const double* dA, const double* db, const int32_t* dm, uint8_t* dadj) {
+                          return plp_adjacent_pairs_dev(ctx, st, n, m_max, d, dA, db, dm, abs_tol, dadj);
+                      });
+}
+
+int plp_overlap_pairs(plp_ctx* ctx, int n, int m_max, int d, const double* A, const double* b, const int32_t* m,
+                      double abs_tol, uint8_t* out) {
+    int rc = check_pairs(ctx, n < 0, n == 0, m_max, d, A, b, out);
+    if (rc || n == 0) return rc;
+    return pairs_host(ctx, n, m_max, d, A, b, m, out, (size_t)n * n,
+                      [&](hipStream_t st, const double* dA, const double* db, const int32_t* dm, uint8_t* dout) {
+                          return plp_overlap_pairs_dev(ctx, st, n, m_max, d, dA, db, dm, abs_tol, dout);
+                      });
+}
+
+int plp_overlap_cross(plp_ctx* ctx, int n1, int n2, int m_max, int d, const double* A, const double* b, const int32_t* m,
+                      double thresh, uint8_t* out) {
+    int rc = check_cross(ctx, n1, n2, m_max, d, A, b, out);
+    if (rc || n1 == 0 || n2 == 0) return rc;
+    return pairs_host(ctx, (size_t)n1 + n2, m_max, d, A, b, m, out, (size_t)n1 * n2,
+                      [&](hipStream_t st, const double* dA, const double* db, const int32_t* dm, uint8_t* dout) {
+                          return plp_overlap_cross_dev(ctx, st, n1, n2, m_max, d, dA, db, dm, thresh, dout);
+                      });
+}
+
+int plp_adjacent_pairs_range(plp_ctx* ctx, int n, int m_max, int d, const double* A, const double* b,
+                             const int32_t* m, double abs_tol, int64_t pair_lo, int64_t pair_hi, uint8_t* out) {
+    int rc = check_pair_range(ctx, n, m_max, d, A, b, pair_lo, pair_hi, out, false);
+    if (rc || pair_lo == pair_hi) return rc;
+    return pairs_host(ctx, n, m_max, d, A, b, m, out, (size_t)(pair_hi - pair_lo),
+                      [&](hipStream_t st, const double* dA, const double* db, const int32_t* dm, uint8_t* dout) {
+                          return plp_adjacent_pairs_range_dev(ctx, st, n, m_max, d, dA, db, dm, abs_tol, pair_lo, pair_hi,
+                                                              dout);
+                      });
 }
 
 int plp_selftest(plp_ctx* ctx, int group_size, double* out_d, uint32_t* out_u) {
     if (!ctx || !out_d || !out_u) return fail(PLP_EINVAL, "NULL pointer");
-    HIP_TRY(hipSetDevice(ctx->device));
-    int rc = ensure_arena(ctx, 128 * 8 + 128 * 4 + 1024);
+    double* dd;
+    uint32_t* du;
+    HostCall hc(ctx);
+    hc.out(dd, out_d, 128);
+    hc.out(du, out_u, 128);
+    int rc = hc.reserve();
     if (rc) return rc;
-    Arena a(ctx);
-    double* dd = a.take<double>(128);
-    unsigned* du = a.take<unsigned>(128);
-    if (plp::launch_selftest(group_size, dd, du, ctx->stream)) return fail(PLP_EINVAL, "group size must be 8/16/32/64");
+    if (plp::launch_selftest(group_size, dd, du, hc.st)) return fail(PLP_EINVAL, "group size must be 8/16/32/64");
     rc = check_launch("selftest_kernel");
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out_d, dd, 128 * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(out_u, du, 128 * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return PLP_OK;
+    return hc.download();
 }
 
 // ------------------------------------------------------------------------------- region_diff search

@@ -153,4 +153,16 @@ void launch_hull_drop(long long n, const long long* idx, int* owner, hipStream_t
 
 int launch_selftest(int gs, double* out_d, unsigned* out_u, hipStream_t st);
 
+// the verifier behind the LP / Chebyshev / bounding-box batches (plp_verify.hip): `scratch` holds verify_scratch_bytes(nlp,
+// m_max) bytes, `parity` alternates between the launches of a stream (which of its two list counters this one uses)
+size_t verify_scratch_bytes(long long nlp, int m_max);
+bool verify_enabled();
+int launch_verify_lp(long long B, int m_max, int n, const double* c, const double* G, const double* h, const int* mrows,
+                     double* x, double* fun, int* status, void* scratch, int parity, hipStream_t st);
+int launch_verify_cheby(long long B, int m_max, int d, const double* A, const double* b, const int* mrows, double* r,
+                        double* xc, int* status, void* scratch, int parity, hipStream_t st);
+int launch_verify_box(long long B, int m_max, int d, const double* A, const double* b, const int* mrows, double* lb, double* ub,
+                      int* status, const signed char* basis8, const double* centre, const double* xfin, void* scratch,
+                      int parity, hipStream_t st);
+
 }  // namespace plp

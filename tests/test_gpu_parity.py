@@ -1171,6 +1171,14 @@ def test_contains_vs_oracle(pa, oracle):
             assert np.array_equal(reg.astype(bool), out.astype(bool).any(axis=0))
     with pytest.raises(ValueError):
         pa.contains_batch(A, b, np.zeros((3, 4)))
+    # once a large batch has been staged the context owns a staging buffer; the containment matrix of 1 MiB or more still
+    # comes back as a direct copy (the library declares it so): the 64 x 20000 matrix again, after a staged reduce
+    from polytope_amd.synth import random_hpolytopes
+    As, bs = random_hpolytopes(100000, 16, 3, seed=0)
+    pa.reduce_batch(As, bs)
+    A, b, X = containment_workload(64, 20000, d=6, m=16, seed=6)
+    o = oracle.contains(A, b, np.ascontiguousarray(X.T), abs_tol=1e-7)
+    assert np.array_equal(pa.contains_batch(A, b, X, abs_tol=1e-7, region=False), o)
 
 
 def test_reduce_latency_form_bitwise(pa, monkeypatch):
