@@ -228,6 +228,30 @@ int plp_volume_hits_dev(plp_ctx *ctx, void *stream, int64_t B, int m_max, int d,
                         const uint64_t *inc, int64_t N, uint32_t *hits, int32_t *flags);
 
 /*
+ * Support functions  h_P(c) = max { c.x : A x <= b }  of B packed polytopes in K directions each (template directions,
+ * H-in-H containment, the facet LPs of an iterative hull): the rows of a polytope are read once for all its directions.
+ * In:  A[B][m_max][d], b[B][m_max], m[B] (NULL = m_max) as for plp_reduce_batch;
+ *      C: the directions, [K][d] shared by every polytope (c_shared != 0) or [B][K][d];
+ *      xc[B][d]: a STRICTLY interior point of each polytope (plp_cheby_batch's centre), from which every LP starts.
+ * Out: val[B][K] = c.x at the optimum (the MAXIMUM), x[B][K][d] the point (NULL: not written), status[B][K]:
+ *        0  optimum;
+ *        3  unbounded in that direction: val = +inf, x = NaN;
+ *        1  NOT SETTLED HERE (val = x = NaN) -- a row i < m with b_i - a_i.xc <= 0 (xc is not strictly inside, or NaN),
+ *           an LP the one-LP-per-lane engine hands back (degenerate steps, dependent active rows, its iteration cap), or a
+ *           final point x' = x - xc with  max_i (a_i.x' - beta_i) > 1e-9 max(1, |beta|_max),  beta_i = b_i - a_i.xc.  The
+ *           caller solves these (polytope, direction) pairs as generic LPs (plp_lp_solve_batch with c = -C).
+ *      That end check is a feasibility check only; optimality is the engine's own multiplier test.  The answers of this
+ *      call are NOT under the verifier's certificate (plp_verify_counters does not see them).
+ * d <= 4, m_max <= 64, K >= 1 and B * K <= 2^31 - 1, else PLP_EUNSUPPORTED.  B = 0: returns PLP_OK, nothing runs.
+ * The host-pointer form checks A, b and C for inf / nan when the context asks for it (plp_ctx_set_check_finite).
+ */
+int plp_support_batch(plp_ctx *ctx, int64_t B, int m_max, int d, const double *A, const double *b, const int32_t *m,
+                      int K, const double *C, int c_shared, const double *xc, double *val, double *x, int32_t *status);
+int plp_support_batch_dev(plp_ctx *ctx, void *stream, int64_t B, int m_max, int d, const double *A, const double *b,
+                          const int32_t *m, int K, const double *C, int c_shared, const double *xc, double *val,
+                          double *x, int32_t *status);
+
+/*
  * Containment of N points in P polytopes:  all_i( A_p[i,:].x - b_p[i] < abs_tol ).
  * Replaces: Polytope.contains (polytope/polytope.py:206-218), Region.contains (:732-746),
  *           is_inside (:1017-1029), __contains__ (:191-204, :723-730).

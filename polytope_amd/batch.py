@@ -417,6 +417,130 @@ def volume_batch(A, b, m=None, nsamples=None, seed=None, lb=None, ub=None):
     return dict(volume=vol, hits=hits, nsamples=N, lb=lb, ub=ub, flags=flags, seeds=seeds)
 
 
+# ------------------------------------------------------------------------------------- support functions
+_SUPPORT_MAX_D = 4          # the shared-row kernel (csrc/plp_support.hip) walks in R^3 / R^4
+_SUPPORT_CHUNK = 1 << 20    # LPs per lpsolve_batch call when rows are expanded per direction
+
+
+def _support_input(be, a):
+    """C / xc of support_batch on the backend of A (a numpy array beside CUDA tensors goes to their device)."""
+    if be.torch is not None and not _is_torch(a):
+        a = _np(a)
+        _count_h2d(a)
+        a = be.torch.as_tensor(a).to(be.device)
+    return be.arr(a)
+
+
+def _support_pairs(be, A, b, m, C, shared, pi, ji, flat, h, x, status):
+    """The LPs (polytope pi[t], direction ji[t]) as generic LPs  min -c.x  s.t. A x <= b  through lpsolve_batch, the rows
+    gathered per pair, at most _SUPPORT_CHUNK LPs per call; results written to position flat[t] of h / x / status."""
+    hf, sf = h.reshape(-1), status.reshape(-1)
+    xf = None if x is None else x.reshape(-1, x.shape[-1])
+    for lo in range(0, int(pi.shape[0]), _SUPPORT_CHUNK):
+        p, j, f = pi[lo:lo + _SUPPORT_CHUNK], ji[lo:lo + _SUPPORT_CHUNK], flat[lo:lo + _SUPPORT_CHUNK]
+        c = -(C[j] if shared else C[p, j])
+        sol = lpsolve_batch(c, A[p], b[p], None if m is None else m[p])
+        st = sol["status"]
+        sf[f] = st
+        hv = -sol["fun"]
+        hv[st == 3] = float("inf")
+        hf[f] = hv
+        if xf is not None:
+            xf[f] = sol["x"]
+
+
+def support_batch(A, b, C, m=None, xc=None, points=True, resolve=True):
+    """Support functions  h_P(c) = max { c.x : A x <= b }  of B packed polytopes in K directions each: one LP per
+    (polytope, direction), the rows of a polytope read once for all its directions (include/plp.h: plp_support_batch).
+
+    A[B, m_max, d], b[B, m_max], m[B] as everywhere; C: the directions, [K, d] shared by all polytopes or [B, K, d].
+    xc[B, d]: a strictly interior point per polytope; None: cheby_ball_batch runs first -- a polytope it finds infeasible
+    gets status 2 in every direction, one without a usable centre (the Chebyshev LP not optimal, r <= 0, r = inf) a NaN
+    centre, which the kernel hands back as status 1.
+    -> dict(h[B, K], x[B, K, d] (None with points=False), status int32[B, K]); numpy in, numpy out; CUDA tensors in,
+    tensors out on torch's current stream.
+    status: 0 optimum; 3 unbounded in that direction (h = +inf, x = NaN); 2 the polytope is empty (h = x = NaN);
+    4 numerical failure; 1 (only with resolve=False) not settled by the kernel.  resolve=True (the default) solves the
+    pairs the kernel hands back through lpsolve_batch (c = -C, rows gathered per pair), so a caller sees lpsolve's codes
+    only.  A zero direction gives h = 0, status 0 and x a feasible point.
+    d <= 4 and m_max <= 64 run on the shared-row kernel.  Other shapes (d up to 16, any m_max lpsolve_batch takes) have no
+    shared-row kernel yet: they go through lpsolve_batch with the rows expanded per direction, at most 2^20 LPs at a
+    time, behind the same interface (xc is not used there).
+    The kernel's answers pass an end check of the final point against every row (1e-9 relative); they are NOT under the
+    verifier's certificate that lpsolve_batch / cheby_ball_batch / bbox_batch answers carry."""
+    be = _Backend(A)
+    A, b, m, (B, m_max, d) = _packed(be, A, b, m)
+    C = _support_input(be, C)
+    shp = tuple(C.shape)
+    if len(shp) not in (2, 3):
+        raise ValueError("C must be [K, d] or [B, K, d], got %d dimensions" % len(shp))
+    if shp[-1] != d or (len(shp) == 3 and shp[0] != B):
+        raise ValueError("C must be [K, %d] or [%d, K, %d], got %s" % (d, B, d, list(shp)))
+    K = int(shp[-2])
+    if K < 1:
+        raise ValueError("C holds no direction (K = 0)")
+    shared = len(shp) == 2
+    if xc is not None:
+        xc = _support_input(be, xc)
+        if tuple(xc.shape) != (B, d):
+            raise ValueError("xc must be [B, d] = [%d, %d], got %s" % (B, d, list(xc.shape)))
+    xp = be.torch if be.torch is not None else np
+    h, status = be.out((B, K), zero=True), be.out((B, K), np.int32, zero=True)
+    x = be.out((B, K, d), zero=True) if points else None
+    if B == 0:
+        return dict(h=h, x=x, status=status)
+    if d > _SUPPORT_MAX_D or m_max > MAX_M:   # no shared-row kernel at this shape yet
+        n = B * K
+        for lo in range(0, n, _SUPPORT_CHUNK):
+            flat = xp.arange(lo, min(lo + _SUPPORT_CHUNK, n), **({} if be.torch is None else {"device": be.device}))
+            _support_pairs(be, A, b, m, C, shared, flat // K, flat % K, flat, h, x, status)
+        return dict(h=h, x=x, status=status)
+    infeasible = None
+    if xc is None:
+        ball = cheby_ball_batch(A, b, m)
+        r = ball["r"]
+        ok = (ball["status"] == 0) & (r > 0) & (r < float("inf"))
+        nan = float("nan") if be.torch is None else be.torch.full((), float("nan"), dtype=be.torch.float64, device=be.device)
+        xc = xp.where(ok[:, None], ball["xc"], nan)
+        infeasible = ball["status"] == 2
+    be.call("plp_support_batch", B, m_max, d, A, b, m, K, C, 1 if shared else 0, xc, h, x, status, h2d=(A, b, m, C, xc))
+    if infeasible is not None and bool(infeasible.any()):
+        status[infeasible] = 2
+        h[infeasible] = float("nan")
+        if x is not None:
+            x[infeasible] = float("nan")
+    if resolve:
+        pi, ji = xp.nonzero(status == 1) if be.torch is None else (status == 1).nonzero(as_tuple=True)
+        if int(pi.shape[0]):
+            _support_pairs(be, A, b, m, C, shared, pi, ji, pi * K + ji, h, x, status)
+    return dict(h=h, x=x, status=status)
+
+
+def subset_batch(A, b, QA, Qb, m=None, mq=None, abs_tol=1e-7):
+    """The exact H-in-H test  P_k <= Q_k  for B pairs: P_k = {A_k x <= b_k} lies in Q_k = {QA_k x <= Qb_k} iff the support
+    function of P_k in the direction of every row of Q_k stays below that row's right-hand side.
+    A[B, m_max, d], b[B, m_max], m[B];  QA[B, mq_max, d], Qb[B, mq_max], mq[B] (rows of Q_k in use) -> bool[B]:
+    all(h_P(q_j) <= g_j + abs_tol) over the live rows (q_j, g_j) of Q -- support_batch with C = QA.  An empty P is a subset
+    of anything; a direction in which P is unbounded means False.
+    This is NOT what is_subset / `<=` of polytope_amd.polytope compute: those replay the reference's region_diff route (with
+    its sampled volumes) and are not wired to this call."""
+    be = _Backend(A)
+    QA = _support_input(be, QA)
+    if len(QA.shape) != 3:
+        raise ValueError("QA must be [B, mq_max, d]")
+    Bq, mq_max, _ = QA.shape
+    Qb = _support_input(be, Qb).reshape(Bq, mq_max)
+    res = support_batch(A, b, QA, m=m, points=False)
+    h, st = res["h"], res["status"]
+    xp = be.torch if be.torch is not None else np
+    fine = ((st == 0) & (h <= Qb + abs_tol)) | (st == 2)
+    if mq is not None:
+        mq = _support_input(be, mq)
+        rows = xp.arange(mq_max, **({} if be.torch is None else {"device": be.device}))
+        fine = fine | (rows[None, :] >= mq.reshape(Bq, 1))
+    return fine.all(1)
+
+
 def assign_batch(X, normals, offsets, abs_tol=1e-7):
     """quickhull outside-set assignment + furthest point (quickhull.py:87-102,117-121,224-245).
 

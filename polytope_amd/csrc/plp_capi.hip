@@ -783,6 +783,57 @@ int plp_volume_hits(plp_ctx* ctx, int64_t B, int m_max, int d, const double* A, 
     return hc.download();
 }
 
+// ------------------------------------------------------------------------------- support functions
+namespace {
+int support_check(plp_ctx* ctx, int64_t B, int m_max, int d, const double* A, const double* b, int K, const double* C,
+                  const double* xc, const double* val, const int32_t* status) {
+    if (!ctx) return fail(PLP_EINVAL, "ctx is NULL");
+    if (B < 0 || m_max < 0 || d < 1) return fail(PLP_EINVAL, "bad sizes");
+    if (B == 0) return PLP_OK;
+    if (d > 4 || m_max > plp::MAX_M)
+        return fail(PLP_EUNSUPPORTED, "support: m_max=%d d=%d outside the shared-row kernel (m<=64, d<=4)", m_max, d);
+    if (K < 1) return fail(PLP_EUNSUPPORTED, "support: K=%d directions (needs K >= 1)", K);
+    if (B > 2147483647ll / K) return fail(PLP_EUNSUPPORTED, "support: B * K exceeds 2^31 - 1");
+    if (!C || !xc || !val || !status || (m_max > 0 && (!A || !b))) return fail(PLP_EINVAL, "NULL pointer");
+    return PLP_OK;
+}
+}  // namespace
+
+int plp_support_batch_dev(plp_ctx* ctx, void* stream, int64_t B, int m_max, int d, const double* A, const double* b,
+                          const int32_t* m, int K, const double* C, int c_shared, const double* xc, double* val, double* x,
+                          int32_t* status) {
+    int rc = support_check(ctx, B, m_max, d, A, b, K, C, xc, val, status);
+    if (rc || B == 0) return rc;
+    if (plp::launch_support(B, m_max, d, A, b, m, K, C, c_shared, xc, val, x, status, (hipStream_t)stream))
+        return fail(PLP_EUNSUPPORTED, "support: unsupported size");
+    return check_launch("support_kernel");
+}
+
+int plp_support_batch(plp_ctx* ctx, int64_t B, int m_max, int d, const double* A, const double* b, const int32_t* m, int K,
+                      const double* C, int c_shared, const double* xc, double* val, double* x, int32_t* status) {
+    int rc = support_check(ctx, B, m_max, d, A, b, K, C, xc, val, status);
+    if (rc || B == 0) return rc;
+    const size_t lps = (size_t)B * K;
+    double *dA, *db, *dC, *dxc, *dval, *dx;
+    int32_t *dm, *dst;
+    HostCall hc(ctx);
+    hc.in(dA, A, (size_t)B * m_max * d, 0, true);
+    hc.in(db, b, (size_t)B * m_max, 0, true);
+    hc.in(dm, m, B);
+    hc.in(dC, C, (c_shared ? (size_t)K : lps) * d, 0, true);
+    hc.in(dxc, xc, (size_t)B * d);   // (a centre may be NaN: that polytope comes back as status 1)
+    hc.out(dval, val, lps);
+    hc.out(dx, x, x ? lps * d : 0);
+    hc.out(dst, status, lps);
+    rc = hc.reserve();
+    if (rc) return rc;
+    rc = hc.upload();
+    if (rc) return rc;
+    rc = plp_support_batch_dev(ctx, hc.st, B, m_max, d, dA, db, dm, K, dC, c_shared, dxc, dval, x ? dx : nullptr, dst);
+    if (rc) return rc;
+    return hc.download();
+}
+
 }  // extern "C"
 
 struct plp_hull {

@@ -58,6 +58,10 @@ size_t fm_lds_bytes(int m_max, int d);
 int launch_volume_hits(long long B, int m_max, int d, const double* A, const double* b, const int* mrows, const double* lb,
                        const double* ub, const unsigned long long* state, const unsigned long long* inc, long long N,
                        unsigned* hits, int* flags, hipStream_t st);
+// support functions in K directions per polytope, rows staged once (plp_support.hip; d <= 4, m_max <= 64): val[B][K],
+// x[B][K][d] (or nullptr), status[B][K] (0 optimum, 3 unbounded, 1 handed back).  2: unsupported size
+int launch_support(long long B, int m_max, int d, const double* A, const double* b, const int* mrows, int K, const double* C,
+                   int c_shared, const double* xc, double* val, double* x, int* status, hipStream_t st);
 int launch_reduce_lds(long long B, int m_max, int d, const double* A, const double* b, const int* mrows, double abs_tol,
                       unsigned long long* keep, int* flags, double* r, double* xc, int* nlp, hipStream_t st);
 
