@@ -466,8 +466,13 @@ def support_batch(A, b, C, m=None, xc=None, points=True, resolve=True):
     d <= 4 and m_max <= 64 run on the shared-row kernel.  Other shapes (d up to 16, any m_max lpsolve_batch takes) have no
     shared-row kernel yet: they go through lpsolve_batch with the rows expanded per direction, at most 2^20 LPs at a
     time, behind the same interface (xc is not used there).
-    The kernel's answers pass an end check of the final point against every row (1e-9 relative); they are NOT under the
-    verifier's certificate that lpsolve_batch / cheby_ball_batch / bbox_batch answers carry."""
+    The kernel's status-0 answers pass two end checks: the final point against every row (1e-10 of the extent, and what
+    it is outside a row by is worth at most 1e-10 of the extent in h), and an optimality certificate on the rows the walk
+    ended on (multipliers >= 0, complementary slackness to 1e-10 and the cost's residual to 1e-12 of the extent).  So with E
+    = max(1, |x|_inf, |h|): h <= h* + 1e-10 E, and h >= h* - 2e-10 E provided an optimal point lies within 100 max(1, |x - xc|)
+    of x (for an optimal face reaching further the residual term is not bounded; plp_support.hpp).  What fails either
+    check is handed back (status 1) and, with resolve=True, solved by lpsolve_batch under the verifier's certificate.  The
+    kernel's own certificate is not that one."""
     be = _Backend(A)
     A, b, m, (B, m_max, d) = _packed(be, A, b, m)
     C = _support_input(be, C)

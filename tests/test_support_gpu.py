@@ -17,7 +17,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 from polytope_amd import _lib, batch  # noqa: E402
 from polytope_amd.synth import random_hpolytopes  # noqa: E402
 import support_host as sh  # noqa: E402
-from test_support_host import family_case  # noqa: E402
+from test_support_host import family_case, soak_family_case  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -96,6 +96,108 @@ def test_families_raw_and_resolved(L, oracle, k, shared):
     At, bt, mt, Ct = dev(A, b, m, C_)
     rt = batch.support_batch(At, bt, Ct, m=mt)
     sh.check_against_oracle(A, b, m, C_, rt["h"].cpu().numpy(), rt["x"].cpu().numpy(), rt["status"].cpu().numpy(), ost, oh)
+
+
+ALL_FAMILIES = sh.FAMILIES + ("degenerate",)
+
+
+@pytest.mark.parametrize("fam", ALL_FAMILIES)
+def test_soak_families_raw_equal_the_host_build(L, oracle, fam):
+    """The inputs of tests/test_support_host.py: test_soak_families_equal_the_oracle / test_degenerate_vertices_equal_the_oracle
+    (the seven soak families, NaN centres included, both layouts of C; `dup` also on the stream of seed 8): statuses
+    identical to the host build's, h and x bit for bit where the status is 0 -- what the host build is held to against the
+    oracle there, the device inherits."""
+    cases = list(soak_family_case(oracle, fam))
+    if fam != "degenerate":   # the translated case of tests/test_support_host.py: beta = b - a.xc cancels three digits
+        cases += soak_family_case(oracle, fam, seed=sh.FAMILY_SEED[fam] + 100, shapes=((32, 4), (16, 3)), translate=1e3)
+    if fam == "dup":
+        for seed in (7, 8, 9, 10):
+            cases += soak_family_case(oracle, "dup", seed=seed, shapes=sh.FOUND_SHAPES)
+    for case in cases:
+        for layout in ("shared", "own"):
+            want_h, want_x, want_st = sh.run_case(L, case, layout)
+            raw = batch.support_batch(case["A"], case["b"], case[layout][0], m=case["m"], xc=case["xc"], resolve=False)
+            assert np.array_equal(raw["status"], want_st), (case["shape"], layout, np.argwhere(raw["status"] != want_st)[:5])
+            ok = want_st == 0
+            assert same_bits(raw["h"][ok], want_h[ok]) and same_bits(raw["x"][ok], want_x[ok]), (case["shape"], layout)
+            assert np.all(np.isnan(raw["h"][want_st == 1])) and np.all(raw["h"][want_st == 3] == np.inf)
+
+
+def test_found_fixtures_raw_equal_the_host_build(L):
+    """tests/golden/found/support/*.npz: the three polytopes with the four status-0 answers that were not optimal, and the 54
+    LPs on which the oracle is off -- statuses and bits of the host build (which tests/test_support_host.py holds against the
+    oracle and the exact optimum by name)."""
+    z = np.load(os.path.join(ROOT, "tests", "golden", "found", "support", "dup.npz"))
+    calls = [(z["A_" + k[2:]][None], z["b_" + k[2:]][None], z["C_" + k[2:]], z["xc_" + k[2:]][None]) for k in z.files if k.startswith("A_")]
+    calls += [(A[None], b[None], c[None], xc[None]) for _, A, b, c, xc, _, _ in sh.oracle_off_fixture()]
+    assert len(calls) == 3 + 54
+    for A, b, C_, xc in calls:
+        want_h, want_x, want_st = sh.run(L, A, b, C_, xc)
+        raw = batch.support_batch(A, b, C_, xc=xc, resolve=False)
+        assert np.array_equal(raw["status"], want_st)
+        ok = want_st == 0
+        assert same_bits(raw["h"][ok], want_h[ok]) and same_bits(raw["x"][ok], want_x[ok])
+
+
+@pytest.mark.parametrize("fam", ALL_FAMILIES)
+def test_soak_families_resolved_equal_the_oracle(oracle, fam):
+    """resolve=True on the same inputs: EVERY LP against the oracle with the extent rule, nothing left out -- the centre given
+    (numpy in) and left to cheby_ball_batch (CUDA tensors in, and numpy for the shared layout).  A polytope the oracle finds
+    empty gives 2 in every direction."""
+    for case in soak_family_case(oracle, fam):
+        A, b, m = case["A"], case["b"], case["m"]
+        for layout in ("shared", "own"):
+            C_, ost, oh, ox = case[layout]
+            res = batch.support_batch(A, b, C_, m=m, xc=case["xc"])
+            sh.check_against_oracle(A, b, m, C_, res["h"], res["x"], res["status"], ost, oh, ext=ox)
+            At, bt, mt, Ct = dev(A, b, m, C_)
+            rt = batch.support_batch(At, bt, Ct, m=mt)
+            assert rt["h"].is_cuda
+            sh.check_against_oracle(A, b, m, C_, rt["h"].cpu().numpy(), rt["x"].cpu().numpy(), rt["status"].cpu().numpy(), ost, oh, ext=ox)
+            if layout == "shared":
+                rn = batch.support_batch(A, b, C_, m=m)
+                sh.check_against_oracle(A, b, m, C_, rn["h"], rn["x"], rn["status"], ost, oh, ext=ox)
+
+
+@pytest.mark.parametrize("m_max,d", [(32, 4), (48, 4)])
+def test_subset_batch_on_rows_a_hair_apart(oracle, m_max, d):
+    """`dup`, B = 60: P against Q = the rows of P with every right-hand side moved to the oracle's h_P(a_i) + -1e-3 max(1, |h|)
+    -- up on every row for the even polytopes (inside), down on some for the odd ones (not inside); a row in whose direction
+    P is unbounded keeps its b (not inside).  No row is within 1e-4 of a tie; the verdicts are those of the oracle's h.  (An
+    h that is too small -- a feasible vertex that is not the optimum -- turns "not inside" into "inside".)"""
+    def make():
+        rng = np.random.default_rng(700 + m_max)
+        A, b, m = sh.family("dup", B=60, rng=rng, shape=(m_max, d))
+        ost, oh = sh.oracle_support(oracle, A, b, m, A)
+        return A, b, m, ost, oh, rng.random((60, m_max))
+    A, b, m, ost, oh, u = sh.memo(("subset_dup", m_max), make)
+    down = (u < 0.15) & (np.arange(60) % 2 == 1)[:, None]
+    down[1::2, 0] = True
+    assert np.all(np.isin(ost, (0, 3)))
+    Qb = np.where(ost == 0, oh + np.where(down, -1e-3, 1e-3) * np.maximum(1.0, np.abs(oh)), b)
+    gap = np.where(ost == 0, Qb - oh, -np.inf)
+    assert np.all(np.abs(gap) > 1e-4)
+    expect = (gap >= 0).all(axis=1)
+    assert expect[1::2].sum() == 0 and expect[0::2].sum() >= 20
+    got = batch.subset_batch(A, b, A, Qb, m=m, mq=m)
+    assert got.dtype == bool and np.array_equal(got, expect), np.nonzero(got != expect)[0]
+    gt = batch.subset_batch(*dev(A, b, A, Qb), m=dev(m)[0], mq=dev(m)[0])
+    assert gt.is_cuda and np.array_equal(gt.cpu().numpy(), expect)
+
+
+def test_soak_family_on_another_stream(oracle):
+    """`dup` at (48, 4), K = 15, on a torch stream that is not the default one: the default stream's bits."""
+    import torch
+    case = soak_family_case(oracle, "dup")[5]
+    C_ = case["shared"][0]
+    full = batch.support_batch(case["A"], case["b"], C_, m=case["m"])
+    At, bt, mt, Ct = dev(case["A"], case["b"], case["m"], C_)
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream()
+    with torch.cuda.stream(side):
+        rs = batch.support_batch(At, bt, Ct, m=mt)
+    side.synchronize()
+    assert np.array_equal(rs["status"].cpu().numpy(), full["status"]) and same_bits(rs["h"].cpu().numpy(), full["h"])
 
 
 @pytest.mark.parametrize("k", range(len(sh.SHAPES)))
