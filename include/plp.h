@@ -252,6 +252,37 @@ int plp_support_batch_dev(plp_ctx *ctx, void *stream, int64_t B, int m_max, int 
                           double *x, int32_t *status);
 
 /*
+ * Vertices of B packed polytopes (H-representation to V-representation on the small-polytope path): every d-subset of a
+ * polytope's rows is solved and tested against all rows, one polytope per wavefront, the rows read once.
+ * In:  A[B][m_max][d], b[B][m_max], m[B] (NULL = m_max) as for plp_reduce_batch;
+ *      keep[B] (NULL = every row): bit i set = row i is live, the keep word of plp_reduce_batch.  Pass it: rows that are
+ *      redundant to 1e-7 but not identical do cross somewhere, and each crossing inside the polytope is reported.
+ * Rule (sequential; the kernel computes exactly this list): the live rows, scaled to unit 2-norm, in row order -- a live
+ *      zero row with b >= 0 is ignored, with b < 0 the polytope is empty; every d-subset (i0 < i1 < ...) in lexicographic
+ *      order, skipped when |det| <= 1e-12; the solution v is feasible when a_i.v - b_i <= 1e-9 max(1, |v|_inf, |b_i|) on
+ *      every staged row; a feasible v is dropped when a vertex accepted BEFORE it lies within 1e-9 max(1, |v|_inf) of it
+ *      in the max-norm.  Each geometric vertex appears once, whatever its degeneracy.
+ * Out: V[B][v_max][d] the vertices in that order (NaN beyond count), count[B],
+ *      basis[B][v_max][d] the ORIGINAL row indices of the accepting subset (-1 beyond count; NULL: not written), status[B]:
+ *        0                all vertices written;
+ *        PLP_XS_OVERFLOW  more than v_max distinct vertices: the first v_max are written, count = v_max;
+ *        PLP_XS_EMPTY     no feasible candidate, or an infeasible zero row: count = 0.
+ *      The caller vouches for boundedness: an unbounded polytope has the vertices the rule finds and no status of its own
+ *      (PLP_XS_FLAT / PLP_XS_UNBOUNDED are set by callers that test for it first, as extreme_batch of the Python package does).
+ * 1 <= d <= 4 and m_max <= 64, else PLP_EUNSUPPORTED; v_max < 1 is PLP_EINVAL.  B = 0: returns PLP_OK, nothing runs.
+ * The host-pointer form checks A and b for inf / nan when the context asks for it (plp_ctx_set_check_finite).
+ */
+#define PLP_XS_OVERFLOW 1
+#define PLP_XS_EMPTY 2
+#define PLP_XS_FLAT 3      /* set by callers: empty or not full-dimensional (Chebyshev radius <= abs_tol) */
+#define PLP_XS_UNBOUNDED 4 /* set by callers: a side of the bounding box is infinite                      */
+int plp_extreme_batch(plp_ctx *ctx, int64_t B, int m_max, int d, const double *A, const double *b, const int32_t *m,
+                      const uint64_t *keep, int v_max, double *V, int32_t *count, int32_t *basis, int32_t *status);
+int plp_extreme_batch_dev(plp_ctx *ctx, void *stream, int64_t B, int m_max, int d, const double *A, const double *b,
+                          const int32_t *m, const uint64_t *keep, int v_max, double *V, int32_t *count, int32_t *basis,
+                          int32_t *status);
+
+/*
  * Containment of N points in P polytopes:  all_i( A_p[i,:].x - b_p[i] < abs_tol ).
  * Replaces: Polytope.contains (polytope/polytope.py:206-218), Region.contains (:732-746),
  *           is_inside (:1017-1029), __contains__ (:191-204, :723-730).

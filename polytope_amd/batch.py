@@ -546,6 +546,121 @@ def subset_batch(A, b, QA, Qb, m=None, mq=None, abs_tol=1e-7):
     return fine.all(1)
 
 
+# ------------------------------------------------------------------------------------- vertex enumeration
+# status codes of extreme_batch (include/plp.h: PLP_XS_*); the kernel sets the first three, this module the last two
+XS_OK, XS_OVERFLOW, XS_EMPTY, XS_FLAT, XS_UNBOUNDED = 0, 1, 2, 3, 4
+_EXTREME_MAX_D = 4   # the enumeration kernel (csrc/plp_extreme.hip)
+
+
+def _extreme_vmax(d, n):
+    """The most vertices a polytope of n facets has in dimension d (the upper-bound theorem), at least 1."""
+    return max(1, {1: 2, 2: n, 3: 2 * n - 4}.get(d, n * (n - 3) // 2))
+
+
+def _extreme_unbounded(be, A, b, m, flat, d):
+    """bool[B]: a side of the bounding box is infinite (polytopes marked `flat` are not looked at).  bbox_batch answers from
+    the Chebyshev centre; the polytopes it hands back (status 1: r < 1e-6, a Bland case) get the 2 d generic LPs, where
+    an LP that ends unbounded -- or in any state but optimal / infeasible -- means the polytope is not vouched for.
+    With CUDA tensors the host has to know whether anything was handed back: one flag is read back (a synchronisation),
+    and the indices of those polytopes when there are any."""
+    xp = be.torch if be.torch is not None else np
+    box = bbox_batch(A, b, m)
+    inf = float("inf")
+    open_ = ((box["lb"] == -inf) | (box["ub"] == inf) | (box["lb"] != box["lb"]) | (box["ub"] != box["ub"])).any(1)
+    handled = box["status"] == 0
+    unb = handled & open_ & ~flat
+    back = ~handled & ~flat
+    if bool(back.any()):
+        rest = xp.nonzero(back)[0] if be.torch is None else back.nonzero(as_tuple=True)[0]
+        nr = int(rest.shape[0])
+        cost = np.vstack([np.eye(d), -np.eye(d)])
+        if be.torch is not None:
+            cost = be.torch.as_tensor(cost).to(be.device)
+            rep = lambda a: a[rest].repeat_interleave(2 * d, dim=0)   # noqa: E731
+            c = cost.repeat(nr, 1)
+        else:
+            rep = lambda a: np.repeat(a[rest], 2 * d, axis=0)   # noqa: E731
+            c = np.tile(cost, (nr, 1))
+        st = lpsolve_batch(c, rep(A), rep(b), None if m is None else rep(m))["status"].reshape(nr, 2 * d)
+        unb[rest] = ((st != 0) & (st != 2)).any(1)
+    return unb
+
+
+def extreme_batch(A, b, m=None, v_max=None, reduce=True, abs_tol=1e-7, basis=False):
+    """The vertices of B packed polytopes in one launch: for each polytope the vertices of reduce(P), each geometric vertex
+    once (include/plp.h: plp_extreme_batch -- every d-subset of the rows solved and tested against all rows, one polytope
+    per wavefront).  What extreme() computes per polytope (ref polytope.py:1597-1682), without its repeats of a degenerate
+    vertex (one per simplex of the dual hull) and with a status where it returns None, raises or writes inf / nan.
+
+    A[B, m_max, d], b[B, m_max], m[B] as everywhere; d <= 4 and m_max <= 64.
+    -> dict(V[B, v_max, d] (NaN beyond count), count int32[B], status int32[B], basis int32[B, v_max, d] or None: the
+    input rows of the subset that gave each vertex, -1 beyond count); numpy in, numpy out; CUDA tensors in, tensors out on
+    torch's current stream.
+    status: XS_OK all vertices written; XS_OVERFLOW more than v_max distinct vertices, the first v_max are written;
+    XS_EMPTY no subset of the rows gives a feasible point; XS_FLAT empty or not full-dimensional (reduce_batch says
+    RF_EMPTY, or r <= abs_tol); XS_UNBOUNDED a side of the bounding box is infinite.  FLAT and UNBOUNDED have count 0.
+    reduce=True (the default): reduce_batch supplies the rows in use (`keep`), the radius and the flags, bbox_batch (and
+    the generic LPs for what it hands back) decides boundedness, the kernel runs on what remains.  reduce=False: the
+    kernel runs on the rows as given -- the caller vouches for boundedness and gets raw enumeration: rows that are redundant
+    to 1e-7 but not identical do cross, and the crossings inside the polytope come back as vertices.
+    v_max=None: sized from the upper-bound theorem for the largest number of rows in use in the batch (2, n, 2 n - 4,
+    n (n - 3) / 2 for d = 1 .. 4; one scalar is read back for it).
+    What waits for the device with CUDA tensors: that scalar (v_max=None), and with reduce=True one flag -- did bbox_batch
+    hand a polytope back -- plus the indices of such polytopes when there are any.  reduce=False with v_max given
+    enqueues the kernel and returns."""
+    be = _Backend(A)
+    shp = tuple(A.shape) if hasattr(A, "shape") else np.shape(A)
+    if len(shp) != 3:
+        raise ValueError("A must be [B, m_max, d], got %d dimensions" % len(shp))
+    B, m_max, d = (int(v) for v in shp)
+    bshp = tuple(b.shape) if hasattr(b, "shape") else np.shape(b)
+    if tuple(int(v) for v in bshp) != (B, m_max):
+        raise ValueError("b must be [B, m_max] = [%d, %d], got %s" % (B, m_max, list(bshp)))
+    if m is not None and int(np.prod(tuple(m.shape) if hasattr(m, "shape") else np.shape(m))) != B:
+        raise ValueError("m must be [B] = [%d]" % B)
+    if d < 1 or d > _EXTREME_MAX_D:
+        raise ValueError("extreme_batch enumerates bases in dimension 1 .. %d, got d = %d" % (_EXTREME_MAX_D, d))
+    if m_max > MAX_M:
+        raise ValueError("extreme_batch takes polytopes of up to %d rows, got m_max = %d" % (MAX_M, m_max))
+    if v_max is not None and (not _is_int(v_max) or v_max < 1):
+        raise ValueError("`v_max` must be an integer >= 1, given:  {v}".format(v=v_max))
+    A, b, m, _ = _packed(be, A, b, m)
+    torch = be.torch
+    xp = torch if torch is not None else np
+    on = {} if torch is None else {"device": be.device}
+
+    def empty_result(vm):
+        return dict(V=be.out((B, vm, d), zero=True), count=be.out((B,), np.int32, zero=True),
+                    status=be.out((B,), np.int32, zero=True), basis=be.out((B, vm, d), np.int32, zero=True) if basis else None)
+    if B == 0:
+        return empty_result(1 if v_max is None else int(v_max))
+    keep = flat = unb = None
+    if reduce:
+        red = reduce_batch(A, b, m, abs_tol=abs_tol)
+        flat = ((red["flags"] & _lib.RF_EMPTY) != 0) | ~(red["r"] > abs_tol)
+        unb = _extreme_unbounded(be, A, b, m, flat, d)
+        keep = red["keep"]
+        keep = xp.where(flat | unb, xp.zeros_like(keep), keep)   # (no live row: the kernel leaves at once, count 0)
+    if v_max is None:
+        if keep is not None:
+            bits = xp.arange(64, **on) if torch is not None else np.arange(64, dtype=np.uint64)
+            n = int((((keep[:, None] >> bits[None, :]) & 1) != 0).sum(1).max())
+        elif m is not None:
+            n = min(m_max, max(0, int(m.max())))
+        else:
+            n = m_max
+        v_max = _extreme_vmax(d, n)
+    v_max = int(v_max)
+    res = empty_result(v_max)
+    be.call("plp_extreme_batch", B, m_max, d, A, b, m, keep, v_max, res["V"], res["count"], res["basis"], res["status"],
+            h2d=(A, b, m, keep))
+    if reduce:
+        st = res["status"]
+        code = (lambda v: xp.full_like(st, v))
+        res["status"] = xp.where(flat, code(XS_FLAT), xp.where(unb, code(XS_UNBOUNDED), st))
+    return res
+
+
 def assign_batch(X, normals, offsets, abs_tol=1e-7):
     """quickhull outside-set assignment + furthest point (quickhull.py:87-102,117-121,224-245).
 

@@ -834,6 +834,59 @@ int plp_support_batch(plp_ctx* ctx, int64_t B, int m_max, int d, const double* A
     return hc.download();
 }
 
+// ------------------------------------------------------------------------------- vertex enumeration
+namespace {
+int extreme_check(plp_ctx* ctx, int64_t B, int m_max, int d, const double* A, const double* b, int v_max, const double* V,
+                  const int32_t* count, const int32_t* status) {
+    if (!ctx) return fail(PLP_EINVAL, "ctx is NULL");
+    if (B < 0 || m_max < 0 || d < 1) return fail(PLP_EINVAL, "bad sizes");
+    if (B == 0) return PLP_OK;
+    if (d > 4 || m_max > plp::MAX_M)
+        return fail(PLP_EUNSUPPORTED, "extreme: m_max=%d d=%d outside the enumeration kernel (m<=64, d<=4)", m_max, d);
+    if (v_max < 1) return fail(PLP_EINVAL, "extreme: v_max=%d (needs v_max >= 1)", v_max);
+    if (B > 2147483647ll) return fail(PLP_EUNSUPPORTED, "extreme: B exceeds 2^31 - 1");
+    if (!V || !count || !status || (m_max > 0 && (!A || !b))) return fail(PLP_EINVAL, "NULL pointer");
+    return PLP_OK;
+}
+}  // namespace
+
+int plp_extreme_batch_dev(plp_ctx* ctx, void* stream, int64_t B, int m_max, int d, const double* A, const double* b,
+                          const int32_t* m, const uint64_t* keep, int v_max, double* V, int32_t* count, int32_t* basis,
+                          int32_t* status) {
+    int rc = extreme_check(ctx, B, m_max, d, A, b, v_max, V, count, status);
+    if (rc || B == 0) return rc;
+    if (plp::launch_extreme(B, m_max, d, A, b, m, reinterpret_cast<const unsigned long long*>(keep), v_max, V, count, basis,
+                            status, (hipStream_t)stream))
+        return fail(PLP_EUNSUPPORTED, "extreme: unsupported size");
+    return check_launch("extreme_kernel");
+}
+
+int plp_extreme_batch(plp_ctx* ctx, int64_t B, int m_max, int d, const double* A, const double* b, const int32_t* m,
+                      const uint64_t* keep, int v_max, double* V, int32_t* count, int32_t* basis, int32_t* status) {
+    int rc = extreme_check(ctx, B, m_max, d, A, b, v_max, V, count, status);
+    if (rc || B == 0) return rc;
+    const size_t slots = (size_t)B * v_max * d;
+    double *dA, *db, *dV;
+    int32_t *dm, *dcount, *dbasis, *dst;
+    uint64_t* dkeep;
+    HostCall hc(ctx);
+    hc.in(dA, A, (size_t)B * m_max * d, 0, true);
+    hc.in(db, b, (size_t)B * m_max, 0, true);
+    hc.in(dm, m, B);
+    hc.in(dkeep, keep, B);
+    hc.out(dV, V, slots);
+    hc.out(dcount, count, B);
+    hc.out(dbasis, basis, basis ? slots : 0);
+    hc.out(dst, status, B);
+    rc = hc.reserve();
+    if (rc) return rc;
+    rc = hc.upload();
+    if (rc) return rc;
+    rc = plp_extreme_batch_dev(ctx, hc.st, B, m_max, d, dA, db, dm, dkeep, v_max, dV, dcount, basis ? dbasis : nullptr, dst);
+    if (rc) return rc;
+    return hc.download();
+}
+
 }  // extern "C"
 
 struct plp_hull {

@@ -62,6 +62,10 @@ int launch_volume_hits(long long B, int m_max, int d, const double* A, const dou
 // x[B][K][d] (or nullptr), status[B][K] (0 optimum, 3 unbounded, 1 handed back).  2: unsupported size
 int launch_support(long long B, int m_max, int d, const double* A, const double* b, const int* mrows, int K, const double* C,
                    int c_shared, const double* xc, double* val, double* x, int* status, hipStream_t st);
+// vertices of small polytopes by enumeration of bases, one polytope per wavefront (plp_extreme.hip; d <= 4, m_max <= 64):
+// V[B][v_max][d], count[B], basis[B][v_max][d] (or nullptr), status[B] (0, 1 overflow, 2 empty).  2: unsupported size
+int launch_extreme(long long B, int m_max, int d, const double* A, const double* b, const int* mrows,
+                   const unsigned long long* keep, int v_max, double* V, int* count, int* basis, int* status, hipStream_t st);
 int launch_reduce_lds(long long B, int m_max, int d, const double* A, const double* b, const int* mrows, double abs_tol,
                       unsigned long long* keep, int* flags, double* r, double* xc, int* nlp, hipStream_t st);
 
