@@ -283,6 +283,40 @@ int plp_extreme_batch_dev(plp_ctx *ctx, void *stream, int64_t B, int m_max, int 
                           int32_t *status);
 
 /*
+ * Facets of B packed point sets (V-representation to H-representation on the small-set path, the other direction of
+ * plp_extreme_batch): every d-subset of a set's points spans a hyperplane, which is a facet when all points lie on one
+ * side of it; one point set per wavefront, the points read once.
+ * In:  X[B][n_max][d], n[B] (NULL = n_max): the points in use per set;
+ *      keep[B] (NULL = every point): bit i set = point i is live.
+ * Rule (sequential; the kernel computes exactly this list): the live points in index order, moved to the centre
+ *      c = (min + max) / 2 of their bounding box and divided by s = max |p_i - c|_inf, so that they lie in [-1, 1]^d and
+ *      the tolerances are absolute.  Every d-subset (i0 < i1 < ...) in lexicographic order: nu = the generalised cross
+ *      product of the edges q_ik - q_i0, skipped unless |nu| > 1e-12 prod |edges|; nu scaled to unit length,
+ *      r_i = nu.(q_i - q_i0) over all points.  All |r_i| <= 1e-9: the set is flat.  max r <= 1e-9: the facet nu;
+ *      min r >= -1e-9: the facet -nu.  A facet is dropped when one accepted BEFORE it has the same normal and offset to
+ *      1e-9 (max-norm), so a face with more than d points appears once.
+ * Out: Ao[B][f_max][d] unit normals and bo[B][f_max], the rows Ao x <= bo in the caller's coordinates, in that order (NaN
+ *      beyond count); on[B][f_max]: bit i set = point i is live and lies on the facet to 1e-9 of the extent (0 beyond
+ *      count); count[B]; basis[B][f_max][d] the ORIGINAL indices of the accepting subset (-1 beyond count; NULL: not
+ *      written); status[B]:
+ *        0                all facets written;
+ *        PLP_HS_OVERFLOW  more than f_max distinct facets: the first f_max are written, count = f_max;
+ *        PLP_HS_FLAT      fewer than d + 1 live points, all of them one point, or all on one hyperplane: count = 0.
+ *      The rows are neither reduced nor ordered further; no vertex list is written (the bits of `on` are the points on
+ *      the boundary, plp_extreme_batch on the rows gives the vertices).
+ * 1 <= d <= 4 and n_max <= 64, else PLP_EUNSUPPORTED; f_max < 1 is PLP_EINVAL.  B = 0: returns PLP_OK, nothing runs.
+ * The host-pointer form checks X for inf / nan when the context asks for it (plp_ctx_set_check_finite).
+ */
+#define PLP_HS_OK 0
+#define PLP_HS_OVERFLOW 1
+#define PLP_HS_FLAT 2
+int plp_hull_batch(plp_ctx *ctx, int64_t B, int n_max, int d, const double *X, const int32_t *n, const uint64_t *keep,
+                   int f_max, double *Ao, double *bo, uint64_t *on, int32_t *count, int32_t *basis, int32_t *status);
+int plp_hull_batch_dev(plp_ctx *ctx, void *stream, int64_t B, int n_max, int d, const double *X, const int32_t *n,
+                       const uint64_t *keep, int f_max, double *Ao, double *bo, uint64_t *on, int32_t *count,
+                       int32_t *basis, int32_t *status);
+
+/*
  * Containment of N points in P polytopes:  all_i( A_p[i,:].x - b_p[i] < abs_tol ).
  * Replaces: Polytope.contains (polytope/polytope.py:206-218), Region.contains (:732-746),
  *           is_inside (:1017-1029), __contains__ (:191-204, :723-730).

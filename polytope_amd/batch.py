@@ -661,6 +661,61 @@ def extreme_batch(A, b, m=None, v_max=None, reduce=True, abs_tol=1e-7, basis=Fal
     return res
 
 
+# ------------------------------------------------------------------------------------- facet enumeration
+# status codes of hull_batch (include/plp.h: PLP_HS_*)
+HS_OK, HS_OVERFLOW, HS_FLAT = 0, 1, 2
+
+
+def hull_batch(X, n=None, f_max=None, basis=False):
+    """The facets of B packed point sets in one launch: rows A x <= b of the convex hull of each set, each face once
+    (include/plp.h: plp_hull_batch -- every d-subset of the points spans a hyperplane, which is a facet when all points lie
+    on one side of it; one point set per wavefront).  What quickhull() computes per set (ref quickhull.py:141-359), without
+    its repeats of a face that carries more than d points and with a status where it prints "not fully dimensional".
+
+    X[B, n_max, d], n[B] (the points in use per set, None = n_max); d <= 4 and n_max <= 64.
+    -> dict(A[B, f_max, d] unit normals and b[B, f_max] (NaN beyond count), on uint64[B, f_max]: bit i set when point i
+    lies on the facet (0 beyond count), count int32[B], status int32[B], basis int32[B, f_max, d] or None: the points of
+    the subset that gave each facet, -1 beyond count); numpy in, numpy out; CUDA tensors in, tensors out on torch's current
+    stream, `on` then as int64 with the same bits (torch has no unsigned words).  numpy input is checked for inf / nan by
+    the library, padding included: the V of extreme_batch carries NaN beyond count, so pass it on as CUDA tensors or zero it.
+    The rule: the points are moved to the centre of their bounding box and scaled to [-1, 1]^d, so the tolerances are
+    absolute; a subset is skipped when its normal is shorter than 1e-12 of the product of its edge lengths; a point is on
+    a plane, or on its right side, to 1e-9; all points on one plane means the set is flat; a facet is dropped when one
+    accepted before it has the same unit normal and offset to 1e-9.
+    status: HS_OK all facets written; HS_OVERFLOW more than f_max distinct facets, the first f_max are written; HS_FLAT
+    fewer than d + 1 points, or all of them in one hyperplane: count 0.
+    f_max=None: sized from the upper-bound theorem for the largest n of the batch (2, n, 2 n - 4, n (n - 3) / 2 for
+    d = 1 .. 4, the bound of extreme_batch by duality; one scalar is read back for it when n is a CUDA tensor).  With
+    f_max given the call enqueues the kernel and returns.
+    Not provided: a vertex list -- the bits of `on` name the points on the boundary, and extreme_batch on the rows gives the
+    vertices.  The rows are neither reduced (a near-degenerate subset can repeat a face as a second, slightly tilted row)
+    nor passed through Polytope."""
+    be = _Backend(X)
+    shp = tuple(X.shape) if hasattr(X, "shape") else np.shape(X)
+    if len(shp) != 3:
+        raise ValueError("X must be [B, n_max, d], got %d dimensions" % len(shp))
+    B, n_max, d = (int(v) for v in shp)
+    if n is not None and int(np.prod(tuple(n.shape) if hasattr(n, "shape") else np.shape(n))) != B:
+        raise ValueError("n must be [B] = [%d]" % B)
+    if d < 1 or d > _EXTREME_MAX_D:
+        raise ValueError("hull_batch enumerates hyperplanes in dimension 1 .. %d, got d = %d" % (_EXTREME_MAX_D, d))
+    if n_max > MAX_M:
+        raise ValueError("hull_batch takes point sets of up to %d points, got n_max = %d" % (MAX_M, n_max))
+    if f_max is not None and (not _is_int(f_max) or f_max < 1):
+        raise ValueError("`f_max` must be an integer >= 1, given:  {v}".format(v=f_max))
+    X, n = be.arr(X), be.arr(n, np.int32, (B,))
+    if f_max is None:
+        f_max = _extreme_vmax(d, n_max if n is None or B == 0 else min(n_max, max(0, int(n.max()))))
+    f_max = int(f_max)
+    res = dict(A=be.out((B, f_max, d), zero=True), b=be.out((B, f_max), zero=True), on=be.out((B, f_max), np.uint64, zero=True),
+               count=be.out((B,), np.int32, zero=True), status=be.out((B,), np.int32, zero=True),
+               basis=be.out((B, f_max, d), np.int32, zero=True) if basis else None)
+    if B:
+        be.call("plp_hull_batch", B, n_max, d, X, n, None, f_max, res["A"], res["b"], res["on"], res["count"], res["basis"],
+                res["status"], h2d=(X, n))
+    return res
+
+
 def assign_batch(X, normals, offsets, abs_tol=1e-7):
     """quickhull outside-set assignment + furthest point (quickhull.py:87-102,117-121,224-245).
 

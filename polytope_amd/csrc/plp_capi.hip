@@ -887,6 +887,60 @@ int plp_extreme_batch(plp_ctx* ctx, int64_t B, int m_max, int d, const double* A
     return hc.download();
 }
 
+// ------------------------------------------------------------------------------- facet enumeration
+namespace {
+int hull_enum_check(plp_ctx* ctx, int64_t B, int n_max, int d, const double* X, int f_max, const double* Ao, const double* bo,
+                    const uint64_t* on, const int32_t* count, const int32_t* status) {
+    if (!ctx) return fail(PLP_EINVAL, "ctx is NULL");
+    if (B < 0 || n_max < 0) return fail(PLP_EINVAL, "bad sizes");
+    if (B == 0) return PLP_OK;
+    if (d < 1 || d > 4 || n_max > plp::MAX_M)
+        return fail(PLP_EUNSUPPORTED, "hull: n_max=%d d=%d outside the enumeration kernel (n<=64, 1<=d<=4)", n_max, d);
+    if (f_max < 1) return fail(PLP_EINVAL, "hull: f_max=%d (needs f_max >= 1)", f_max);
+    if (B > 2147483647ll) return fail(PLP_EUNSUPPORTED, "hull: B=%lld exceeds 2^31 - 1", (long long)B);
+    if (!Ao || !bo || !on || !count || !status || (n_max > 0 && !X)) return fail(PLP_EINVAL, "NULL pointer");
+    return PLP_OK;
+}
+}  // namespace
+
+int plp_hull_batch_dev(plp_ctx* ctx, void* stream, int64_t B, int n_max, int d, const double* X, const int32_t* n,
+                       const uint64_t* keep, int f_max, double* Ao, double* bo, uint64_t* on, int32_t* count, int32_t* basis,
+                       int32_t* status) {
+    int rc = hull_enum_check(ctx, B, n_max, d, X, f_max, Ao, bo, on, count, status);
+    if (rc || B == 0) return rc;
+    if (plp::launch_hull_enum(B, n_max, d, X, n, reinterpret_cast<const unsigned long long*>(keep), f_max, Ao, bo,
+                              reinterpret_cast<unsigned long long*>(on), count, basis, status, (hipStream_t)stream))
+        return fail(PLP_EUNSUPPORTED, "hull: unsupported size");
+    return check_launch("hull_enum_kernel");
+}
+
+int plp_hull_batch(plp_ctx* ctx, int64_t B, int n_max, int d, const double* X, const int32_t* n, const uint64_t* keep, int f_max,
+                   double* Ao, double* bo, uint64_t* on, int32_t* count, int32_t* basis, int32_t* status) {
+    int rc = hull_enum_check(ctx, B, n_max, d, X, f_max, Ao, bo, on, count, status);
+    if (rc || B == 0) return rc;
+    const size_t slots = (size_t)B * f_max;
+    double *dX, *dA, *db;
+    int32_t *dn, *dcount, *dbasis, *dst;
+    uint64_t *dkeep, *don;
+    HostCall hc(ctx);
+    hc.in(dX, X, (size_t)B * n_max * d, 0, true);
+    hc.in(dn, n, B);
+    hc.in(dkeep, keep, B);
+    hc.out(dA, Ao, slots * d);
+    hc.out(db, bo, slots);
+    hc.out(don, on, slots);
+    hc.out(dcount, count, B);
+    hc.out(dbasis, basis, basis ? slots * d : 0);
+    hc.out(dst, status, B);
+    rc = hc.reserve();
+    if (rc) return rc;
+    rc = hc.upload();
+    if (rc) return rc;
+    rc = plp_hull_batch_dev(ctx, hc.st, B, n_max, d, dX, dn, dkeep, f_max, dA, db, don, dcount, basis ? dbasis : nullptr, dst);
+    if (rc) return rc;
+    return hc.download();
+}
+
 }  // extern "C"
 
 struct plp_hull {

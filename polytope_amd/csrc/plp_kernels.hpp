@@ -66,6 +66,11 @@ int launch_support(long long B, int m_max, int d, const double* A, const double*
 // V[B][v_max][d], count[B], basis[B][v_max][d] (or nullptr), status[B] (0, 1 overflow, 2 empty).  2: unsupported size
 int launch_extreme(long long B, int m_max, int d, const double* A, const double* b, const int* mrows,
                    const unsigned long long* keep, int v_max, double* V, int* count, int* basis, int* status, hipStream_t st);
+// facets of small point sets by enumeration of hyperplanes, one point set per wavefront (plp_hull_enum.hip; d <= 4,
+// n_max <= 64): Ao[B][f_max][d], bo[B][f_max], on[B][f_max], count[B], basis[B][f_max][d] (or nullptr), status[B] (0,
+// 1 overflow, 2 flat).  2: unsupported size
+int launch_hull_enum(long long B, int n_max, int d, const double* X, const int* npts, const unsigned long long* keep, int f_max,
+                     double* Ao, double* bo, unsigned long long* on, int* count, int* basis, int* status, hipStream_t st);
 int launch_reduce_lds(long long B, int m_max, int d, const double* A, const double* b, const int* mrows, double abs_tol,
                       unsigned long long* keep, int* flags, double* r, double* xc, int* nlp, hipStream_t st);
 
