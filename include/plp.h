@@ -317,6 +317,43 @@ int plp_hull_batch_dev(plp_ctx *ctx, void *stream, int64_t B, int n_max, int d, 
                        int32_t *basis, int32_t *status);
 
 /*
+ * Exact volumes and facet areas of B packed polytopes (d <= 4): Lasserre's facet recursion on the rows,
+ * vol_d(P) = (1 / d) sum_i h_i vol_{d-1}(P ^ H_i), taken down to lines where the measure is an interval length; no vertex
+ * list, no LP, no samples.  One polytope per wavefront, the rows read once.
+ * In:  A[B][m_max][d], b[B][m_max], m[B] (NULL = m_max) as for plp_reduce_batch;
+ *      keep[B] (NULL = every row): bit i set = row i is live, the keep word of plp_reduce_batch;
+ *      xc[B][d] (NULL = 0) and scale[B] (NULL = 1): the rule runs on the rows of (P - xc) / scale, on which its tolerances
+ *      are absolute; a point inside the polytope and half the longest side of its bounding box keep them meaningful.
+ * Rule (sequential; the kernel computes exactly these numbers, polytope_amd/csrc/plp_volume_exact.hpp): the live rows
+ *      scaled to unit 2-norm, in row order -- a live zero row with b >= 0 is ignored, with b < 0 (or NaN) the member is
+ *      empty.  A chain of rows (i_1 .. i_k) is the face on which they are tight, with an orthonormal basis of their normals
+ *      and the foot point of the reference point on it.  A row whose normal, projected off the chain's, shrinks by 1e-12 at
+ *      some level is parallel to the face there: more than 1e-9 behind it, the face is empty; on it to 1e-9, facing the same
+ *      way and of lower index than the chain's row of that level, the face belongs to that row and this chain is empty;
+ *      else the row says nothing.  The other rows cut the face; a full chain (d - 1 rows) is a line, cut to an interval.
+ *      Sums over the cutting rows in increasing index.
+ * Out: volume[B]; area[B][m_max] the (d-1)-measure of each row's facet at the row's index, 0 for rows that are not live
+ *      (d = 1: 1 for the lowest-index row at each end; NULL: not written); status[B]:
+ *        PLP_VS_OK         a volume of 0 is the answer for an empty or a flat set;
+ *        PLP_VS_UNBOUNDED  volume = +inf: a face has no end, or no row cuts it (a member without rows included);
+ *        PLP_VS_EMPTY      an infeasible zero row: volume 0, areas 0.
+ *      (PLP_VS_FLAT is set by callers that test for it first, as volume_exact_batch of the Python package does.)
+ * Cost: n^(d-1) chains of n rows each for n live rows -- as plp_extreme_batch at (16, 3), milliseconds per polytope at (64, 4).
+ * 1 <= d <= 4 and m_max <= 64, else PLP_EUNSUPPORTED.  B = 0: returns PLP_OK, nothing runs, no pointer is touched.
+ * The host-pointer form checks A, b, xc and scale for inf / nan when the context asks for it (plp_ctx_set_check_finite).
+ */
+#define PLP_VS_OK 0
+#define PLP_VS_UNBOUNDED 1
+#define PLP_VS_EMPTY 2
+#define PLP_VS_FLAT 3 /* set by callers: empty or not full-dimensional (Chebyshev radius <= abs_tol) */
+int plp_vol_exact_batch(plp_ctx *ctx, int64_t B, int m_max, int d, const double *A, const double *b, const int32_t *m,
+                           const uint64_t *keep, const double *xc, const double *scale, double *volume, double *area,
+                           int32_t *status);
+int plp_vol_exact_batch_dev(plp_ctx *ctx, void *stream, int64_t B, int m_max, int d, const double *A, const double *b,
+                               const int32_t *m, const uint64_t *keep, const double *xc, const double *scale,
+                               double *volume, double *area, int32_t *status);
+
+/*
  * Containment of N points in P polytopes:  all_i( A_p[i,:].x - b_p[i] < abs_tol ).
  * Replaces: Polytope.contains (polytope/polytope.py:206-218), Region.contains (:732-746),
  *           is_inside (:1017-1029), __contains__ (:191-204, :723-730).

@@ -26,7 +26,7 @@ from .polytope import (  # noqa: F401
     is_empty, is_fulldim, is_convex, is_adjacent, is_subset,
     reduce, separate, box2poly,
     cheby_ball, bounding_box, envelope, extreme, qhull,
-    is_inside, union, mldivide, intersect, volume,
+    is_inside, union, mldivide, intersect, volume, volume_exact,
 )
 from .prop2partition import (  # noqa: F401
     Partition, MetricPartition, find_adjacent_regions)
@@ -34,6 +34,7 @@ from . import polytope, prop2partition, quickhull  # noqa: F401,E402  (submodule
 from .batch import (  # noqa: F401
     lpsolve_batch, cheby_ball_batch, bbox_batch, reduce_batch, contains_batch, assign_batch, adjacent_pairs, keep_to_bool,
     verify_careful_lps, lp_histograms, projection_batch, volume_batch, support_batch, subset_batch, extreme_batch, hull_batch,
+    volume_exact_batch,
 )
 
 __version__ = "0.1.0"

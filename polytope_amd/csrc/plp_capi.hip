@@ -941,6 +941,59 @@ int plp_hull_batch(plp_ctx* ctx, int64_t B, int n_max, int d, const double* X, c
     return hc.download();
 }
 
+// ------------------------------------------------------------------------------- exact volume
+namespace {
+int volume_exact_check(plp_ctx* ctx, int64_t B, int m_max, int d, const double* A, const double* b, const double* volume,
+                       const int32_t* status) {
+    if (!ctx) return fail(PLP_EINVAL, "ctx is NULL");
+    if (B < 0 || m_max < 0) return fail(PLP_EINVAL, "bad sizes");
+    if (B == 0) return PLP_OK;
+    if (d < 1 || d > 4 || m_max > plp::MAX_M)
+        return fail(PLP_EUNSUPPORTED, "volume_exact: m_max=%d d=%d outside the kernel (m<=64, 1<=d<=4)", m_max, d);
+    if (B > 2147483647ll) return fail(PLP_EUNSUPPORTED, "volume_exact: B=%lld exceeds 2^31 - 1", (long long)B);
+    if (!volume || !status || (m_max > 0 && (!A || !b))) return fail(PLP_EINVAL, "NULL pointer");
+    return PLP_OK;
+}
+}  // namespace
+
+int plp_vol_exact_batch_dev(plp_ctx* ctx, void* stream, int64_t B, int m_max, int d, const double* A, const double* b,
+                               const int32_t* m, const uint64_t* keep, const double* xc, const double* scale, double* volume,
+                               double* area, int32_t* status) {
+    int rc = volume_exact_check(ctx, B, m_max, d, A, b, volume, status);
+    if (rc || B == 0) return rc;
+    if (plp::launch_volume_exact(B, m_max, d, A, b, m, reinterpret_cast<const unsigned long long*>(keep), xc, scale, volume, area,
+                                 status, (hipStream_t)stream))
+        return fail(PLP_EUNSUPPORTED, "volume_exact: unsupported size");
+    return check_launch("volume_exact_kernel");
+}
+
+int plp_vol_exact_batch(plp_ctx* ctx, int64_t B, int m_max, int d, const double* A, const double* b, const int32_t* m,
+                           const uint64_t* keep, const double* xc, const double* scale, double* volume, double* area,
+                           int32_t* status) {
+    int rc = volume_exact_check(ctx, B, m_max, d, A, b, volume, status);
+    if (rc || B == 0) return rc;
+    double *dA, *db, *dxc, *dscale, *dvol, *darea;
+    int32_t *dm, *dst;
+    uint64_t* dkeep;
+    HostCall hc(ctx);
+    hc.in(dA, A, (size_t)B * m_max * d, 0, true);
+    hc.in(db, b, (size_t)B * m_max, 0, true);
+    hc.in(dm, m, B);
+    hc.in(dkeep, keep, B);
+    hc.in(dxc, xc, (size_t)B * d, 0, true);
+    hc.in(dscale, scale, B, 0, true);
+    hc.out(dvol, volume, B);
+    hc.out(darea, area, area ? (size_t)B * m_max : 0);
+    hc.out(dst, status, B);
+    rc = hc.reserve();
+    if (rc) return rc;
+    rc = hc.upload();
+    if (rc) return rc;
+    rc = plp_vol_exact_batch_dev(ctx, hc.st, B, m_max, d, dA, db, dm, dkeep, dxc, dscale, dvol, area ? darea : nullptr, dst);
+    if (rc) return rc;
+    return hc.download();
+}
+
 }  // extern "C"
 
 struct plp_hull {

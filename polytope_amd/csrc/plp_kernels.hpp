@@ -71,6 +71,12 @@ int launch_extreme(long long B, int m_max, int d, const double* A, const double*
 // 1 overflow, 2 flat).  2: unsupported size
 int launch_hull_enum(long long B, int n_max, int d, const double* X, const int* npts, const unsigned long long* keep, int f_max,
                      double* Ao, double* bo, unsigned long long* on, int* count, int* basis, int* status, hipStream_t st);
+// exact volumes and facet areas of small polytopes by Lasserre's facet recursion, one polytope per wavefront
+// (plp_volume_exact.hip; d <= 4, m_max <= 64): volume[B], area[B][m_max] (or nullptr), status[B] (0, 1 unbounded, 2 empty);
+// keep, xc[B][d], scale[B] may be nullptr.  2: unsupported size
+int launch_volume_exact(long long B, int m_max, int d, const double* A, const double* b, const int* mrows,
+                        const unsigned long long* keep, const double* xc, const double* scale, double* volume, double* area,
+                        int* status, hipStream_t st);
 int launch_reduce_lds(long long B, int m_max, int d, const double* A, const double* b, const int* mrows, double abs_tol,
                       unsigned long long* keep, int* flags, double* r, double* xc, int* nlp, hipStream_t st);
 

@@ -1968,6 +1968,21 @@ def volume(polyreg, nsamples=None, seed=None):
     return vol
 
 
+def volume_exact(poly):
+    """The exact volume of one Polytope of dimension <= 4 and at most 64 rows, as a float (polytope_amd.batch.
+    volume_exact_batch with reduce=True: 0.0 for an empty or flat polytope, inf for an unbounded one).  Deterministic, and
+    apart from `volume`: the cached `poly.volume` (the Monte-Carlo estimate) is neither read nor set.  A Region raises: its
+    members may overlap, so their volumes do not add up to the Region's."""
+    if isinstance(poly, Region):
+        raise Exception("volume_exact: not executable for regions (their members may overlap)")
+    from . import batch
+    A = np.asarray(poly.A, dtype=float)
+    if A.ndim != 2 or A.shape[0] == 0:
+        return 0.0   # (the empty Polytope())
+    res = batch.volume_exact_batch(A[np.newaxis], np.asarray(poly.b, dtype=float).reshape(1, -1), areas=False)
+    return float(res["volume"][0])
+
+
 # ====================================================================================== adjacency
 def _adjacency_stack(poly1, poly2, overlap, abs_tol):
     """The slightly inflated stacked polytope whose full-dimensionality decides adjacency
