@@ -367,6 +367,58 @@ int plp_contains_dev(plp_ctx *ctx, void *stream, int P, int m_max, int d, const 
                      const int32_t *m, int64_t N, const double *X, double abs_tol, int mode, uint8_t *out);
 
 /*
+ * Point location: for each of N points the FIRST of P polytopes that contains it, and optionally how many do.
+ * No counterpart in the reference, whose users loop `x in region` over a partition one point at a time.
+ * In:  A[P][m_max][d], b[P][m_max], m[P] (NULL = m_max), X[d][N] and abs_tol exactly as plp_contains takes them.
+ * Out: first[N] = min { p : all_{i < m[p]} (fl(A_p[i].x) - b_p[i]) < abs_tol }  or -1, the dot product in
+ *      plp_contains' arithmetic (s = a0 x0; s = fma(a_k, x_k, s), k ascending): first[q] is the arg-max over p of
+ *      plp_contains' mode-1 matrix wherever column q holds a 1;
+ *      count[N] (NULL: not computed, and the search for a point stops at its first hit) = the number of such p.
+ *      A polytope with m[p] = 0 contains every point (NaN points too); a point with a NaN coordinate is in no polytope
+ *      that has a row.
+ * grid == NULL: every polytope is tested against every point (wave-uniform rows, as plp_contains).
+ * grid != NULL (a HOST pointer in both forms): a uniform grid over up to PLP_LOCATE_MAX_AXES coordinate axes culls the
+ *      candidates.  Axis j of the grid is coordinate axis[j], cut into res[j] cells of width 1 / inv_h[j] from lo[j] on;
+ *      cell_j(x) = (int) fmin(fmax(floor((x - lo[j]) * inv_h[j]), 0), res[j] - 1), NaN -> 0; the flat cell number is
+ *      row-major over j.  G = prod res[j] <= PLP_LOCATE_MAX_CELLS.  cell_start[G + 1] and cell_items[cell_start[G]] are
+ *      the lists plp_locate_grid_count / _fill build: cell c holds polytopes cell_items[cell_start[c] .. cell_start[c + 1]),
+ *      ascending.  The answer equals the dense one provided every polytope is listed in the cell of every point it contains.
+ * plp_locate_grid_count: a polytope is listed in the cells [cell_j(lb_j - pad'), cell_j(ub_j + pad')] of its box
+ *      lb[P][d], ub[P][d] (pad' = pad * max(1, the box's largest finite |bound| on any axis); +-inf sides and NaN bounds span the axis; lb_j - pad' > ub_j + pad'
+ *      on a gridded axis -- e.g. lb = +inf, ub = -inf -- lists it nowhere).  Writes the exclusive prefix sums of the list
+ *      lengths to cell_start[G + 1] (saturating at 2^31 - 1) and the longest list's length to max_len[1].
+ * plp_locate_grid_fill: with that cell_start, writes cell_items (cell_start[G] entries, every list sorted ascending, so
+ *      the result is deterministic); cursor[G] is scratch.
+ * Errors, as plp_contains: negative sizes, d < 1, a bad grid descriptor: PLP_EINVAL "bad sizes"; NULL first / X / lists:
+ *      PLP_EINVAL "NULL pointer"; d > 16: PLP_EUNSUPPORTED.  N = 0 returns at once; P = 0 writes first = -1, count = 0.
+ */
+#define PLP_LOCATE_MAX_AXES 3
+#define PLP_LOCATE_MAX_CELLS (1 << 18)
+typedef struct plp_locate_grid {
+    int32_t naxes;                      /* 1 .. PLP_LOCATE_MAX_AXES */
+    int32_t axis[PLP_LOCATE_MAX_AXES];  /* distinct coordinate axes, each < d */
+    int32_t res[PLP_LOCATE_MAX_AXES];   /* cells along each, >= 1 */
+    int32_t reserved;
+    double lo[PLP_LOCATE_MAX_AXES];     /* lower end of cell 0 */
+    double inv_h[PLP_LOCATE_MAX_AXES];  /* 1 / cell width, >= 0 (0: one cell) */
+} plp_locate_grid;
+int plp_locate(plp_ctx *ctx, int P, int m_max, int d, const double *A, const double *b, const int32_t *m, int64_t N,
+               const double *X, double abs_tol, const plp_locate_grid *grid, const int32_t *cell_start,
+               const int32_t *cell_items, int32_t *first, int32_t *count);
+int plp_locate_dev(plp_ctx *ctx, void *stream, int P, int m_max, int d, const double *A, const double *b,
+                   const int32_t *m, int64_t N, const double *X, double abs_tol, const plp_locate_grid *grid,
+                   const int32_t *cell_start, const int32_t *cell_items, int32_t *first, int32_t *count);
+int plp_locate_grid_count(plp_ctx *ctx, int P, int d, const double *lb, const double *ub, double pad,
+                          const plp_locate_grid *grid, int32_t *cell_start, int32_t *max_len);
+int plp_locate_grid_count_dev(plp_ctx *ctx, void *stream, int P, int d, const double *lb, const double *ub, double pad,
+                              const plp_locate_grid *grid, int32_t *cell_start, int32_t *max_len);
+int plp_locate_grid_fill(plp_ctx *ctx, int P, int d, const double *lb, const double *ub, double pad,
+                         const plp_locate_grid *grid, const int32_t *cell_start, int32_t *cursor, int32_t *cell_items);
+int plp_locate_grid_fill_dev(plp_ctx *ctx, void *stream, int P, int d, const double *lb, const double *ub, double pad,
+                             const plp_locate_grid *grid, const int32_t *cell_start, int32_t *cursor,
+                             int32_t *cell_items);
+
+/*
  * quickhull outside-set assignment and furthest point.
  * Replaces: distance() (polytope/quickhull.py:117-121), the assignment loops (:224-245,
  *           :311-336: a point goes to the FIRST facet with distance > abs_tol) and

@@ -65,6 +65,13 @@ SIGNATURES = {
     "plp_vol_exact_batch_dev": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "plp_contains": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int64, _vp, C.c_double, C.c_int, _vp]),
     "plp_contains_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int64, _vp, C.c_double, C.c_int, _vp]),
+    "plp_locate": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int64, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp]),
+    "plp_locate_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int64, _vp, C.c_double, _vp, _vp, _vp,
+                                 _vp, _vp]),
+    "plp_locate_grid_count": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, C.c_double, _vp, _vp, _vp]),
+    "plp_locate_grid_count_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_double, _vp, _vp, _vp]),
+    "plp_locate_grid_fill": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp]),
+    "plp_locate_grid_fill_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp]),
     "plp_assign": (C.c_int, [_vp, C.c_int64, C.c_int, _vp, C.c_int, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp]),
     "plp_assign_dev": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, C.c_int, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp]),
     "plp_hull_create": (C.c_int, [_vp, C.c_int64, C.c_int, _vp, C.POINTER(_vp)]),
@@ -95,6 +102,13 @@ SIGNATURES = {
     "plp_quickhull_last_error": (C.c_char_p, []),
     "plp_selftest": (C.c_int, [_vp, C.c_int, _vp, _vp]),
 }
+
+
+class LocateGridDesc(C.Structure):
+    """plp_locate_grid of include/plp.h (always a host pointer)."""
+    _fields_ = [("naxes", C.c_int32), ("axis", C.c_int32 * 3), ("res", C.c_int32 * 3), ("reserved", C.c_int32),
+                ("lo", C.c_double * 3), ("inv_h", C.c_double * 3)]
+
 
 _lib = None
 _lock = threading.Lock()

@@ -292,6 +292,243 @@ def contains_batch(A, b, X, abs_tol=1e-7, m=None, region=True):
     return out
 
 
+# ------------------------------------------------------------------------------------- point location
+# Relative pad of a polytope's box before it is cut into cells: max(1e-9, 1000 x the worst excess of a dense-accepted point
+# beyond the oracle's box of the normalised relaxed rows over the soak families) -- DESIGN 4.15 has the measurement
+# (scripts/measure_locate_pad.py: worst 3.16e-12, in the `dup` family; at the rounding level, <= 2e-16, in the others).
+_LOCATE_PAD = 3.2e-9
+_LOCATE_MAX_CELLS = 1 << 18    # include/plp.h: PLP_LOCATE_MAX_CELLS
+_LOCATE_MAX_ITEMS = 1 << 24    # entries of cell_items beyond which a grid is declined
+_LOCATE_MAX_LIST = 1024        # ... and the longest single list
+_LOCATE_MAX_RES = 4096         # cells along one axis
+# grid="auto": dense below this many polytopes.  Measured (P sweep at N = 2^20, square cells in d = 2, grid build
+# included): dense 0.31 / 1.19 ms at P = 256 / 1024 against 0.70 / 0.65 ms -- the crossing is near P = 600.
+_LOCATE_AUTO_P = 600
+
+
+class _HostStruct(object):
+    """A ctypes structure as an argument of _Backend.call: a host pointer on either backend."""
+
+    def __init__(self, obj):
+        self.obj = obj
+        self.data = C.addressof(obj)
+        self.ctypes = self
+
+    def data_ptr(self):
+        return self.data
+
+
+class LocateGrid(object):
+    """What locate_grid builds for one packed table and one abs_tol: kind "grid" with the descriptor (axes, lo, inv_h, res)
+    and the cell lists cell_start int32[G + 1], cell_items int32[n_items] (numpy, or resident CUDA tensors), or kind
+    "dense" -- the grid was declined (`reason` says why) and locate_batch runs the dense kernel."""
+
+    def __init__(self, kind, abs_tol, shape, desc=None, cell_start=None, cell_items=None, n_items=0, max_list=0,
+                 pad=_LOCATE_PAD, reason=""):
+        self.kind, self.abs_tol, self.shape = kind, float(abs_tol), tuple(int(v) for v in shape)
+        self.desc, self.cell_start, self.cell_items = desc, cell_start, cell_items
+        self.n_items, self.max_list, self.pad, self.reason = int(n_items), int(max_list), float(pad), reason
+
+    @property
+    def axes(self):
+        return [] if self.desc is None else [int(self.desc.axis[j]) for j in range(self.desc.naxes)]
+
+    @property
+    def res(self):
+        return [] if self.desc is None else [int(self.desc.res[j]) for j in range(self.desc.naxes)]
+
+    @property
+    def cells(self):
+        return int(np.prod(self.res)) if self.desc is not None else 0
+
+    def __repr__(self):
+        if self.kind != "grid":
+            return "LocateGrid(dense: %s)" % self.reason
+        return "LocateGrid(axes=%s, res=%s, items=%d, longest list=%d)" % (self.axes, self.res, self.n_items, self.max_list)
+
+
+def _locate_axes(P, dom_lo, dom_hi, wsum, nfin, d):
+    """The gridded axes and their resolutions from per-axis statistics of the boxes (host scalars): over the polytopes whose
+    box is finite on axis k, dom_lo / dom_hi = the extent of the boxes, wsum = the sum of their widths, nfin = how many.
+    A cell is about as wide as the mean box; the min(d, 3) axes along which a polytope covers the smallest share of the
+    cells are taken; the product of the resolutions is capped at max(64, 8 P) and 2^18.  -> [(axis, lo, inv_h, res)]"""
+    cand = []
+    for k in range(d):
+        ext = dom_hi[k] - dom_lo[k]
+        if not (nfin[k] > 0 and np.isfinite(ext) and ext > 0):
+            continue
+        wmean = wsum[k] / nfin[k]
+        res = int(min(_LOCATE_MAX_RES, max(1.0, np.floor(ext / max(wmean, ext / _LOCATE_MAX_RES) + 0.5))))
+        if res < 2:
+            continue
+        cover = (nfin[k] * min(1.0, wmean / ext + 1.0 / res) + (P - nfin[k])) / float(P)
+        cand.append((cover, k, float(dom_lo[k]), float(ext), res))
+    cand.sort()
+    cand = cand[:min(d, 3)]
+    if not cand:
+        return []
+    # cell 0 starts half a cell below the boxes: a tiling whose cells line up with the grid's would otherwise touch three
+    # cells per axis (its own and, by the relaxation and the pad, both neighbours) instead of two
+    cap = min(_LOCATE_MAX_CELLS, max(64, 8 * P))
+    res = [c[4] for c in cand]
+    while int(np.prod([r + 1 for r in res])) > cap:
+        j = int(np.argmax(res))
+        res[j] = max(1, res[j] * 3 // 4)
+    return [(k, lo - 0.5 * ext / r, r / ext, r + 1) for (_, k, lo, ext, _), r in zip(cand, res)]
+
+
+def _locate_rows(be, A, b, m, abs_tol):
+    """The relaxed, normalised rows of locate_grid on the backend of A -> An, bn (vacuous, unusable and padding rows become
+    0 . x <= 1), every[P] (no box to be had from these rows: listed everywhere), nowhere[P] (contains nothing)."""
+    tor = be.torch
+    xp = tor if tor is not None else np
+    kw = {} if tor is None else {"device": be.device}
+    P, m_max = int(A.shape[0]), int(A.shape[1])
+    with np.errstate(all="ignore"):
+        rows = (xp.arange(m_max, **kw)[None, :] < m[:, None]) if m is not None else \
+            xp.ones((P, m_max), dtype=(bool if tor is None else tor.bool), **kw)
+        nrm = xp.sqrt((A * A).sum(-1))
+        br = b + abs_tol
+        zero = rows & (A == 0).all(-1)
+        bad = rows & ~zero & ~(xp.isfinite(nrm) & (nrm > 0) & xp.isfinite(br))
+        nowhere = (zero & ~(br > 0)).any(-1)
+        use = rows & ~zero & ~bad
+        one = xp.ones_like(nrm)
+        safe = xp.where(use, nrm, one)
+        An = xp.where(use[:, :, None], A / safe[:, :, None], xp.zeros_like(A))
+        bn = xp.where(use, br / safe, one)
+        every = bad.any(-1) | ~use.any(-1)
+    return An, bn, every, nowhere
+
+
+def _locate_boxes(be, lb, ub, every, nowhere):
+    """The boxes the grid is built from: (-inf, inf) where `every`, (inf, -inf) where `nowhere`; and the statistics that
+    pick the axes, on the host (one read-back): st[0] / st[1] the extent of the finite boxes per axis, st[2] the sum of
+    their widths, st[3] their number, st[4] the number of polytopes listed everywhere."""
+    tor = be.torch
+    xp = tor if tor is not None else np
+    inf = float("inf")
+    with np.errstate(all="ignore"):
+        lb = xp.where(every[:, None], xp.full_like(lb, -inf), lb)
+        ub = xp.where(every[:, None], xp.full_like(ub, inf), ub)
+        lb = xp.where(nowhere[:, None], xp.full_like(lb, inf), lb)
+        ub = xp.where(nowhere[:, None], xp.full_like(ub, -inf), ub)
+        lb, ub = (lb.contiguous(), ub.contiguous()) if tor is not None else (np.ascontiguousarray(lb), np.ascontiguousarray(ub))
+        fin = xp.isfinite(lb) & xp.isfinite(ub)
+        zeros = xp.zeros_like(lb)
+        amin, amax = (lambda t: t.amin(0), lambda t: t.amax(0)) if tor is not None else (lambda t: t.min(0), lambda t: t.max(0))
+        f64 = (lambda t: t.to(tor.float64)) if tor is not None else (lambda t: t.astype(np.float64))
+        st = xp.stack([amin(xp.where(fin, lb, xp.full_like(lb, inf))), amax(xp.where(fin, ub, xp.full_like(ub, -inf))),
+                       xp.where(fin, ub - lb, zeros).sum(0), f64(fin.sum(0)), zeros[0] + f64((every & ~nowhere).sum())])
+        st = st.cpu().numpy() if tor is not None else st
+    return lb, ub, st
+
+
+def _locate_desc(P, d, st):
+    """The grid descriptor for the statistics of _locate_boxes -> (LocateGridDesc, axes) or (None, [])."""
+    axes = _locate_axes(P, st[0], st[1], st[2], st[3], d)
+    if not axes:
+        return None, []
+    desc = _lib.LocateGridDesc()
+    desc.naxes = len(axes)
+    for j, (k, lo, inv_h, res) in enumerate(axes):
+        desc.axis[j], desc.lo[j], desc.inv_h[j], desc.res[j] = k, lo, inv_h, res
+    for j in range(len(axes), 3):
+        desc.res[j] = 1
+    return desc, axes
+
+
+def locate_grid(A, b, m=None, abs_tol=1e-7, max_items=_LOCATE_MAX_ITEMS, max_list=_LOCATE_MAX_LIST):
+    """The culling grid of locate_batch for the packed table A[P, m_max, d], b[P, m_max], m[P] and this abs_tol.
+
+    Every row is relaxed and normalised -- a_i / |a_i|, (b_i + abs_tol) / |a_i| -- and bbox_batch boxes the result; a
+    polytope is listed in the cells its box (padded by 3.2e-9 of its largest coordinate, at least 1) reaches on up to three gridded axes.  A zero row
+    with b_i + abs_tol > 0 is vacuous; a zero row otherwise means the polytope contains nothing (0 - b_i < abs_tol is
+    false) and it is listed nowhere.  A polytope is listed in EVERY cell when its box is not to be had: bbox_batch status
+    != 0, no rows, a row with inf / nan or a norm that under- or overflows.  Infinite sides span their axis.
+    Declined -- kind "dense", nothing raised -- when the table has more than 64 rows per polytope (bbox_batch's limit;
+    the dense kernel has none), when no axis separates the boxes, the lists would hold more than
+    `max_items` entries or one of them more than `max_list`.
+    numpy in: numpy lists; CUDA tensors in: resident tensors built on torch's current stream (two small read-backs: the
+    box statistics that pick the axes, and the size of cell_items)."""
+    be = _Backend(A)
+    A, b, m, (P, m_max, d) = _packed(be, A, b, m)
+    if d < 1 or d > MAX_D:
+        raise _lib.UnsupportedSize("locate_grid: d=%d outside 1..%d" % (d, MAX_D))
+    abs_tol = float(abs_tol)
+
+    def dense(reason):
+        return LocateGrid("dense", abs_tol, (P, m_max, d), reason=reason)
+    if P == 0 or m_max == 0:
+        return dense("no rows")
+    if m_max > MAX_M:   # (the dense kernel, like contains_batch, has no row limit; the boxes have)
+        return dense("m_max=%d: bbox_batch boxes polytopes of up to %d rows" % (m_max, MAX_M))
+    An, bn, every, nowhere = _locate_rows(be, A, b, m, abs_tol)
+    box = bbox_batch(An, bn, m)
+    lb, ub, st = _locate_boxes(be, box["lb"], box["ub"], every | (box["status"] != 0), nowhere)
+    if st[4, 0] > max_list:
+        return dense("%d polytopes without a usable box: every list would exceed %d" % (int(st[4, 0]), max_list))
+    desc, axes = _locate_desc(P, d, st)
+    if desc is None:
+        return dense("no axis along which the boxes are narrower than their common extent")
+    G = int(np.prod([a[3] for a in axes]))
+    hs = _HostStruct(desc)
+    cell_start = be.out((G + 1,), np.int32, zero=True)
+    max_len = be.out((1,), np.int32, zero=True)
+    be.call("plp_locate_grid_count", P, d, lb, ub, _LOCATE_PAD, hs, cell_start, max_len, h2d=(lb, ub))
+    if be.torch is not None:
+        n_items, longest = (int(v) for v in be.torch.stack([cell_start[G], max_len[0]]).cpu())
+    else:
+        n_items, longest = int(cell_start[G]), int(max_len[0])
+    if n_items > max_items or longest > max_list:
+        return dense("%d list entries (budget %d), longest list %d (cap %d)" % (n_items, max_items, longest, max_list))
+    cell_items = be.out((n_items,), np.int32, zero=True)
+    cursor = be.out((G,), np.int32, zero=True)
+    be.call("plp_locate_grid_fill", P, d, lb, ub, _LOCATE_PAD, hs, cell_start, cursor, cell_items, h2d=(lb, ub, cell_start))
+    return LocateGrid("grid", abs_tol, (P, m_max, d), desc, cell_start, cell_items, n_items, longest)
+
+
+def locate_batch(A, b, X, abs_tol=1e-7, m=None, count=False, grid="auto"):
+    """For each of the N column vectors X[d, N] the index of the FIRST of the P packed polytopes that contains it, or -1
+    (no counterpart in the reference; TuLiP's find_discrete_state loops `x in region`).
+
+    -> first int32[N], or (first, count int32[N]) with count=True: how many polytopes contain the point.
+    The dense answer is the definition: first[q] = min { p : all_{i < m[p]} (fl(A_p[i] . x_q) - b_p[i]) < abs_tol } in
+    contains_batch's arithmetic, i.e. the arg-max over p of contains_batch(..., region=False) wherever a column holds a 1.
+    A polytope with m[p] == 0 contains every point (NaN points too); a NaN coordinate is in no polytope that has a row.
+    grid: None -- every polytope against every point; a LocateGrid from locate_grid (same table shape and abs_tol, else
+    ValueError) -- candidates from the point's cell only; "auto" -- dense below 600 polytopes (the measured crossing at
+    N = 2^20), else a grid built for this call.  A declined grid (kind "dense") runs the dense kernel."""
+    be = _Backend(X)
+    A, b, m, (P, m_max, d) = _packed(be, A, b, m)
+    X = be.arr(X)
+    if len(X.shape) != 2 or X.shape[0] != d:
+        raise ValueError("points should be column vectors")
+    N = int(X.shape[1])
+    abs_tol = float(abs_tol)
+    if isinstance(grid, LocateGrid):
+        if grid.abs_tol != abs_tol or grid.shape != (P, m_max, d):
+            raise ValueError("locate_batch: the LocateGrid was built for abs_tol=%r and a table of shape %s, not abs_tol=%r "
+                             "and %s" % (grid.abs_tol, list(grid.shape), abs_tol, [P, m_max, d]))
+        if grid.kind == "grid" and _is_torch(grid.cell_start) != (be.torch is not None):
+            raise ValueError("locate_batch: the LocateGrid's lists and the points must both be numpy arrays or both CUDA tensors")
+    elif grid is not None and not (isinstance(grid, str) and grid == "auto"):
+        raise ValueError("grid must be 'auto', None or a LocateGrid")
+    first = be.out((N,), np.int32, zero=True)
+    cnt = be.out((N,), np.int32, zero=True) if count else None
+    if N == 0:
+        return (first, cnt) if count else first
+    if isinstance(grid, str):
+        grid = locate_grid(A, b, m, abs_tol) if P >= _LOCATE_AUTO_P else None
+    if grid is not None and grid.kind == "grid":
+        args = (_HostStruct(grid.desc), grid.cell_start, grid.cell_items if grid.n_items else None)
+        h2d = (A, b, m, X, grid.cell_start, grid.cell_items)
+    else:
+        args, h2d = (None, None, None), (A, b, m, X)
+    be.call("plp_locate", P, m_max, d, A, b, m, N, X, abs_tol, *args, first, cnt, h2d=h2d)
+    return (first, cnt) if count else first
+
+
 # flags of volume_batch (include/plp.h: PLP_VF_*)
 VF_NONFINITE, VF_NOROWS = 1, 2
 _VOLUME_MAX_N = 2 ** 31 - 1

@@ -2,6 +2,7 @@
 // Host-pointer entry points stage through a grow-only device scratch arena owned by the
 // context, call the *_dev entry point on the context's stream and synchronise.
 #include "plp_hostcall.hpp"
+#include "plp_locate.hpp"
 
 namespace {
 
@@ -560,6 +561,147 @@ int plp_contains(plp_ctx* ctx, int P, int m_max, int d, const double* A, const d
     rc = hc.upload();
     if (rc) return rc;
     rc = plp_contains_dev(ctx, hc.st, P, m_max, d, dA, db, dm, N, dX, abs_tol, mode, dout);
+    if (rc) return rc;
+    return hc.download();
+}
+
+// ------------------------------------------------------------------------------- locate
+namespace {
+int grid_cells(const plp_locate_grid* g) {
+    int G = 1;
+    for (int j = 0; j < g->naxes; ++j) G *= g->res[j];
+    return G;
+}
+
+int check_locate(plp_ctx* ctx, int P, int m_max, int d, const double* A, const double* b, int64_t N, const double* X,
+                 const plp_locate_grid* grid, const int32_t* cell_start, const int32_t* cell_items, const int32_t* first) {
+    if (!ctx) return fail(PLP_EINVAL, "ctx is NULL");
+    if (P < 0 || m_max < 0 || d < 1 || N < 0) return fail(PLP_EINVAL, "bad sizes");
+    if (N == 0) return PLP_OK;
+    if (!X || !first || ((!A || !b) && P > 0 && m_max > 0)) return fail(PLP_EINVAL, "NULL pointer");
+    if (d > plp::MAX_D) return fail(PLP_EUNSUPPORTED, "d=%d > 16", d);
+    if (grid && P > 0 && !cell_start) return fail(PLP_EINVAL, "NULL pointer");
+    (void)cell_items;  // (may be NULL: a grid without a single entry)
+    return PLP_OK;
+}
+
+int check_locate_grid(plp_ctx* ctx, int P, int d, const double* lb, const double* ub, double pad, const plp_locate_grid* grid,
+                      const int32_t* cell_start, const void* other) {
+    if (!ctx) return fail(PLP_EINVAL, "ctx is NULL");
+    if (P < 0 || d < 1 || !(pad >= 0.0)) return fail(PLP_EINVAL, "bad sizes");
+    if (!grid || !cell_start || !other || (P > 0 && (!lb || !ub))) return fail(PLP_EINVAL, "NULL pointer");
+    if (d > plp::MAX_D) return fail(PLP_EUNSUPPORTED, "d=%d > 16", d);
+    return PLP_OK;
+}
+}  // namespace
+
+int plp_locate_dev(plp_ctx* ctx, void* stream, int P, int m_max, int d, const double* A, const double* b, const int32_t* m,
+                   int64_t N, const double* X, double abs_tol, const plp_locate_grid* grid, const int32_t* cell_start,
+                   const int32_t* cell_items, int32_t* first, int32_t* count) {
+    int rc = check_locate(ctx, P, m_max, d, A, b, N, X, grid, cell_start, cell_items, first);
+    if (rc || N == 0) return rc;
+    if (plp::launch_locate(P, m_max, d, A, b, m, N, X, abs_tol, grid, cell_start, cell_items, first, count, (hipStream_t)stream))
+        return fail(PLP_EINVAL, "bad sizes (locate: grid descriptor)");
+    return check_launch("locate_kernel");
+}
+
+int plp_locate(plp_ctx* ctx, int P, int m_max, int d, const double* A, const double* b, const int32_t* m, int64_t N,
+               const double* X, double abs_tol, const plp_locate_grid* grid, const int32_t* cell_start,
+               const int32_t* cell_items, int32_t* first, int32_t* count) {
+    int rc = check_locate(ctx, P, m_max, d, A, b, N, X, grid, cell_start, cell_items, first);
+    if (rc || N == 0) return rc;
+    if (grid && plp::loc::grid_bad(*grid, d))
+        return fail(PLP_EINVAL, "bad sizes (locate: grid descriptor)");  // (before cell_start[G] is read)
+    const bool lists = grid && P > 0;
+    const size_t G = lists ? (size_t)grid_cells(grid) : 0;
+    const size_t items = lists ? (size_t)(cell_start[G] < 0 ? 0 : cell_start[G]) : 0;
+    double *dA, *db, *dX;
+    int32_t *dm, *dcs, *dci, *dfirst, *dcount;
+    HostCall hc(ctx);
+    hc.in(dA, A, (size_t)P * m_max * d);
+    hc.in(db, b, (size_t)P * m_max);
+    hc.in(dm, m, P);
+    hc.in(dX, X, (size_t)N * d);
+    hc.in(dcs, lists ? cell_start : nullptr, G + 1);
+    hc.in(dci, lists && items ? cell_items : nullptr, items);
+    hc.out(dfirst, first, (size_t)N);
+    hc.out(dcount, count, count ? (size_t)N : 0);
+    hc.direct_out = true;
+    rc = hc.reserve();
+    if (rc) return rc;
+    rc = hc.upload();
+    if (rc) return rc;
+    rc = plp_locate_dev(ctx, hc.st, P, m_max, d, dA, db, dm, N, dX, abs_tol, grid, dcs, dci, dfirst, count ? dcount : nullptr);
+    if (rc) return rc;
+    return hc.download();
+}
+
+int plp_locate_grid_count_dev(plp_ctx* ctx, void* stream, int P, int d, const double* lb, const double* ub, double pad,
+                              const plp_locate_grid* grid, int32_t* cell_start, int32_t* max_len) {
+    int rc = check_locate_grid(ctx, P, d, lb, ub, pad, grid, cell_start, max_len);
+    if (rc) return rc;
+    const int lr_count = plp::launch_locate_grid_count(P, d, lb, ub, pad, grid, cell_start, max_len, (hipStream_t)stream);
+    if (lr_count == 3) return fail(PLP_EHIP, "locate grid: hipMemsetAsync failed");
+    if (lr_count) return fail(PLP_EINVAL, "bad sizes (locate: grid descriptor)");
+    return check_launch("locate_grid_count_kernel");
+}
+
+int plp_locate_grid_count(plp_ctx* ctx, int P, int d, const double* lb, const double* ub, double pad,
+                          const plp_locate_grid* grid, int32_t* cell_start, int32_t* max_len) {
+    int rc = check_locate_grid(ctx, P, d, lb, ub, pad, grid, cell_start, max_len);
+    if (rc) return rc;
+    if (plp::loc::grid_bad(*grid, d))
+        return fail(PLP_EINVAL, "bad sizes (locate: grid descriptor)");
+    double *dlb, *dub;
+    int32_t *dcs, *dml;
+    HostCall hc(ctx);
+    hc.in(dlb, lb, (size_t)P * d);
+    hc.in(dub, ub, (size_t)P * d);
+    hc.out(dcs, cell_start, (size_t)grid_cells(grid) + 1);
+    hc.out(dml, max_len, 1);
+    rc = hc.reserve();
+    if (rc) return rc;
+    rc = hc.upload();
+    if (rc) return rc;
+    rc = plp_locate_grid_count_dev(ctx, hc.st, P, d, dlb, dub, pad, grid, dcs, dml);
+    if (rc) return rc;
+    return hc.download();
+}
+
+int plp_locate_grid_fill_dev(plp_ctx* ctx, void* stream, int P, int d, const double* lb, const double* ub, double pad,
+                             const plp_locate_grid* grid, const int32_t* cell_start, int32_t* cursor, int32_t* cell_items) {
+    int rc = check_locate_grid(ctx, P, d, lb, ub, pad, grid, cell_start, cursor);
+    if (rc) return rc;
+    const int lr_fill = plp::launch_locate_grid_fill(P, d, lb, ub, pad, grid, cell_start, cursor, cell_items, (hipStream_t)stream);
+    if (lr_fill == 3) return fail(PLP_EHIP, "locate grid: hipMemsetAsync failed");
+    if (lr_fill) return fail(PLP_EINVAL, "bad sizes (locate: grid descriptor)");
+    return check_launch("locate_grid_fill_kernel");
+}
+
+// (host-pointer form: cursor may be NULL -- the scratch lives in the arena either way)
+int plp_locate_grid_fill(plp_ctx* ctx, int P, int d, const double* lb, const double* ub, double pad,
+                         const plp_locate_grid* grid, const int32_t* cell_start, int32_t* cursor, int32_t* cell_items) {
+    int rc = check_locate_grid(ctx, P, d, lb, ub, pad, grid, cell_start, grid);
+    if (rc) return rc;
+    if (plp::loc::grid_bad(*grid, d))
+        return fail(PLP_EINVAL, "bad sizes (locate: grid descriptor)");
+    const size_t G = (size_t)grid_cells(grid);
+    const size_t items = (size_t)(cell_start[G] < 0 ? 0 : cell_start[G]);
+    if (items && !cell_items) return fail(PLP_EINVAL, "NULL pointer");
+    double *dlb, *dub;
+    int32_t *dcs, *dcur, *dci;
+    HostCall hc(ctx);
+    hc.in(dlb, lb, (size_t)P * d);
+    hc.in(dub, ub, (size_t)P * d);
+    hc.in(dcs, cell_start, G + 1);
+    hc.out(dcur, (int32_t*)nullptr, G);
+    hc.out(dci, cell_items, items);
+    (void)cursor;
+    rc = hc.reserve();
+    if (rc) return rc;
+    rc = hc.upload();
+    if (rc) return rc;
+    rc = plp_locate_grid_fill_dev(ctx, hc.st, P, d, dlb, dub, pad, grid, dcs, dcur, dci);
     if (rc) return rc;
     return hc.download();
 }

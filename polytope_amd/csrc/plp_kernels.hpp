@@ -3,6 +3,8 @@
 #pragma once
 #include "plp_common.hpp"
 
+struct plp_locate_grid;  // include/plp.h
+
 namespace plp {
 
 // lanes per LP group for polytopes with up to m_max rows (-1: unsupported)
@@ -157,6 +159,20 @@ int launch_reduce(int d, const ReduceArgs& a, int phase, hipStream_t st);
 int launch_contains(int P, int m_max, int d, const double* A, const double* b, const int* mrows, long long N,
                     const double* X, double abs_tol, int mode, unsigned char* out, void* scratch, hipStream_t st);
 size_t contains_scratch_bytes(int P, int m_max);
+
+// point location (plp_locate.hip): first[N] = the first polytope containing each point or -1, count[N] (or nullptr) how
+// many do; grid == nullptr: every polytope against every point, else the cell lists cell_start / cell_items of the grid.
+// The grid descriptors are host pointers (passed to the kernels by value).  2: unsupported size or a bad descriptor;
+// 3 (count / fill): clearing the counters failed (a HIP error)
+int launch_locate(int P, int m_max, int d, const double* A, const double* b, const int* mrows, long long N, const double* X,
+                  double abs_tol, const plp_locate_grid* grid, const int* cell_start, const int* cell_items, int* first,
+                  int* count, hipStream_t st);
+// cell_start[G + 1]: exclusive prefix sums of the cells' list lengths, max_len[1]: the longest list
+int launch_locate_grid_count(int P, int d, const double* lb, const double* ub, double pad, const plp_locate_grid* grid,
+                             int* cell_start, int* max_len, hipStream_t st);
+// cell_items[cell_start[G]], every list ascending; cursor[G]: scratch
+int launch_locate_grid_fill(int P, int d, const double* lb, const double* ub, double pad, const plp_locate_grid* grid,
+                            const int* cell_start, int* cursor, int* cell_items, hipStream_t st);
 
 int launch_assign(long long N, int d, const double* X, int F, const double* normals, const double* offsets,
                   double abs_tol, int* facet_of_point, double* dist, long long* argmax, double* maxd,

@@ -97,6 +97,7 @@ class _NoDeviceState(object):
         st = dict(self.__dict__)
         st.pop("_packed", None)
         st.pop("_p2p_flat", None)
+        st.pop("_locate", None)
         st.pop("_merge_stable", None)   # (a note of mldivide's to itself: see _passed_untouched)
         return st
 
@@ -373,6 +374,16 @@ class Region(_NoDeviceState):
             raise ValueError("points should be column vectors")
         return _contains_many(self.list_poly, points, abs_tol, region=True, owner=self)
 
+    def locate(self, points, abs_tol=ABS_TOL):
+        """For each column of `points` the index into `list_poly` of the FIRST member that contains it, or -1 (int32[N];
+        no counterpart in the reference, whose users loop `x in poly`).  Members with an empty description contain
+        nothing.  On 'hip' the packed rows and the culling grid stay on this Region between calls (batch.locate_batch)."""
+        if not isinstance(points, np.ndarray):
+            points = np.array(points)
+        if points.shape[0] != self.dim:
+            raise ValueError("points should be column vectors")
+        return _locate_many(self.list_poly, points, abs_tol, owner=self, table_owner=self)
+
     def __eq__(self, other):
         return self <= other and other <= self
 
@@ -604,6 +615,53 @@ def _contains_many(polys, points, abs_tol, region=True, owner=None):
     for p in polys:
         inside |= np.all(p.A.dot(points) - p.b[:, np.newaxis] < abs_tol, axis=0)
     return inside
+
+
+def _locate_many(polys, points, abs_tol, owner=None, table_owner=None):
+    """Index into `polys` of the first polytope containing each column of `points`, or -1 (int32[N]).  'hip': the packed
+    table comes from _table_of (kept on `table_owner`), and the LocateGrid built for it is kept on `owner` beside the
+    table and abs_tol it was built for -- _table_of hands out the same table object as long as the rows' content is
+    unchanged, so a second call uploads the points only."""
+    points = np.asarray(points, dtype=float)
+    if points.ndim != 2:
+        raise ValueError("points should be column vectors")
+    N = points.shape[1]
+    if _use_hip():
+        solvers._require("hip")
+        idx = np.array([k for k, p in enumerate(polys) if p.A.size > 0], dtype=np.int64)
+        if idx.size == 0 or N == 0:
+            return np.full(N, -1, dtype=np.int32)
+        members = [polys[k] for k in idx]
+        if members[0].A.shape[1] > _MAX_DIM:
+            raise ValueError("the 'hip' backend handles dimension <= %d, got %d" % (_MAX_DIM, members[0].A.shape[1]))
+        from . import batch
+        tab = _table_of(members, table_owner)
+        At, bt, mt = tab.dev()
+        grid = None
+        if len(members) >= batch._LOCATE_AUTO_P:
+            hit = owner.__dict__.get("_locate") if owner is not None else None
+            if hit is not None and hit[0] is tab and hit[1] == float(abs_tol):
+                grid = hit[2]
+            else:
+                grid = batch.locate_grid(At, bt, mt, abs_tol)
+                if owner is not None:
+                    owner.__dict__["_locate"] = (tab, float(abs_tol), grid)
+        pts = np.ascontiguousarray(points)
+        if isinstance(At, np.ndarray):   # no torch in the process: host pointers all the way
+            first = batch.locate_batch(At, bt, pts, abs_tol, m=mt, grid=grid)
+        else:
+            batch._count_h2d(pts)
+            Xt = _torch_or_none().as_tensor(pts).to(At.device)
+            first = batch.locate_batch(At, bt, Xt, abs_tol, m=mt, grid=grid).cpu().numpy()
+        return np.where(first >= 0, idx[np.maximum(first, 0)], -1).astype(np.int32)
+    # explicitly selected non-'hip' backend: the reference's own numpy expression (ref :217-218), last member first
+    first = np.full(N, -1, dtype=np.int32)
+    for k in range(len(polys) - 1, -1, -1):
+        p = polys[k]
+        if p.A.size == 0:
+            continue
+        first[np.all(p.A.dot(points) - p.b[:, np.newaxis] < abs_tol, axis=0)] = k
+    return first
 
 
 def _ball_from_lp(status, r, xc):

@@ -307,6 +307,24 @@ class Partition(pc._NoDeviceState):
     def __getitem__(self, key):
         return self.regions[key]
 
+    def locate(self, points, abs_tol=pc.ABS_TOL):
+        """For each column of `points` the index of the FIRST region that contains it, or -1 (int32[N]) -- what a loop of
+        `x in region` over the partition finds (no counterpart in the reference).  The member polytopes of all regions
+        form one flat table, region-major, so the owner of the first containing member is the first containing region.
+        On 'hip' the table and its culling grid are kept on this partition between calls (polytope._locate_many)."""
+        regions = _regions_of(self)
+        points = np.asarray(points, dtype=float)
+        if points.ndim != 2:
+            raise ValueError("points should be column vectors")
+        if not regions:
+            return np.full(points.shape[1], -1, dtype=np.int32)
+        members, first, _ = _flat_members(regions, self)
+        hit = pc._locate_many(members, points, abs_tol, owner=self, table_owner=self)
+        region_of = np.repeat(np.arange(len(regions)), np.diff(first))
+        if region_of.size == 0:
+            return hit
+        return np.where(hit >= 0, region_of[np.maximum(hit, 0)], -1).astype(np.int32)
+
     def is_partition(self):
         """Return True if Regions are pairwise disjoint and cover domain (ref :102-105)."""
         return self.is_cover() and self.are_disjoint()
