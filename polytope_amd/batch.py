@@ -794,15 +794,35 @@ def _extreme_vmax(d, n):
     return max(1, {1: 2, 2: n, 3: 2 * n - 4}.get(d, n * (n - 3) // 2))
 
 
-def _extreme_unbounded(be, A, b, m, flat, d, box=None):
-    """bool[B]: a side of the bounding box is infinite (polytopes marked `flat` are not looked at; `box`: the result of
-    bbox_batch(A, b, m) when the caller has it already).  bbox_batch answers from
+def _small_shape(name, what, A, b, m):
+    """The shape checks of the enumeration calls (extreme_batch, volume_exact_batch, hull_batch) -> (B, rows_max, d).
+    `what`: the words in which the messages of `name` differ -- (the array, its middle dimension, the count per member, what
+    it does in dimension 1 .. 4, what it takes up to MAX_M of); b=None: there is no right-hand side to check."""
+    arr, rows, cnt, does, items = what
+    shape = lambda a: tuple(int(v) for v in (a.shape if hasattr(a, "shape") else np.shape(a)))   # noqa: E731
+    shp = shape(A)
+    if len(shp) != 3:
+        raise ValueError("%s must be [B, %s, d], got %d dimensions" % (arr, rows, len(shp)))
+    B, rows_max, d = shp
+    if b is not None and shape(b) != (B, rows_max):
+        raise ValueError("b must be [B, %s] = [%d, %d], got %s" % (rows, B, rows_max, list(shape(b))))
+    if m is not None and int(np.prod(shape(m))) != B:
+        raise ValueError("%s must be [B] = [%d]" % (cnt, B))
+    if d < 1 or d > _EXTREME_MAX_D:
+        raise ValueError("%s %s dimension 1 .. %d, got d = %d" % (name, does, _EXTREME_MAX_D, d))
+    if rows_max > MAX_M:
+        raise ValueError("%s takes %s, got %s = %d" % (name, items % MAX_M, rows, rows_max))
+    return B, rows_max, d
+
+
+def _extreme_unbounded(be, A, b, m, flat, d, box):
+    """bool[B]: a side of the bounding box `box` = bbox_batch(A, b, m) is infinite (polytopes marked `flat` are not looked
+    at).  bbox_batch answers from
     the Chebyshev centre; the polytopes it hands back (status 1: r < 1e-6, a Bland case) get the 2 d generic LPs, where
     an LP that ends unbounded -- or in any state but optimal / infeasible -- means the polytope is not vouched for.
     With CUDA tensors the host has to know whether anything was handed back: one flag is read back (a synchronisation),
     and the indices of those polytopes when there are any."""
     xp = be.torch if be.torch is not None else np
-    box = bbox_batch(A, b, m) if box is None else box
     inf = float("inf")
     open_ = ((box["lb"] == -inf) | (box["ub"] == inf) | (box["lb"] != box["lb"]) | (box["ub"] != box["ub"])).any(1)
     handled = box["status"] == 0
@@ -822,6 +842,24 @@ def _extreme_unbounded(be, A, b, m, flat, d, box=None):
         st = lpsolve_batch(c, rep(A), rep(b), None if m is None else rep(m))["status"].reshape(nr, 2 * d)
         unb[rest] = ((st != 0) & (st != 2)).any(1)
     return unb
+
+
+def _reduced_and_bounded(be, A, b, m, abs_tol, d):
+    """What reduce=True puts in front of an enumeration kernel, in this order on the device: reduce_batch, bbox_batch, the
+    generic LPs for what bbox_batch handed back (_extreme_unbounded) -> (red, box, flat bool[B]: RF_EMPTY or r <= abs_tol,
+    unb bool[B], keep: red["keep"], zero for a flat or unbounded member -- no live row: the kernel leaves at once)."""
+    xp = be.torch if be.torch is not None else np
+    red = reduce_batch(A, b, m, abs_tol=abs_tol)
+    flat = ((red["flags"] & _lib.RF_EMPTY) != 0) | ~(red["r"] > abs_tol)
+    box = bbox_batch(A, b, m)
+    unb = _extreme_unbounded(be, A, b, m, flat, d, box)
+    keep = xp.where(flat | unb, xp.zeros_like(red["keep"]), red["keep"])
+    return red, box, flat, unb, keep
+
+
+def _overlay(xp, flat, unb, x, if_flat, if_unb):
+    """x[B] with if_flat where `flat`, else if_unb where `unb`."""
+    return xp.where(flat, xp.full_like(x, if_flat), xp.where(unb, xp.full_like(x, if_unb), x))
 
 
 def extreme_batch(A, b, m=None, v_max=None, reduce=True, abs_tol=1e-7, basis=False):
@@ -847,19 +885,7 @@ def extreme_batch(A, b, m=None, v_max=None, reduce=True, abs_tol=1e-7, basis=Fal
     hand a polytope back -- plus the indices of such polytopes when there are any.  reduce=False with v_max given
     enqueues the kernel and returns."""
     be = _Backend(A)
-    shp = tuple(A.shape) if hasattr(A, "shape") else np.shape(A)
-    if len(shp) != 3:
-        raise ValueError("A must be [B, m_max, d], got %d dimensions" % len(shp))
-    B, m_max, d = (int(v) for v in shp)
-    bshp = tuple(b.shape) if hasattr(b, "shape") else np.shape(b)
-    if tuple(int(v) for v in bshp) != (B, m_max):
-        raise ValueError("b must be [B, m_max] = [%d, %d], got %s" % (B, m_max, list(bshp)))
-    if m is not None and int(np.prod(tuple(m.shape) if hasattr(m, "shape") else np.shape(m))) != B:
-        raise ValueError("m must be [B] = [%d]" % B)
-    if d < 1 or d > _EXTREME_MAX_D:
-        raise ValueError("extreme_batch enumerates bases in dimension 1 .. %d, got d = %d" % (_EXTREME_MAX_D, d))
-    if m_max > MAX_M:
-        raise ValueError("extreme_batch takes polytopes of up to %d rows, got m_max = %d" % (MAX_M, m_max))
+    B, m_max, d = _small_shape("extreme_batch", ("A", "m_max", "m", "enumerates bases in", "polytopes of up to %d rows"), A, b, m)
     if v_max is not None and (not _is_int(v_max) or v_max < 1):
         raise ValueError("`v_max` must be an integer >= 1, given:  {v}".format(v=v_max))
     A, b, m, _ = _packed(be, A, b, m)
@@ -874,11 +900,7 @@ def extreme_batch(A, b, m=None, v_max=None, reduce=True, abs_tol=1e-7, basis=Fal
         return empty_result(1 if v_max is None else int(v_max))
     keep = flat = unb = None
     if reduce:
-        red = reduce_batch(A, b, m, abs_tol=abs_tol)
-        flat = ((red["flags"] & _lib.RF_EMPTY) != 0) | ~(red["r"] > abs_tol)
-        unb = _extreme_unbounded(be, A, b, m, flat, d)
-        keep = red["keep"]
-        keep = xp.where(flat | unb, xp.zeros_like(keep), keep)   # (no live row: the kernel leaves at once, count 0)
+        _, _, flat, unb, keep = _reduced_and_bounded(be, A, b, m, abs_tol, d)
     if v_max is None:
         if keep is not None:
             bits = xp.arange(64, **on) if torch is not None else np.arange(64, dtype=np.uint64)
@@ -893,9 +915,7 @@ def extreme_batch(A, b, m=None, v_max=None, reduce=True, abs_tol=1e-7, basis=Fal
     be.call("plp_extreme_batch", B, m_max, d, A, b, m, keep, v_max, res["V"], res["count"], res["basis"], res["status"],
             h2d=(A, b, m, keep))
     if reduce:
-        st = res["status"]
-        code = (lambda v: xp.full_like(st, v))
-        res["status"] = xp.where(flat, code(XS_FLAT), xp.where(unb, code(XS_UNBOUNDED), st))
+        res["status"] = _overlay(xp, flat, unb, res["status"], XS_FLAT, XS_UNBOUNDED)
     return res
 
 
@@ -927,19 +947,7 @@ def volume_exact_batch(A, b, m=None, reduce=True, abs_tol=1e-7, areas=True):
     What waits for the device with CUDA tensors: with reduce=True one flag -- did bbox_batch hand a polytope back -- plus
     the indices of such polytopes when there are any.  reduce=False enqueues the kernel and returns."""
     be = _Backend(A)
-    shp = tuple(A.shape) if hasattr(A, "shape") else np.shape(A)
-    if len(shp) != 3:
-        raise ValueError("A must be [B, m_max, d], got %d dimensions" % len(shp))
-    B, m_max, d = (int(v) for v in shp)
-    bshp = tuple(b.shape) if hasattr(b, "shape") else np.shape(b)
-    if tuple(int(v) for v in bshp) != (B, m_max):
-        raise ValueError("b must be [B, m_max] = [%d, %d], got %s" % (B, m_max, list(bshp)))
-    if m is not None and int(np.prod(tuple(m.shape) if hasattr(m, "shape") else np.shape(m))) != B:
-        raise ValueError("m must be [B] = [%d]" % B)
-    if d < 1 or d > _EXTREME_MAX_D:
-        raise ValueError("volume_exact_batch takes dimension 1 .. %d, got d = %d" % (_EXTREME_MAX_D, d))
-    if m_max > MAX_M:
-        raise ValueError("volume_exact_batch takes polytopes of up to %d rows, got m_max = %d" % (MAX_M, m_max))
+    B, m_max, d = _small_shape("volume_exact_batch", ("A", "m_max", "m", "takes", "polytopes of up to %d rows"), A, b, m)
     A, b, m, _ = _packed(be, A, b, m)
     xp = be.torch if be.torch is not None else np
     res = dict(volume=be.out((B,), zero=True), area=be.out((B, m_max), zero=True) if areas else None,
@@ -948,12 +956,7 @@ def volume_exact_batch(A, b, m=None, reduce=True, abs_tol=1e-7, areas=True):
         return res
     keep = xc = scale = flat = unb = None
     if reduce:
-        red = reduce_batch(A, b, m, abs_tol=abs_tol)
-        flat = ((red["flags"] & _lib.RF_EMPTY) != 0) | ~(red["r"] > abs_tol)
-        box = bbox_batch(A, b, m)
-        unb = _extreme_unbounded(be, A, b, m, flat, d, box=box)
-        keep = red["keep"]
-        keep = xp.where(flat | unb, xp.zeros_like(keep), keep)   # (no live row: the kernel leaves at once)
+        red, box, flat, unb, keep = _reduced_and_bounded(be, A, b, m, abs_tol, d)
         with np.errstate(invalid="ignore"):   # (an open box: inf - inf, masked below)
             side, mid = box["ub"] - box["lb"], 0.5 * (box["lb"] + box["ub"])
         boxed = (box["status"] == 0) & ~flat & ~unb & (side == side).all(1) & (side > 0).all(1)
@@ -964,13 +967,10 @@ def volume_exact_batch(A, b, m=None, reduce=True, abs_tol=1e-7, areas=True):
     be.call("plp_vol_exact_batch", B, m_max, d, A, b, m, keep, xc, scale, res["volume"], res["area"], res["status"],
             h2d=(A, b, m, keep, xc, scale))
     if reduce:
-        st, vol = res["status"], res["volume"]
-        code = (lambda v: xp.full_like(st, v))
-        gone = flat | unb
-        res["status"] = xp.where(flat, code(VS_FLAT), xp.where(unb, code(VS_UNBOUNDED), st))
-        res["volume"] = xp.where(flat, xp.zeros_like(vol), xp.where(unb, xp.full_like(vol, float("inf")), vol))
+        res["status"] = _overlay(xp, flat, unb, res["status"], VS_FLAT, VS_UNBOUNDED)
+        res["volume"] = _overlay(xp, flat, unb, res["volume"], 0.0, float("inf"))
         if areas:
-            res["area"] = xp.where(gone[:, None], xp.zeros_like(res["area"]), res["area"])
+            res["area"] = xp.where((flat | unb)[:, None], xp.zeros_like(res["area"]), res["area"])
     return res
 
 
@@ -1004,16 +1004,8 @@ def hull_batch(X, n=None, f_max=None, basis=False):
     vertices.  The rows are neither reduced (a near-degenerate subset can repeat a face as a second, slightly tilted row)
     nor passed through Polytope."""
     be = _Backend(X)
-    shp = tuple(X.shape) if hasattr(X, "shape") else np.shape(X)
-    if len(shp) != 3:
-        raise ValueError("X must be [B, n_max, d], got %d dimensions" % len(shp))
-    B, n_max, d = (int(v) for v in shp)
-    if n is not None and int(np.prod(tuple(n.shape) if hasattr(n, "shape") else np.shape(n))) != B:
-        raise ValueError("n must be [B] = [%d]" % B)
-    if d < 1 or d > _EXTREME_MAX_D:
-        raise ValueError("hull_batch enumerates hyperplanes in dimension 1 .. %d, got d = %d" % (_EXTREME_MAX_D, d))
-    if n_max > MAX_M:
-        raise ValueError("hull_batch takes point sets of up to %d points, got n_max = %d" % (MAX_M, n_max))
+    B, n_max, d = _small_shape("hull_batch", ("X", "n_max", "n", "enumerates hyperplanes in", "point sets of up to %d points"),
+                               X, None, n)
     if f_max is not None and (not _is_int(f_max) or f_max < 1):
         raise ValueError("`f_max` must be an integer >= 1, given:  {v}".format(v=f_max))
     X, n = be.arr(X), be.arr(n, np.int32, (B,))

@@ -33,87 +33,32 @@
 // as separate multiplies and adds in a fixed order, sqrt and / are correctly rounded on both sides, so the device's V is the
 // host's bit for bit.
 #pragma once
-#include <math.h>
-#include <stddef.h>
-#include <stdint.h>
-
-#if defined(__HIPCC__)
-#define PLP_XS_FN __host__ __device__ __forceinline__
-#else
-#define PLP_XS_FN static inline
-#endif
+#include "plp_enum.hpp"
 
 namespace plp {
 namespace extreme {
 
-constexpr int MAX_DIM = 4, MAX_ROWS = 64;
+constexpr int MAX_DIM = wenum::MAX_DIM, MAX_ROWS = wenum::MAX_ITEMS;
+using wenum::binom, wenum::candidates, wenum::next, wenum::unrank;   // (the names they had here before plp_enum.hpp)
 constexpr double DET_TOL = 1e-12, FEAS_TOL = 1e-9, SAME_TOL = 1e-9;
 enum : int { XS_OK = 0, XS_OVERFLOW = 1, XS_EMPTY = 2 };   // include/plp.h: PLP_XS_*
 
 // LDS (or host scratch) of one polytope: the staged rows [MAX_ROWS][D], their right-hand sides and original indices
 constexpr size_t lds_bytes(int D, int m_max) { return (size_t)m_max * (D + 1) * sizeof(double) + (size_t)m_max * sizeof(int); }
 
-// C(k, q) for q <= 3 and 0 <= k <= 64 (0 when k < q)
-PLP_XS_FN int binom(const int k, const int q) {
-    return q == 0 ? 1 : (q == 1 ? k : (q == 2 ? k * (k - 1) / 2 : k * (k - 1) * (k - 2) / 6));
-}
-// the number of candidates: C(n, D)
+// one input row -> its staged form (wenum::unit_row and its verdict; beta = b_i / |a_i|)
 template <int D>
-PLP_XS_FN int candidates(const int n) {
-    return D == 4 ? (int)((long long)binom(n, 3) * (n - 3) / 4) : binom(n, D);
-}
-
-// the D-subset of {0 .. n - 1} of lexicographic rank r (0 <= r < C(n, D))
-template <int D>
-PLP_XS_FN void unrank(const int n, int r, int (&idx)[D]) {
-    int c = 0;
-#pragma unroll
-    for (int pos = 0; pos < D; ++pos) {
-        const int q = D - 1 - pos;   // rows still to pick after this one
-        if (q == 0) {
-            c += r;
-        } else {
-            for (;;) {
-                const int cnt = binom(n - 1 - c, q);
-                if (r < cnt) break;
-                r -= cnt;
-                ++c;
-            }
-        }
-        idx[pos] = c;
-        ++c;
-    }
-}
-
-// the subset after idx in lexicographic order; false when idx was the last
-template <int D>
-PLP_XS_FN bool next(const int n, int (&idx)[D]) {
-    int pos = D - 1;
-    while (pos >= 0 && idx[pos] == n - D + pos) --pos;
-    if (pos < 0) return false;
-    ++idx[pos];
-    for (int k = pos + 1; k < D; ++k) idx[k] = idx[k - 1] + 1;
-    return true;
-}
-
-// one input row -> its staged form.  0: not staged (a zero row that says nothing), 1: staged, 2: the polytope is empty
-template <int D>
-PLP_XS_FN int stage_row(const double* a, const double bi, double (&u)[D], double& beta) {
-    double s = a[0] * a[0];
-#pragma unroll
-    for (int k = 1; k < D; ++k) s = s + a[k] * a[k];
-    const double nrm = sqrt(s);
-    if (nrm == 0.0) return bi >= 0.0 ? 0 : 2;
-#pragma unroll
-    for (int k = 0; k < D; ++k) u[k] = a[k] / nrm;
-    beta = bi / nrm;
-    return 1;
+PLP_ENUM_FN int stage_row(const double* a, const double bi, double (&u)[D], double& beta) {
+    double nrm;
+    const int kind = wenum::unit_row<D>(a, bi, u, nrm);
+    if (kind == 1) beta = bi / nrm;
+    return kind;
 }
 
 // A_S v = b_S by elimination with partial pivoting on M = [A_S | b_S], every index a compile-time one.
 // -> |det A_S| > DET_TOL (v is only meaningful then)
 template <int D>
-PLP_XS_FN bool solve(double (&M)[D][D + 1], double (&v)[D]) {
+PLP_ENUM_FN bool solve(double (&M)[D][D + 1], double (&v)[D]) {
     double det = 1.0;
 #pragma unroll
     for (int c = 0; c < D; ++c) {
@@ -147,17 +92,9 @@ PLP_XS_FN bool solve(double (&M)[D][D + 1], double (&v)[D]) {
     return true;
 }
 
-template <int D>
-PLP_XS_FN double norm_inf(const double (&v)[D]) {
-    double e = fabs(v[0]);
-#pragma unroll
-    for (int k = 1; k < D; ++k) e = fmax(e, fabs(v[k]));
-    return e;
-}
-
 // the candidate of subset idx on the staged rows sA[n][D], sb[n]: solved, finite and feasible -> v
 template <int D>
-PLP_XS_FN bool candidate(const double* sA, const double* sb, const int n, const int (&idx)[D], double (&v)[D]) {
+PLP_ENUM_FN bool candidate(const double* sA, const double* sb, const int n, const int (&idx)[D], double (&v)[D]) {
     double M[D][D + 1];
 #pragma unroll
     for (int r = 0; r < D; ++r) {
@@ -166,23 +103,18 @@ PLP_XS_FN bool candidate(const double* sA, const double* sb, const int n, const 
         M[r][D] = sb[idx[r]];
     }
     if (!solve<D>(M, v)) return false;
-    const double vn = norm_inf<D>(v);
+    const double vn = wenum::norm_inf<D>(v);
     if (!(vn < __builtin_inf())) return false;
     const double ext = fmax(1.0, vn);
     bool ok = true;
-    for (int i = 0; i < n; ++i) {
-        double s = sA[i * D] * v[0];
-#pragma unroll
-        for (int k = 1; k < D; ++k) s = s + sA[i * D + k] * v[k];
-        ok = ok & (s - sb[i] <= FEAS_TOL * fmax(ext, fabs(sb[i])));
-    }
+    for (int i = 0; i < n; ++i) ok = ok & (wenum::dot<D>(sA + i * D, v) - sb[i] <= FEAS_TOL * fmax(ext, fabs(sb[i])));
     return ok;
 }
 
 // an accepted vertex w lies within SAME_TOL of the candidate v (the tolerance is the CANDIDATE's)
 template <int D>
-PLP_XS_FN bool same(const double (&v)[D], const double* w) {
-    const double tol = SAME_TOL * fmax(1.0, norm_inf<D>(v));
+PLP_ENUM_FN bool same(const double (&v)[D], const double* w) {
+    const double tol = SAME_TOL * fmax(1.0, wenum::norm_inf<D>(v));
     bool close = true;
 #pragma unroll
     for (int k = 0; k < D; ++k) close = close & (fabs(v[k] - w[k]) <= tol);
@@ -192,8 +124,8 @@ PLP_XS_FN bool same(const double (&v)[D], const double* w) {
 // The whole rule for one polytope, sequentially (the host build; the kernel's answers are held against it bit for bit).
 // A[m_max][D], b[m_max], m rows of them in use, keep: bit i = row i is live.  V[v_max][D], basis[v_max][D] or nullptr.
 template <int D>
-PLP_XS_FN void one(const int m_max, const double* A, const double* b, int m, const uint64_t keep, const int v_max, double* V,
-                   int* basis, int& count, int& status) {
+PLP_ENUM_FN void one(const int m_max, const double* A, const double* b, int m, const uint64_t keep, const int v_max, double* V,
+                     int* basis, int& count, int& status) {
     double sA[MAX_ROWS * D], sb[MAX_ROWS];
     int sidx[MAX_ROWS];
     m = m < 0 ? 0 : (m > m_max ? m_max : m);
@@ -212,24 +144,18 @@ PLP_XS_FN void one(const int m_max, const double* A, const double* b, int m, con
     count = 0;
     status = XS_OK;
     if (!empty && n >= D) {
-        int idx[D];
-        for (int k = 0; k < D; ++k) idx[k] = k;
-        do {
-            double v[D];
-            if (!candidate<D>(sA, sb, n, idx, v)) continue;
-            bool dup = false;
-            for (int q = 0; q < count && !dup; ++q) dup = same<D>(v, V + (size_t)q * D);
-            if (dup) continue;
-            if (count == v_max) {
-                status = XS_OVERFLOW;
-                break;
-            }
-            for (int k = 0; k < D; ++k) {
-                V[(size_t)count * D + k] = v[k];
-                if (basis) basis[(size_t)count * D + k] = sidx[idx[k]];
-            }
-            ++count;
-        } while (next<D>(n, idx));
+        double v[D];   // the candidate the list is looking at
+        const bool over = wenum::greedy_list<D>(
+            n, v_max, count,
+            [&](const int(&idx)[D]) { return candidate<D>(sA, sb, n, idx, v) ? wenum::LIST_TAKE : wenum::LIST_SKIP; },
+            [&](const int q) { return same<D>(v, V + (size_t)q * D); },
+            [&](const int q, const int(&idx)[D]) {
+                for (int k = 0; k < D; ++k) {
+                    V[(size_t)q * D + k] = v[k];
+                    if (basis) basis[(size_t)q * D + k] = sidx[idx[k]];
+                }
+            });
+        if (over) status = XS_OVERFLOW;
     }
     if (count == 0) status = XS_EMPTY;
     for (size_t q = (size_t)count * D; q < (size_t)v_max * D; ++q) {

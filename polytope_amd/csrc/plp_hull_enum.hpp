@@ -10,7 +10,7 @@
 //               FLAT when s is not a positive finite number or fewer than D + 1 points are live.  Else q_i = (p_i - c) / s:
 //               every coordinate lies in [-1, 1], and the tolerances below are absolute on the q.
 //   candidates  every D-subset S = (i0 < i1 < ...) of the staged points, in lexicographic order (unrank / next / binom of
-//               plp_extreme.hpp).  Edges e_k = q_ik - q_i0, k = 1 .. D - 1; the normal nu is their generalised cross
+//               plp_enum.hpp).  Edges e_k = q_ik - q_i0, k = 1 .. D - 1; the normal nu is their generalised cross
 //               product (normal<D> below fixes the order of operations: D = 1: 1, D = 2: (e_y, -e_x), D = 3: e1 x e2,
 //               D = 4: the signed 3 x 3 cofactors of [e1; e2; e3]).  S is skipped unless |nu|_2 > DEG_TOL prod |e_k|_2 --
 //               which also skips a zero edge (both sides 0) and anything that is not a number.  Else nu <- nu / |nu|_2,
@@ -50,12 +50,12 @@
 // written as separate multiplies and adds in a fixed order, sqrt and / are correctly rounded on both sides, so the device's
 // rows are the host's bit for bit.
 #pragma once
-#include "plp_extreme.hpp"
+#include "plp_enum.hpp"
 
 namespace plp {
 namespace hullenum {
 
-constexpr int MAX_DIM = 4, MAX_POINTS = 64;
+constexpr int MAX_DIM = wenum::MAX_DIM, MAX_POINTS = wenum::MAX_ITEMS;
 constexpr double DEG_TOL = 1e-12, SIDE_TOL = 1e-9, SAME_TOL = 1e-9;
 enum : int { HS_OK = 0, HS_OVERFLOW = 1, HS_FLAT = 2 };   // include/plp.h: PLP_HS_*
 enum : int { CAND_NONE = 0, CAND_FACET = 1, CAND_FLAT = 2 };
@@ -64,9 +64,9 @@ enum : int { CAND_NONE = 0, CAND_FACET = 1, CAND_FLAT = 2 };
 constexpr size_t lds_bytes(int D, int n_max) { return (size_t)n_max * D * sizeof(double) + (size_t)n_max * sizeof(int); }
 
 // the centre of [lo, hi] (a zero is +0) and a point's distance from it in the max-norm
-PLP_XS_FN double centre(const double lo, const double hi) { return (lo + hi) / 2.0 + 0.0; }
+PLP_ENUM_FN double centre(const double lo, const double hi) { return (lo + hi) / 2.0 + 0.0; }
 template <int D>
-PLP_XS_FN double reach(const double (&p)[D], const double (&c)[D]) {
+PLP_ENUM_FN double reach(const double (&p)[D], const double (&c)[D]) {
     double e = fabs(p[0] - c[0]);
 #pragma unroll
     for (int k = 1; k < D; ++k) e = fmax(e, fabs(p[k] - c[k]));
@@ -74,13 +74,13 @@ PLP_XS_FN double reach(const double (&p)[D], const double (&c)[D]) {
 }
 // is this (s, live points) a set the enumeration takes?
 template <int D>
-PLP_XS_FN bool stageable(const double s, const int live) {
+PLP_ENUM_FN bool stageable(const double s, const int live) {
     return s > 0.0 && s < __builtin_inf() && live >= D + 1;
 }
 
 // a1 (b2 c3 - b3 c2) - a2 (b1 c3 - b3 c1) + a3 (b1 c2 - b2 c1): the determinant of the columns a, b, c
-PLP_XS_FN double det3(const double a1, const double a2, const double a3, const double b1, const double b2, const double b3,
-                      const double c1, const double c2, const double c3) {
+PLP_ENUM_FN double det3(const double a1, const double a2, const double a3, const double b1, const double b2, const double b3,
+                        const double c1, const double c2, const double c3) {
     const double t1 = a1 * (b2 * c3 - b3 * c2);
     const double t2 = a2 * (b1 * c3 - b3 * c1);
     const double t3 = a3 * (b1 * c2 - b2 * c1);
@@ -89,15 +89,10 @@ PLP_XS_FN double det3(const double a1, const double a2, const double a3, const d
 
 // The generalised cross product of the edges e[1 .. D - 1] (e[0] is not used) -> nu, and prod |e_k|_2.
 template <int D>
-PLP_XS_FN double normal(const double (&e)[D][D], double (&nu)[D]) {
+PLP_ENUM_FN double normal(const double (&e)[D][D], double (&nu)[D]) {
     double prod = 1.0;
 #pragma unroll
-    for (int k = 1; k < D; ++k) {
-        double s = e[k][0] * e[k][0];
-#pragma unroll
-        for (int j = 1; j < D; ++j) s = s + e[k][j] * e[k][j];
-        prod = prod * sqrt(s);
-    }
+    for (int k = 1; k < D; ++k) prod = prod * sqrt(wenum::dot<D>(e[k], e[k]));
     if constexpr (D == 1) {
         nu[0] = 1.0;
     } else if constexpr (D == 2) {
@@ -122,19 +117,11 @@ PLP_XS_FN double normal(const double (&e)[D][D], double (&nu)[D]) {
     return prod;
 }
 
-template <int D>
-PLP_XS_FN double dot(const double (&u)[D], const double* w) {
-    double s = u[0] * w[0];
-#pragma unroll
-    for (int k = 1; k < D; ++k) s = s + u[k] * w[k];
-    return s;
-}
-
 // The candidate of subset idx on the staged points sq[n][D] (sidx[n]: their original indices) -> CAND_*; for a facet
 // (nu, off) is the row on the staged points, oriented, and `on` its incidence word.
 template <int D>
-PLP_XS_FN int candidate(const double* sq, const int* sidx, const int n, const int (&idx)[D], double (&nu)[D], double& off,
-                        uint64_t& on) {
+PLP_ENUM_FN int candidate(const double* sq, const int* sidx, const int n, const int (&idx)[D], double (&nu)[D], double& off,
+                          uint64_t& on) {
     double e[D][D];
 #pragma unroll
     for (int k = 1; k < D; ++k) {
@@ -142,18 +129,15 @@ PLP_XS_FN int candidate(const double* sq, const int* sidx, const int n, const in
         for (int j = 0; j < D; ++j) e[k][j] = sq[idx[k] * D + j] - sq[idx[0] * D + j];
     }
     const double prod = normal<D>(e, nu);
-    double s = nu[0] * nu[0];
-#pragma unroll
-    for (int j = 1; j < D; ++j) s = s + nu[j] * nu[j];
-    const double nn = sqrt(s);
+    const double nn = sqrt(wenum::dot<D>(nu, nu));
     if (!(nn > DEG_TOL * prod)) return CAND_NONE;
 #pragma unroll
     for (int j = 0; j < D; ++j) nu[j] = nu[j] / nn;
-    off = dot<D>(nu, sq + idx[0] * D);
+    off = wenum::dot<D>(nu, sq + idx[0] * D);
     double hi = -__builtin_inf(), lo = __builtin_inf();
     uint64_t w = 0;
     for (int i = 0; i < n; ++i) {
-        const double r = dot<D>(nu, sq + i * D) - off;
+        const double r = wenum::dot<D>(nu, sq + i * D) - off;
         hi = fmax(hi, r);
         lo = fmin(lo, r);
         w |= (uint64_t)(fabs(r) <= SIDE_TOL) << sidx[i];
@@ -172,7 +156,7 @@ PLP_XS_FN int candidate(const double* sq, const int* sidx, const int n, const in
 
 // an accepted facet (w, woff) is the candidate's row to SAME_TOL
 template <int D>
-PLP_XS_FN bool same(const double (&nu)[D], const double off, const double* w, const double woff) {
+PLP_ENUM_FN bool same(const double (&nu)[D], const double off, const double* w, const double woff) {
     bool close = fabs(off - woff) <= SAME_TOL;
 #pragma unroll
     for (int k = 0; k < D; ++k) close = close & (fabs(nu[k] - w[k]) <= SAME_TOL);
@@ -181,19 +165,16 @@ PLP_XS_FN bool same(const double (&nu)[D], const double off, const double* w, co
 
 // an accepted row (nu, off) on the staged points -> its right-hand side in the caller's coordinates
 template <int D>
-PLP_XS_FN double unstage(const double* nu, const double off, const double (&c)[D], const double s) {
-    double t = nu[0] * c[0];
-#pragma unroll
-    for (int k = 1; k < D; ++k) t = t + nu[k] * c[k];
-    return t + s * off;
+PLP_ENUM_FN double unstage(const double* nu, const double off, const double (&c)[D], const double s) {
+    return wenum::dot<D>(nu, c) + s * off;
 }
 
 // The whole rule for one point set, sequentially (the host build; the kernel's answers are held against it bit for bit).
 // X[n_max][D], n points of them in use, keep: bit i = point i is live.  Ao[f_max][D], bo[f_max], on[f_max], basis[f_max][D]
 // or nullptr.  While the enumeration runs bo holds `off` of the accepted rows, as it does in the kernel.
 template <int D>
-PLP_XS_FN void one(const int n_max, const double* X, int n, const uint64_t keep, const int f_max, double* Ao, double* bo,
-                   uint64_t* on, int* basis, int& count, int& status) {
+PLP_ENUM_FN void one(const int n_max, const double* X, int n, const uint64_t keep, const int f_max, double* Ao, double* bo,
+                     uint64_t* on, int* basis, int& count, int& status) {
     double sq[MAX_POINTS * D], c[D], lo[D], hi[D], s = 0.0;
     int sidx[MAX_POINTS];
     n = n < 0 ? 0 : (n > n_max ? n_max : n);
@@ -221,32 +202,24 @@ PLP_XS_FN void one(const int n_max, const double* X, int n, const uint64_t keep,
     if (stageable<D>(s, live)) {
         for (int j = 0; j < live; ++j)
             for (int k = 0; k < D; ++k) sq[j * D + k] = (X[(size_t)sidx[j] * D + k] - c[k]) / s;
-        int idx[D];
-        for (int k = 0; k < D; ++k) idx[k] = k;
-        do {
-            double nu[D], off = 0.0;
-            uint64_t w = 0;
-            const int kind = candidate<D>(sq, sidx, live, idx, nu, off, w);
-            if (kind == CAND_FLAT) {
-                count = 0;
-                break;
-            }
-            if (kind != CAND_FACET) continue;
-            bool dup = false;
-            for (int q = 0; q < count && !dup; ++q) dup = same<D>(nu, off, Ao + (size_t)q * D, bo[q]);
-            if (dup) continue;
-            if (count == f_max) {
-                status = HS_OVERFLOW;
-                break;
-            }
-            for (int k = 0; k < D; ++k) {
-                Ao[(size_t)count * D + k] = nu[k];
-                if (basis) basis[(size_t)count * D + k] = sidx[idx[k]];
-            }
-            bo[count] = off;
-            on[count] = w;
-            ++count;
-        } while (extreme::next<D>(live, idx));
+        double nu[D], off = 0.0;   // the candidate the list is looking at
+        uint64_t w = 0;
+        const bool over = wenum::greedy_list<D>(
+            live, f_max, count,
+            [&](const int(&idx)[D]) {   // (a flat candidate ends the list empty)
+                const int kind = candidate<D>(sq, sidx, live, idx, nu, off, w);
+                return kind == CAND_FLAT ? wenum::LIST_END : (kind == CAND_FACET ? wenum::LIST_TAKE : wenum::LIST_SKIP);
+            },
+            [&](const int q) { return same<D>(nu, off, Ao + (size_t)q * D, bo[q]); },
+            [&](const int q, const int(&idx)[D]) {
+                for (int k = 0; k < D; ++k) {
+                    Ao[(size_t)q * D + k] = nu[k];
+                    if (basis) basis[(size_t)q * D + k] = sidx[idx[k]];
+                }
+                bo[q] = off;
+                on[q] = w;
+            });
+        if (over) status = HS_OVERFLOW;
     }
     if (count == 0) status = HS_FLAT;
     for (int q = 0; q < count; ++q) bo[q] = unstage<D>(Ao + (size_t)q * D, bo[q], c, s);

@@ -6,10 +6,8 @@
 
 namespace plp {
 
-constexpr int VX_BLOCK = 64;   // one wavefront per workgroup
-
-// Workgroup P takes polytope P.  Lane i stages row i (m_max <= 64: the rows are read from memory once), the staged rows
-// are compacted into LDS in row order.  The lanes then take the tuples of the last two chain levels, 64 to a round --
+// Workgroup P takes polytope P.  Lane i stages row i, the staged rows are compacted into LDS in row order (wenum::Member).
+// The lanes then take the tuples of the last two chain levels, 64 to a round --
 // (i1) at d = 2, (i1, i2) at d = 3, (i2, i3) under a wave-uniform loop over i1 at d = 4 -- and each evaluates its term
 // (volume_exact::tuple_term: the chain's q, p and h in registers, one pass over the LDS rows in which every lane reads the
 // same address, a broadcast) into the LDS term table.  The sums are the rule's: lane a adds row a of the table in index
@@ -18,7 +16,7 @@ constexpr int VX_BLOCK = 64;   // one wavefront per workgroup
 // in registers is indexed at compile time.
 // At (64, 4) that is 64^3 tuples of 64 rows each per wavefront: milliseconds.  The cost grows as n^D.
 template <int D>
-__global__ __launch_bounds__(VX_BLOCK) void volume_exact_kernel(const int m_max, const double* __restrict__ Ag,
+__global__ __launch_bounds__(wenum::BLOCK) void volume_exact_kernel(const int m_max, const double* __restrict__ Ag,
                                                                 const double* __restrict__ bg, const int* __restrict__ mrows,
                                                                 const unsigned long long* __restrict__ keepg,
                                                                 const double* __restrict__ xcg, const double* __restrict__ scaleg,
@@ -31,18 +29,16 @@ __global__ __launch_bounds__(VX_BLOCK) void volume_exact_kernel(const int m_max,
     double* fterm = sb + m_max;                         // [m_max]: the facets' terms (d = 2)
     double* fmeas = fterm + m_max;                      // [m_max]: the facets' measures
     double* tab = fmeas + m_max;                        // [n][tab_stride(n)] (d >= 3)
-    const int lane = threadIdx.x;
-    const long long P = blockIdx.x;
-    int m = mrows ? mrows[P] : m_max;
-    m = m < 0 ? 0 : (m > m_max ? m_max : m);
-    const unsigned long long keep = keepg ? keepg[P] : ~0ull;
+    wenum::Member me(m_max, mrows, keepg);
+    const int lane = me.lane;
+    const long long P = me.P;
     const double scale = scaleg ? scaleg[P] : 1.0;
     // ---- stage
     int kind = 0;
     double u[D], beta = 0.0;
 #pragma unroll
     for (int k = 0; k < D; ++k) u[k] = 0.0;
-    if (lane < m && ((keep >> lane) & 1ull)) {
+    if (me.live) {
         double a[D], c[D];
         const double* src = Ag + (P * m_max + lane) * D;
 #pragma unroll
@@ -52,10 +48,9 @@ __global__ __launch_bounds__(VX_BLOCK) void volume_exact_kernel(const int m_max,
         }
         kind = stage_row<D>(a, bg[P * m_max + lane], xcg != nullptr, c, scale, u, beta);
     }
-    const unsigned long long staged = __ballot(kind == 1);
+    me.compact(kind == 1);
     const bool empty = __any(kind == 2) != 0;
-    const int n = __popcll(staged);
-    const int pos = __popcll(staged & ((1ull << lane) - 1ull));
+    const int n = me.n, pos = me.pos;
     if (kind == 1) {
 #pragma unroll
         for (int k = 0; k < D; ++k) sU[pos * D + k] = u[k];
@@ -91,7 +86,7 @@ __global__ __launch_bounds__(VX_BLOCK) void volume_exact_kernel(const int m_max,
         const int ns = tab_stride(n), T = n * n;
         const int outer = D == 4 ? n : 1;
         for (int o = 0; o < outer; ++o) {
-            for (int base = 0; base < T; base += VX_BLOCK) {
+            for (int base = 0; base < T; base += wenum::BLOCK) {
                 const int rank = base + lane;
                 if (rank < T) {
                     const int a = rank / n, c = rank - a * n;
@@ -138,19 +133,12 @@ __global__ __launch_bounds__(VX_BLOCK) void volume_exact_kernel(const int m_max,
 int launch_volume_exact(long long B, int m_max, int d, const double* A, const double* b, const int* mrows,
                         const unsigned long long* keep, const double* xc, const double* scale, double* volume, double* area,
                         int* status, hipStream_t st) {
-    if (B < 1 || B > 2147483647ll || m_max < 0 || m_max > volume_exact::MAX_ROWS) return 2;
-#define PLP_VX(D)                                                                                                          \
-    hipLaunchKernelGGL((volume_exact_kernel<D>), dim3((unsigned)B), dim3(VX_BLOCK), volume_exact::lds_bytes(D, m_max), st, \
-                       m_max, A, b, mrows, keep, xc, scale, volume, area, status)
-    switch (d) {
-        case 1: PLP_VX(1); break;
-        case 2: PLP_VX(2); break;
-        case 3: PLP_VX(3); break;
-        case 4: PLP_VX(4); break;
-        default: return 2;
-    }
-#undef PLP_VX
-    return 0;
+    if (B < 1 || B > 2147483647ll || m_max < 0 || m_max > wenum::MAX_ITEMS) return 2;
+    return wenum::dispatch_dim(d, [&](auto dim) {
+        constexpr int D = decltype(dim)::value;
+        hipLaunchKernelGGL((volume_exact_kernel<D>), dim3((unsigned)B), dim3(wenum::BLOCK), volume_exact::lds_bytes(D, m_max), st,
+                           m_max, A, b, mrows, keep, xc, scale, volume, area, status);
+    });
 }
 
 }  // namespace plp

@@ -9,7 +9,7 @@
 // The contract, as a sequential rule (volume_exact::one<D> below is that rule; the kernel evaluates the same terms 64 at a
 // time and adds them in the same order):
 //   staging   the live rows (i < m, bit i of `keep`) in increasing row index, each scaled to unit 2-norm u_i = a_i / |a_i|
-//             (extreme::stage_row).  A live zero row is not staged: with b_i >= 0 it says nothing, with b_i < 0 (or NaN) the
+//             (wenum::unit_row).  A live zero row is not staged: with b_i >= 0 it says nothing, with b_i < 0 (or NaN) the
 //             member is VS_EMPTY with volume 0.  Then beta_i = ((b_i - a_i.c) / |a_i|) / s with c = xc (0 when absent) and
 //             s = scale (1 when absent): the rows of (P - c) / s.  (b_i / |a_i| - u_i.c is the same number with one more
 //             rounding at the size of the offset: 1e-13 of the volume at |c| = 1e3.)  All tolerances are absolute on
@@ -61,58 +61,37 @@
 // separate multiplies and adds in a fixed order, sqrt and / are correctly rounded on both sides, min / max are written as
 // comparisons, so the device's numbers are the host's bit for bit.
 #pragma once
-#include <math.h>
-#include <stddef.h>
-#include <stdint.h>
-
-#include "plp_extreme.hpp"
-
-#define PLP_VX_FN PLP_XS_FN
+#include "plp_enum.hpp"
 
 namespace plp {
 namespace volume_exact {
 
-constexpr int MAX_DIM = 4, MAX_ROWS = 64;
+using wenum::dot;
+constexpr int MAX_DIM = wenum::MAX_DIM, MAX_ROWS = wenum::MAX_ITEMS;
 constexpr double PAR_TOL = 1e-12, PAR_TOL2 = PAR_TOL * PAR_TOL, RES_TOL = 1e-9;
 enum : int { VS_OK = 0, VS_UNBOUNDED = 1, VS_EMPTY = 2, VS_FLAT = 3 };   // include/plp.h: PLP_VS_*
 
 // the row stride of the term table of n staged rows (odd: the lanes that add its rows read different LDS banks)
-PLP_VX_FN int tab_stride(const int n) { return n | 1; }
+PLP_ENUM_FN int tab_stride(const int n) { return n | 1; }
 // LDS (or host scratch) of one polytope: the staged rows [m_max][D] and their beta, the facet terms and facet measures
 // [m_max] each, and for D >= 3 the term table [m_max][tab_stride(m_max)] of the last two chain levels
 constexpr size_t lds_bytes(int D, int m_max) {
     return ((size_t)m_max * (D + 3) + (D >= 3 ? (size_t)m_max * (m_max | 1) : 0)) * sizeof(double);
 }
 
-PLP_VX_FN double inf() { return __builtin_inf(); }
+PLP_ENUM_FN double inf() { return __builtin_inf(); }
 
 // (h / e) R, +inf when R is
-PLP_VX_FN double weigh(const double h, const int e, const double R) { return R == inf() ? inf() : (h / (double)e) * R; }
+PLP_ENUM_FN double weigh(const double h, const int e, const double R) { return R == inf() ? inf() : (h / (double)e) * R; }
 
+// one input row -> its staged form on the rows of (P - c) / s (wenum::unit_row and its verdict, beta shifted and scaled)
 template <int D>
-PLP_VX_FN double dot(const double (&x)[D], const double (&y)[D]) {
-    double s = x[0] * y[0];
-#pragma unroll
-    for (int k = 1; k < D; ++k) s = s + x[k] * y[k];
-    return s;
-}
-
-// one input row -> its staged form on the rows of (P - c) / s.  0: not staged, 1: staged, 2: the member is empty
-template <int D>
-PLP_VX_FN int stage_row(const double (&a)[D], const double bi, const bool shifted, const double (&c)[D], const double s,
-                        double (&u)[D], double& beta) {
-    double s2 = a[0] * a[0], ac = a[0] * c[0];
-#pragma unroll
-    for (int k = 1; k < D; ++k) {
-        s2 = s2 + a[k] * a[k];
-        ac = ac + a[k] * c[k];
-    }
-    const double nrm = sqrt(s2);   // (as extreme::stage_row)
-    if (nrm == 0.0) return bi >= 0.0 ? 0 : 2;
-#pragma unroll
-    for (int k = 0; k < D; ++k) u[k] = a[k] / nrm;
-    beta = ((bi - (shifted ? ac : 0.0)) / nrm) / s;
-    return 1;
+PLP_ENUM_FN int stage_row(const double (&a)[D], const double bi, const bool shifted, const double (&c)[D], const double s,
+                          double (&u)[D], double& beta) {
+    double nrm;
+    const int kind = wenum::unit_row<D>(a, bi, u, nrm);
+    if (kind == 1) beta = ((bi - (shifted ? dot<D>(a, c) : 0.0)) / nrm) / s;
+    return kind;
 }
 
 // the chain of a tuple: K = D - 1 levels at the most, v of them valid (arrays of at least one level, so that D = 1 compiles)
@@ -126,8 +105,8 @@ struct Chain {
 
 // row j = (u, beta) against the first `upto` levels of the chain -> 0 live (w = w_upto, s2 = |w|^2), 1 says nothing, 2 kill
 template <int D>
-PLP_VX_FN int classify(const Chain<D>& c, const int upto, const double (&u)[D], const double beta, const int j, double (&w)[D],
-                       double& s2) {
+PLP_ENUM_FN int classify(const Chain<D>& c, const int upto, const double (&u)[D], const double beta, const int j, double (&w)[D],
+                         double& s2) {
 #pragma unroll
     for (int k = 0; k < D; ++k) w[k] = u[k];
     double sprev = 1.0;
@@ -164,7 +143,7 @@ PLP_VX_FN int classify(const Chain<D>& c, const int upto, const double (&u)[D], 
 
 // r = beta - u.p_v of a row on a chain with v valid levels
 template <int D>
-PLP_VX_FN double residual(const Chain<D>& c, const double (&u)[D], const double beta) {
+PLP_ENUM_FN double residual(const Chain<D>& c, const double (&u)[D], const double beta) {
     double r = beta;
 #pragma unroll
     for (int l = 0; l < D - 1; ++l)
@@ -174,7 +153,7 @@ PLP_VX_FN double residual(const Chain<D>& c, const double (&u)[D], const double 
 
 // the longest valid prefix of the tuple idx[0 .. levels) on the staged rows sU[n][D], sb[n]; h beyond it is 0
 template <int D>
-PLP_VX_FN void build(const double* sU, const double* sb, const int (&idx)[Chain<D>::K], const int levels, Chain<D>& c) {
+PLP_ENUM_FN void build(const double* sU, const double* sb, const int (&idx)[Chain<D>::K], const int levels, Chain<D>& c) {
     c.v = 0;
 #pragma unroll
     for (int l = 0; l < Chain<D>::K; ++l) {
@@ -214,7 +193,7 @@ PLP_VX_FN void build(const double* sU, const double* sb, const int (&idx)[Chain<
 
 // the direction of the line of a full chain
 template <int D>
-PLP_VX_FN void line_dir(const Chain<D>& c, double (&t)[D]) {
+PLP_ENUM_FN void line_dir(const Chain<D>& c, double (&t)[D]) {
     if constexpr (D == 1) {
         t[0] = 1.0;
     } else if constexpr (D == 2) {
@@ -243,7 +222,7 @@ PLP_VX_FN void line_dir(const Chain<D>& c, double (&t)[D]) {
 // The term of the tuple idx (D >= 2): see the head of this file.  `len` is the measure of the tuple's line (the facet area
 // for D = 2), 0 / +inf as the term.
 template <int D>
-PLP_VX_FN double tuple_term(const double* sU, const double* sb, const int n, const int (&idx)[Chain<D>::K], double& len) {
+PLP_ENUM_FN double tuple_term(const double* sU, const double* sb, const int n, const int (&idx)[Chain<D>::K], double& len) {
     Chain<D> c;
     build<D>(sU, sb, idx, D - 1, c);
     const bool full = c.v == D - 1;
@@ -281,7 +260,7 @@ PLP_VX_FN double tuple_term(const double* sU, const double* sb, const int n, con
 
 // h_l of the prefix idx[0 .. l] (0 where it is not valid): the weight of the sums above the table
 template <int D>
-PLP_VX_FN double prefix_h(const double* sU, const double* sb, const int (&idx)[Chain<D>::K], const int l) {
+PLP_ENUM_FN double prefix_h(const double* sU, const double* sb, const int (&idx)[Chain<D>::K], const int l) {
     Chain<D> c;
     build<D>(sU, sb, idx, l + 1, c);
     double h = 0.0;
@@ -292,7 +271,7 @@ PLP_VX_FN double prefix_h(const double* sU, const double* sb, const int (&idx)[C
 }
 
 // D = 1 on the staged rows: the interval, and the rows that own its ends (-1: none)
-PLP_VX_FN double interval(const double* sU, const double* sb, const int n, int& own_lo, int& own_hi) {
+PLP_ENUM_FN double interval(const double* sU, const double* sb, const int n, int& own_lo, int& own_hi) {
     double lo = -inf(), hi = inf();
     own_lo = own_hi = -1;
     for (int j = 0; j < n; ++j) {
@@ -306,7 +285,7 @@ PLP_VX_FN double interval(const double* sU, const double* sb, const int n, int& 
 }
 
 // s^k by repeated multiplication
-PLP_VX_FN double power(const double s, const int k) {
+PLP_ENUM_FN double power(const double s, const int k) {
     double r = 1.0;
     for (int e = 0; e < k; ++e) r = r * s;
     return r;
@@ -316,8 +295,8 @@ PLP_VX_FN double power(const double s, const int k) {
 // A[m_max][D], b[m_max], m rows of them in use, keep: bit i = row i is live; xc[D] or nullptr, scale; area[m_max] or nullptr.
 // work: lds_bytes(D, m_max) bytes.
 template <int D>
-PLP_VX_FN void one(const int m_max, const double* A, const double* b, int m, const uint64_t keep, const double* xc,
-                   const double scale, double& volume, double* area, int& status, double* work) {
+PLP_ENUM_FN void one(const int m_max, const double* A, const double* b, int m, const uint64_t keep, const double* xc,
+                     const double scale, double& volume, double* area, int& status, double* work) {
     double* sU = work;
     double* sb = sU + (size_t)m_max * D;
     double* fterm = sb + m_max;    // the facets' terms of the volume

@@ -27,38 +27,35 @@ void run_d(long long B, int m_max, const double* A, const double* b, const int* 
 // the arguments of plp_extreme_batch without the context; 0, or 2 for a size the kernel does not take
 extern "C" int extreme_host(long long B, int m_max, int d, const double* A, const double* b, const int* m, const uint64_t* keep,
                             int v_max, double* V, int* count, int* basis, int* status) {
-    if (d < 1 || d > plp::extreme::MAX_DIM || m_max < 0 || m_max > plp::extreme::MAX_ROWS || v_max < 1) return 2;
-    switch (d) {
-        case 1: run_d<1>(B, m_max, A, b, m, keep, v_max, V, count, basis, status); break;
-        case 2: run_d<2>(B, m_max, A, b, m, keep, v_max, V, count, basis, status); break;
-        case 3: run_d<3>(B, m_max, A, b, m, keep, v_max, V, count, basis, status); break;
-        default: run_d<4>(B, m_max, A, b, m, keep, v_max, V, count, basis, status); break;
-    }
-    return 0;
+    if (m_max < 0 || m_max > plp::wenum::MAX_ITEMS || v_max < 1) return 2;
+    return plp::wenum::dispatch_dim(
+        d, [&](auto dim) { run_d<decltype(dim)::value>(B, m_max, A, b, m, keep, v_max, V, count, basis, status); });
 }
 
 namespace {
 template <int D>
 long long unrank_mismatches() {
     long long bad = 0;
-    for (int n = D; n <= plp::extreme::MAX_ROWS; ++n) {
+    for (int n = D; n <= plp::wenum::MAX_ITEMS; ++n) {
         int idx[D], got[D];
         for (int k = 0; k < D; ++k) idx[k] = k;
         int r = 0;
         do {
-            plp::extreme::unrank<D>(n, r, got);
+            plp::wenum::unrank<D>(n, r, got);
             for (int k = 0; k < D; ++k) bad += got[k] != idx[k];
             ++r;
-        } while (plp::extreme::next<D>(n, idx));
-        bad += r != plp::extreme::candidates<D>(n);
+        } while (plp::wenum::next<D>(n, idx));
+        bad += r != plp::wenum::candidates<D>(n);
     }
     return bad;
 }
 }  // namespace
 
-// the kernel's unrank() against the sequential rule's next() on every subset of every n <= 64: the number of mismatches
+// unrank() against next() (plp_enum.hpp) on every subset of every n <= 64: the number of mismatches (-1: d not in 1 .. 4)
 extern "C" long long extreme_unrank_mismatches(int d) {
-    return d == 1 ? unrank_mismatches<1>() : d == 2 ? unrank_mismatches<2>() : d == 3 ? unrank_mismatches<3>() : unrank_mismatches<4>();
+    long long bad = -1;
+    plp::wenum::dispatch_dim(d, [&](auto dim) { bad = unrank_mismatches<decltype(dim)::value>(); });
+    return bad;
 }
 
 #ifdef EXTREME_HOST_MAIN

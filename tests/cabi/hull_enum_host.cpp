@@ -27,14 +27,9 @@ void run_d(long long B, int n_max, const double* X, const int* n, const uint64_t
 // the arguments of plp_hull_batch without the context; 0, or 2 for a size the kernel does not take
 extern "C" int hull_enum_host(long long B, int n_max, int d, const double* X, const int* n, const uint64_t* keep, int f_max,
                               double* Ao, double* bo, uint64_t* on, int* count, int* basis, int* status) {
-    if (d < 1 || d > plp::hullenum::MAX_DIM || n_max < 0 || n_max > plp::hullenum::MAX_POINTS || f_max < 1) return 2;
-    switch (d) {
-        case 1: run_d<1>(B, n_max, X, n, keep, f_max, Ao, bo, on, count, basis, status); break;
-        case 2: run_d<2>(B, n_max, X, n, keep, f_max, Ao, bo, on, count, basis, status); break;
-        case 3: run_d<3>(B, n_max, X, n, keep, f_max, Ao, bo, on, count, basis, status); break;
-        default: run_d<4>(B, n_max, X, n, keep, f_max, Ao, bo, on, count, basis, status); break;
-    }
-    return 0;
+    if (n_max < 0 || n_max > plp::wenum::MAX_ITEMS || f_max < 1) return 2;
+    return plp::wenum::dispatch_dim(
+        d, [&](auto dim) { run_d<decltype(dim)::value>(B, n_max, X, n, keep, f_max, Ao, bo, on, count, basis, status); });
 }
 
 #ifdef HULL_HOST_MAIN

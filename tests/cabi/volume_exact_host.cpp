@@ -31,14 +31,9 @@ void run_d(long long B, int m_max, const double* A, const double* b, const int* 
 extern "C" int volume_exact_host(long long B, int m_max, int d, const double* A, const double* b, const int* m,
                                  const uint64_t* keep, const double* xc, const double* scale, double* volume, double* area,
                                  int* status) {
-    if (B < 1 || d < 1 || d > plp::volume_exact::MAX_DIM || m_max < 0 || m_max > plp::volume_exact::MAX_ROWS) return 2;
-    switch (d) {
-        case 1: run_d<1>(B, m_max, A, b, m, keep, xc, scale, volume, area, status); break;
-        case 2: run_d<2>(B, m_max, A, b, m, keep, xc, scale, volume, area, status); break;
-        case 3: run_d<3>(B, m_max, A, b, m, keep, xc, scale, volume, area, status); break;
-        default: run_d<4>(B, m_max, A, b, m, keep, xc, scale, volume, area, status); break;
-    }
-    return 0;
+    if (B < 1 || m_max < 0 || m_max > plp::wenum::MAX_ITEMS) return 2;
+    return plp::wenum::dispatch_dim(
+        d, [&](auto dim) { run_d<decltype(dim)::value>(B, m_max, A, b, m, keep, xc, scale, volume, area, status); });
 }
 
 #ifdef VOLUME_EXACT_HOST_MAIN

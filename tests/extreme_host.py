@@ -4,11 +4,12 @@ kernel against the host build bit for bit, the public extreme_batch against the 
 tests/golden/g29_extreme.npz, the comparison rule and the cap on cases left out of it."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import host_build as hb
+from host_build import ROOT, keep_word, ptr as _p, upper_bound as vmax_for  # noqa: F401
+
 SRC = os.path.join(ROOT, "tests", "cabi", "extreme_host.cpp")
 
 XS_OK, XS_OVERFLOW, XS_EMPTY, XS_FLAT, XS_UNBOUNDED = 0, 1, 2, 3, 4
@@ -26,17 +27,13 @@ UNPINNED_CAP = {"flat": 0.10}
 
 def build(tmpdir, as_path=False):
     """Compiles the host build into tmpdir -> the loaded library, or (as_path) the path of the shared object."""
-    out = os.path.join(str(tmpdir), "libextreme_host.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", out, SRC])
+    out = hb.build(SRC, "libextreme_host.so", tmpdir)
     return out if as_path else load(out)
 
 
 def build_program(tmpdir):
     """The stand-alone program (-DEXTREME_HOST_MAIN) under -fsanitize=address,undefined -> its path."""
-    out = os.path.join(str(tmpdir), "extreme_host_san")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-DEXTREME_HOST_MAIN", "-o", out, SRC])
-    return out
+    return hb.build_program(SRC, "EXTREME_HOST_MAIN", "extreme_host_san", tmpdir)
 
 
 def load(out):
@@ -47,15 +44,6 @@ def load(out):
     L.extreme_unrank_mismatches.restype = C.c_longlong
     L.extreme_unrank_mismatches.argtypes = [C.c_int]
     return L
-
-
-def _p(a):
-    return None if a is None else C.c_void_p(a.ctypes.data)
-
-
-def vmax_for(d, n):
-    """The upper-bound theorem, as batch.extreme_batch sizes v_max (written out again: the test does not ask the code)."""
-    return max(1, 2 if d == 1 else n if d == 2 else 2 * n - 4 if d == 3 else n * (n - 3) // 2)
 
 
 def run(L, A, b, m=None, keep=None, v_max=None, basis=True):
@@ -72,11 +60,6 @@ def run(L, A, b, m=None, keep=None, v_max=None, basis=True):
     rc = L.extreme_host(B, m_max, d, _p(A), _p(b), _p(m), _p(keep), v_max, _p(V), _p(count), _p(bas), _p(status))
     assert rc == 0
     return V, count, bas, status
-
-
-def keep_word(mask):
-    """bool[m] -> the uint64 keep word."""
-    return np.uint64(sum(1 << i for i in np.nonzero(mask)[0]))
 
 
 # ------------------------------------------------------------------------------------------------ the fixture

@@ -4,11 +4,12 @@ kernel against the host build bit for bit, the public hull_batch against the fix
 tests/golden/g30_hull.npz, the comparison rule and the cap on cases left out of it."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import host_build as hb
+from host_build import ROOT, keep_word, same_bits, ptr as _p, upper_bound as fmax_for  # noqa: F401
+
 SRC = os.path.join(ROOT, "tests", "cabi", "hull_enum_host.cpp")
 
 HS_OK, HS_OVERFLOW, HS_FLAT = 0, 1, 2
@@ -25,17 +26,13 @@ UNPINNED_CAP = 0.02
 
 def build(tmpdir, as_path=False):
     """Compiles the host build into tmpdir -> the loaded library, or (as_path) the path of the shared object."""
-    out = os.path.join(str(tmpdir), "libhull_enum_host.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", out, SRC])
+    out = hb.build(SRC, "libhull_enum_host.so", tmpdir)
     return out if as_path else load(out)
 
 
 def build_program(tmpdir):
     """The stand-alone program (-DHULL_HOST_MAIN) under -fsanitize=address,undefined -> its path."""
-    out = os.path.join(str(tmpdir), "hull_enum_host_san")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-DHULL_HOST_MAIN", "-o", out, SRC])
-    return out
+    return hb.build_program(SRC, "HULL_HOST_MAIN", "hull_enum_host_san", tmpdir)
 
 
 def load(out):
@@ -44,15 +41,6 @@ def load(out):
     L.hull_enum_host.argtypes = [C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     return L
-
-
-def _p(a):
-    return None if a is None else C.c_void_p(a.ctypes.data)
-
-
-def fmax_for(d, n):
-    """The upper-bound theorem, as batch.hull_batch sizes f_max (written out again: the test does not ask the code)."""
-    return max(1, 2 if d == 1 else n if d == 2 else 2 * n - 4 if d == 3 else n * (n - 3) // 2)
 
 
 def run(L, X, n=None, keep=None, f_max=None, basis=True):
@@ -71,18 +59,9 @@ def run(L, X, n=None, keep=None, f_max=None, basis=True):
     return dict(A=A, b=b, on=on, count=count, basis=bas, status=status)
 
 
-def keep_word(mask):
-    """bool[n] -> the uint64 keep word."""
-    return np.uint64(sum(1 << int(i) for i in np.nonzero(mask)[0]))
-
-
 def bits(word):
     """a uint64 word -> the set of its bit positions."""
     return {i for i in range(64) if (int(word) >> i) & 1}
-
-
-def same_bits(a, b):
-    return np.array_equal(np.ascontiguousarray(a).view(np.int64), np.ascontiguousarray(b).view(np.int64))
 
 
 def same_result(got, want, basis=True):

@@ -15,6 +15,8 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 from polytope_amd import _lib, batch  # noqa: E402
 from polytope_amd.synth import random_hpolytopes  # noqa: E402
 import extreme_host as xh  # noqa: E402
+import cap_sweep  # noqa: E402
+from host_build import same_bits  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -27,10 +29,6 @@ def L(tmp_path_factory):
 def dev(*arrays):
     import torch
     return [None if a is None else torch.as_tensor(a).to("cuda:0") for a in arrays]
-
-
-def same_bits(a, b):
-    return np.array_equal(np.ascontiguousarray(a).view(np.int64), np.ascontiguousarray(b).view(np.int64))
 
 
 def raw_batch(B, m_max, d, seed):
@@ -104,6 +102,21 @@ def test_overflow_keeps_the_first_vertices():
     assert same_bits(cut["V"], full["V"][:, :3]) and np.array_equal(cut["basis"], full["basis"][:, :3])
     assert batch.extreme_batch(cube, one, v_max=8, reduce=False)["status"][0] == batch.XS_OK
     assert set(map(tuple, full["V"][0])) == {(x, y, z) for x in (-1.0, 1.0) for y in (-1.0, 1.0) for z in (-1.0, 1.0)}
+
+
+def test_cap_sweep_equals_the_host_build(L):
+    """Overflow reached in a LATER round of 64 (tests/cap_sweep.py; the host build's own sweep is in test_extreme_host.py):
+    at every cap from 1 to the full count + 1 the kernel's list is the host build's bit for bit, for the member twice in
+    one launch."""
+    for A, b in cap_sweep.extreme_members():
+        A2, b2 = np.stack([A, A]), np.stack([b, b])
+        full = int(xh.run(L, A[None], b[None])[1][0])
+        for k in range(1, full + 2):
+            wV, wc, wb, ws = xh.run(L, A2, b2, v_max=k)
+            V, count, bas, status = raw(A2, b2, None, None, k)
+            assert np.array_equal(status, ws) and np.array_equal(count, wc), (k, count, status)
+            assert np.array_equal(bas, wb) and same_bits(V, wV), k
+            assert (ws == (xh.XS_OVERFLOW if k < full else xh.XS_OK)).all() and (wc == min(k, full)).all()
 
 
 # ------------------------------------------------------------------------------------------ the fixture, reduce=True

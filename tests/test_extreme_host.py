@@ -24,6 +24,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import extreme_host as xh  # noqa: E402
+import cap_sweep  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -113,6 +114,17 @@ def test_status_and_overflow(L):
     b = np.r_[np.ones(6), 0.0, 2.0][None]    # row 6 (dropped) would cut the cube in half, row 7 cuts one corner off
     V7, c7, b7, s7 = xh.run(L, A, b, keep=keep)
     assert s7[0] == xh.XS_OK and c7[0] == 10 and set(np.unique(b7[0, :10])) == {0, 1, 2, 3, 4, 5, 7}
+
+
+def test_cap_sweep_overflow_in_a_later_round(L):
+    """Every cap from 1 to the full count + 1 on two members whose candidates take two rounds of 64 in the kernel: the
+    12-gon's last vertex lies on rows (10, 11), subset 65 of 66; the (9, 3) polytope's last one comes from a subset of rank
+    >= 64 too.  (The host build has no rounds: this pins the list the kernel is held against in tests/test_extreme_gpu.py.)"""
+    (A, b), (A3, b3) = cap_sweep.extreme_members()
+    V, full, basis = cap_sweep.check_extreme(A, b, lambda A, b, k: xh.run(L, A, b, v_max=k))
+    assert full == 12 and basis[11].tolist() == [10, 11] and np.allclose(np.linalg.norm(V[:12], axis=1), 1.0 / np.cos(np.pi / 12))
+    V, full, basis = cap_sweep.check_extreme(A3, b3, lambda A, b, k: xh.run(L, A, b, v_max=k))
+    assert cap_sweep.subset_rank(basis[full - 1].tolist(), 9) >= 64 > cap_sweep.subset_rank(basis[0].tolist(), 9)
 
 
 def test_stand_alone_program_under_sanitizers(tmp_path, cases):

@@ -16,6 +16,8 @@ from polytope_amd import _lib, batch  # noqa: E402
 from polytope_amd.synth import random_hpolytopes  # noqa: E402
 import extreme_host as xh  # noqa: E402
 import hull_host as hh  # noqa: E402
+import cap_sweep  # noqa: E402
+from cap_sweep import subset_rank  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -79,14 +81,17 @@ def test_kernel_equals_the_host_build(L, n_max, d):
         assert later > 0
 
 
-def subset_rank(idx, n):
-    """The lexicographic rank of the increasing subset idx among the len(idx)-subsets of range(n)."""
-    from math import comb
-    r, prev = 0, -1
-    for k, c in enumerate(idx):
-        r += sum(comb(n - 1 - j, len(idx) - 1 - k) for j in range(prev + 1, c))
-        prev = c
-    return r
+def test_cap_sweep_equals_the_host_build(L):
+    """Overflow reached in a LATER round of 64 (tests/cap_sweep.py; the host build's own sweep is in test_hull_host.py): at
+    every cap from 1 to the full count + 1 the kernel's list is the host build's bit for bit, for the set twice in one
+    launch."""
+    for X in cap_sweep.hull_members():
+        X2 = np.stack([X, X])
+        full = int(hh.run(L, X[None])["count"][0])
+        for k in range(1, full + 2):
+            want = hh.run(L, X2, f_max=k)
+            assert hh.same_result(raw(X2, None, None, k), want) is None, k
+            assert (want["status"] == (hh.HS_OVERFLOW if k < full else hh.HS_OK)).all() and (want["count"] == min(k, full)).all()
 
 
 def test_overflow_on_the_cube():

@@ -20,6 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import hull_host as hh  # noqa: E402
+import cap_sweep  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -143,6 +144,18 @@ def test_overflow_keeps_the_first_facets(L):
     assert np.all(cut["status"] == hh.HS_OVERFLOW) and np.all(cut["count"] == 4)
     assert hh.same_bits(cut["A"], full["A"][:, :4]) and hh.same_bits(cut["b"], full["b"][:, :4])
     assert np.array_equal(cut["on"], full["on"][:, :4]) and np.array_equal(cut["basis"], full["basis"][:, :4])
+
+
+def test_cap_sweep_overflow_in_a_later_round(L):
+    """Every cap from 1 to the full count + 1 on two sets whose candidates take two rounds of 64 in the kernel: the
+    12-gon's last facet is the edge (10, 11), subset 65 of 66; the last facet of the nine points comes from a subset of rank
+    >= 64 too.  (The host build has no rounds: this pins the list the kernel is held against in tests/test_hull_gpu.py.)"""
+    gon, pts = cap_sweep.hull_members()
+    whole, full = cap_sweep.check_hull(gon, lambda X, k: hh.run(L, X, f_max=k))
+    assert full == 12 and whole["basis"][0, 11].tolist() == [10, 11]
+    assert np.allclose(whole["b"][0, :12], np.cos(np.pi / 12)) and all(len(hh.bits(w)) == 2 for w in whole["on"][0, :12])
+    whole, full = cap_sweep.check_hull(pts, lambda X, k: hh.run(L, X, f_max=k))
+    assert cap_sweep.subset_rank(whole["basis"][0, full - 1].tolist(), 9) >= 64 > cap_sweep.subset_rank(whole["basis"][0, 0].tolist(), 9)
 
 
 def test_shift_and_power_of_two_scale_change_no_bit(L):

@@ -7,11 +7,12 @@ import ctypes as C
 import itertools
 import math
 import os
-import subprocess
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import host_build as hb
+from host_build import ROOT, ptr as _p
+
 SRC = os.path.join(ROOT, "tests", "cabi", "volume_exact_host.cpp")
 
 VS_OK, VS_UNBOUNDED, VS_EMPTY, VS_FLAT = 0, 1, 2, 3
@@ -25,17 +26,13 @@ MISS_CAP = {"flat": 0.10}
 
 def build(tmpdir, as_path=False):
     """Compiles the host build into tmpdir -> the loaded library, or (as_path) the path of the shared object."""
-    out = os.path.join(str(tmpdir), "libvolume_exact_host.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", out, SRC])
+    out = hb.build(SRC, "libvolume_exact_host.so", tmpdir)
     return out if as_path else load(out)
 
 
 def build_program(tmpdir):
     """The stand-alone program (-DVOLUME_EXACT_HOST_MAIN) under -fsanitize=address,undefined -> its path."""
-    out = os.path.join(str(tmpdir), "volume_exact_host_san")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-DVOLUME_EXACT_HOST_MAIN", "-o", out, SRC])
-    return out
+    return hb.build_program(SRC, "VOLUME_EXACT_HOST_MAIN", "volume_exact_host_san", tmpdir)
 
 
 def load(out):
@@ -43,10 +40,6 @@ def load(out):
     L.volume_exact_host.restype = C.c_int
     L.volume_exact_host.argtypes = [C.c_longlong, C.c_int, C.c_int] + [C.c_void_p] * 9
     return L
-
-
-def _p(a):
-    return None if a is None else C.c_void_p(a.ctypes.data)
 
 
 def prep(A, b, m=None, keep=None, xc=None, scale=None):
