@@ -566,6 +566,114 @@ PLP_LANE_FN void ratio_row0(const double a0, const double a1, const double a2, c
     bi = better ? i : bi;
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// The ratio test over a SHARE of the rows of a strided tile: the one row loop of the device kernels (plp_reduce_lane.hpp:
+// every tile shape, the relaxed redundancy LPs, the stand-alone boxes) and of tests/cabi/lane_ratio_host.cpp.
+// Element (row i, column k) at pA[(i * D + k) * LS], beta_i at pbeta[i * LS].  The share is rows i0 .. i0 + cnt - 1
+// (cnt a multiple of PLP_LANE_CH, the rows of one trip; on the device cnt is wave-uniform, i0 the lane's own).
+#ifndef PLP_LANE_CH
+#define PLP_LANE_CH 4   // rows per trip of the ratio loop (the fewest rows a lane tests: 16 / 4 in quad mode)
+#endif
+
+// bs / bd / bi <- sl / ad / i in the lanes where `elig & closer` holds.  Device: three moves under the compare's mask (two 64-bit,
+// one 32-bit whose source is the wave-uniform row number in a scalar register) instead of five selects and the add that
+// forms a per-lane row number; the mask goes through the scalar unit, which this VALU-bound kernel leaves idle.
+// (s_and_saveexec writes SCC; nothing inside needs a wait state: EXEC is written by the scalar unit, the moves read VGPRs
+// the compiler has waited for.)  PLP_LANE_SELECT_LATCH: the plain form (A/B).
+PLP_LANE_FN void latch_row(const bool elig, const bool closer, const double sl, const double ad, const int i, double& bs,
+                           double& bd, int& bi) {
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(PLP_LANE_SELECT_LATCH)
+    // (one vote per compare, joined on the scalar unit: the vote of `elig & closer` goes through a 0 / 1 select and a
+    // second compare)
+    const unsigned long long mask = __builtin_amdgcn_ballot_w64(elig) & __builtin_amdgcn_ballot_w64(closer);
+    unsigned long long saved;
+    asm("s_and_saveexec_b64 %[sv], %[m]\n\t"
+        "v_mov_b64 %[bs], %[sl]\n\t"
+        "v_mov_b64 %[bd], %[ad]\n\t"
+        "v_mov_b32 %[bi], %[i]\n\t"
+        "s_mov_b64 exec, %[sv]"
+        : [bs] "+v"(bs), [bd] "+v"(bd), [bi] "+v"(bi), [sv] "=&s"(saved)
+        : [m] "s"(mask), [sl] "v"(sl), [ad] "v"(ad), [i] "s"(i)
+        : "scc");
+#else
+    const bool better = elig & closer;
+    bs = better ? sl : bs;
+    bd = better ? ad : bd;
+    bi = better ? i : bi;
+#endif
+}
+
+// beta + 0.1 in the lanes whose LP relaxes this row (:1149), beta elsewhere: one add under the compare's mask (device)
+PLP_LANE_FN double relax_row(const bool at, double beta) {
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(PLP_LANE_SELECT_LATCH)
+    const unsigned long long mask = __builtin_amdgcn_ballot_w64(at);
+    unsigned long long saved;
+    asm("s_and_saveexec_b64 %[sv], %[m]\n\t"
+        "v_add_f64 %[b], %[b], %[c]\n\t"
+        "s_mov_b64 exec, %[sv]"
+        : [b] "+v"(beta), [sv] "=&s"(saved)
+        : [m] "s"(mask), [c] "s"(0.1)
+        : "scc");
+    return beta;
+#else
+    return at ? beta + 0.1 : beta;
+#endif
+}
+
+// RATIO_WALK: slack (beta_i - a_i.x)+ at the point xv.  RATIO_FIRST: from x' = 0, the slack is beta_i (ratio_row0).
+// RATIO_AXIS: from x' = 0 along dk e_kax, dk = -1 or +1 -- the first pass of a box LP: a_i.d is dk a_i,kax, one column read
+// and no dot product.  For finite rows that is the number ratio_row0 forms (a product with +-1 is exact, the two other
+// terms of its chain add +-0), up to the sign of a zero, which is never above tolp > 0 and so never latched.
+enum : int { RATIO_WALK = 0, RATIO_FIRST = 1, RATIO_AXIS = 2 };
+
+// RELAX: row krv's right-hand side is beta + 0.1 (krv: this lane's).  dv / xv: direction and point (four slots, D used;
+// d <= 3 is embedded in R^3).  Rows are latched by their number INSIDE the share, wave-uniform on the device; the lane's
+// own i0 is added once at the end, so that bi is the absolute row number the callers' tie rule compares.
+template <int D, int LS, int MODE, bool RELAX>
+PLP_LANE_FN void ratio_rows(const double* pA, const double* pbeta, const int i0, const int cnt, const int krv,
+                            const double (&dv)[4], const double (&xv)[4], const int kax, const double dk, const double tolp,
+                            double& bs, double& bd, int& bi) {
+    static_assert(D >= 1 && D <= 4 && (D < 4 || MODE == RATIO_WALK), "R^4 has no peeled first pass");
+    const double* ra = pA + i0 * D * LS + (MODE == RATIO_AXIS ? kax * LS : 0);
+    const double* rb = pbeta + i0 * LS;
+    const int krel = krv - i0;
+    int li = -1;
+    for (int ch = 0; ch < cnt; ch += PLP_LANE_CH) {
+#pragma unroll
+        for (int r = 0; r < PLP_LANE_CH; ++r) {
+            const double* a = ra + (r * D) * LS;
+            double beta = rb[r * LS];
+            if constexpr (RELAX) beta = relax_row(ch + r == krel, beta);
+            double ad, sl;
+            if constexpr (MODE == RATIO_AXIS) {
+                ad = dk * a[0];
+                sl = fmax(beta, 0.0);
+            } else {
+                const double a0 = a[0];
+                const double a1 = D > 1 ? a[(D > 1 ? 1 : 0) * LS] : 0.0;
+                const double a2 = D > 2 ? a[(D > 2 ? 2 : 0) * LS] : 0.0;
+                // the slack in ONE chain, beta - a.x = fma(-a2, x2, fma(-a1, x1, fma(-a0, x0, beta))): one instruction fewer than
+                // a dot product and a subtraction, rounded differently in the last place (ratio_row / ratio_row4, which the
+                // support kernel and the host engine tests use, keep the subtraction); at x' = 0 it is beta exactly, so the
+                // first pass still finds what this one would
+                if constexpr (D == 4) {
+                    const double a3 = a[(D > 3 ? 3 : 0) * LS];
+                    ad = dot4(a0, a1, a2, a3, dv[0], dv[1], dv[2], dv[3]);
+                    sl = fmax(fma(-a3, xv[3], fma(-a2, xv[2], fma(-a1, xv[1], fma(-a0, xv[0], beta)))), 0.0);
+                } else {
+                    ad = dot3(a0, a1, a2, dv[0], dv[1], dv[2]);
+                    sl = MODE == RATIO_FIRST ? fmax(beta, 0.0) : fmax(fma(-a2, xv[2], fma(-a1, xv[1], fma(-a0, xv[0], beta))), 0.0);
+                }
+            }
+            // sl / ad < bs / bd  <=>  sl * bd < bs * ad  (ratio_row); strict: the first row keeps a tie
+            latch_row(ad > tolp, sl * bd < bs * ad, sl, ad, ch + r, bs, bd, li);
+        }
+        ra += PLP_LANE_CH * D * LS;
+        rb += PLP_LANE_CH * LS;
+    }
+    bi = li < 0 ? bi : li + i0;
+}
+
 // The whole LP in one lane, M row slots, BETA(i) the right-hand sides (>= 0).
 // PASS(): called at the top of every ratio test (device: keeps loop-invariant per-row predicates of BETA from being
 // hoisted out of the walk).

@@ -32,10 +32,6 @@
 
 namespace plp {
 
-#ifndef PLP_LANE_CH
-#define PLP_LANE_CH 4   // rows per trip of the ratio loop (the fewest rows a lane tests: 16 / 4 in quad mode)
-#endif
-
 constexpr int LN_ROWS = 16;   // row slots per polytope (ROWS = 32: polytopes of 17..32 rows, e.g. the stack of Polytope.intersect, ref :268-275)
 // GS lanes per polytope (4 / 8 / 16), R = 16 / GS rows per lane in the lane-group stages, NG = 64 / GS polytopes per tile
 // (= per wavefront).  GS = 4 is the throughput form; 8 and 16 put fewer polytopes on a wavefront and finish a tile in
@@ -328,7 +324,7 @@ __device__ __forceinline__ void reduce_lane_tile(
     };
     zero_dead(((unsigned)(live >> row0) & RMASK));
     int flags = fulldim ? 0 : (RF_EMPTY | (f1open ? RF_F1OPEN : 0));
-    int nlp = 1;
+    int nlp = 1, presolved = 0;
     uint64_t keep = 0ull;
     int stage = 0;  // 0 done, 1 needs the box, 2 needs the redundancy LPs
     if (fulldim) {
@@ -344,11 +340,14 @@ __device__ __forceinline__ void reduce_lane_tile(
     // test over its half / quarter of the row slots, and the candidates meet through one / two DPP exchanges (smaller
     // ratio, on ties the lower row: the row a single lane would have found first).  `nparts` is wave-uniform.
     // pA / pbeta: the polytope's rows / right-hand sides in the interleaved tile; RELAX: row krv's right-hand side + 0.1
-    // (:1149) -- an add of 0.1 or 0, not a select between a constant and the LDS value (that becomes a branch around the load).
+    // (:1149) -- an add of 0.1 under the row compare's mask (lane::relax_row), not a select between a constant and the LDS
+    // value (that becomes a branch around the load).
     using LpState = std::conditional_t<D == 4, lane::Lp4, lane::Lp3>;   // d <= 3: the walk in R^3 (lower dimensions embedded); d = 4: in R^4
+    // kax / dk (box LPs, RELAX false: c = -dk e_kax): the walk's first pass reads one column (lane::RATIO_AXIS).
     auto lane_solve = [&](LpState& S, const double (&cv)[4], const bool go_, const double* pA, const double* pbeta, auto relax_tag,
-                          int krv, const int nparts, const int part) {
+                          int krv, const int nparts, const int part, const int kax, const double dk) {
         constexpr bool RELAX = decltype(relax_tag)::value;
+        constexpr int FIRST = RELAX ? lane::RATIO_FIRST : lane::RATIO_AXIS;   // the walk's first pass: x' = 0, every slack is its beta
         const int cnt = rows / nparts;   // wave-uniform
         const int i0 = part * cnt;
         auto row_of = [&](const double* base, double& a0, double& a1, double& a2, double& a3) {
@@ -357,32 +356,12 @@ __device__ __forceinline__ void reduce_lane_tile(
             a2 = D > 2 ? base[(D > 2 ? 2 : 0) * LS] : 0.0;
             a3 = D > 3 ? base[(D > 3 ? 3 : 0) * LS] : 0.0;
         };
-        // the ratio test of one pass: my share of the rows, then the exchange with the other lanes of the LP
-        auto ratio = [&](auto x0_tag, const double (&dv)[4], const double (&xv)[4], double tolp, double& bs, double& bd, int& bi) {
-            constexpr bool X0 = decltype(x0_tag)::value;   // the walk's first pass: x' = 0, every slack is its beta
+        // the ratio test of one pass: my share of the rows (the loop is lane::ratio_rows), then the exchange with the other
+        // lanes of the LP
+        auto ratio = [&](auto mode_tag, const double (&dv)[4], const double (&xv)[4], double tolp, double& bs, double& bd, int& bi) {
+            constexpr int MODE = decltype(mode_tag)::value;
             if constexpr (RELAX) asm volatile("" : "+v"(krv));   // (keeps the per-row compares inside the walk)
-            const double* ra = pA + i0 * D * LS;
-            const double* rb_ = pbeta + i0 * LS;
-            int ic = i0;
-            for (int ch = 0; ch < cnt; ch += PLP_LANE_CH) {
-#pragma unroll
-                for (int r = 0; r < PLP_LANE_CH; ++r) {
-                    double a0, a1, a2, a3;
-                    row_of(ra + (r * D) * LS, a0, a1, a2, a3);
-                    double beta = rb_[r * LS];
-                    if constexpr (RELAX) beta = beta + ((ic + r == krv) ? 0.1 : 0.0);
-                    if constexpr (D == 4)
-                        lane::ratio_row4(a0, a1, a2, a3, beta, ic + r, dv[0], dv[1], dv[2], dv[3], xv[0], xv[1], xv[2], xv[3], tolp,
-                                         bs, bd, bi);
-                    else if constexpr (X0)
-                        lane::ratio_row0(a0, a1, a2, beta, ic + r, dv[0], dv[1], dv[2], tolp, bs, bd, bi);
-                    else
-                        lane::ratio_row(a0, a1, a2, beta, ic + r, dv[0], dv[1], dv[2], xv[0], xv[1], xv[2], tolp, bs, bd, bi);
-                }
-                ra += PLP_LANE_CH * D * LS;
-                rb_ += PLP_LANE_CH * LS;
-                ic += PLP_LANE_CH;
-            }
+            lane::ratio_rows<D, LS, MODE, RELAX>(pA, pbeta, i0, cnt, krv, dv, xv, kax, dk, tolp, bs, bd, bi);
             auto meet = [&](auto ctrl) {
                 constexpr int CTRL = decltype(ctrl)::value;
                 const double ps = dpp_d<CTRL>(bs), pd = dpp_d<CTRL>(bd);
@@ -403,7 +382,7 @@ __device__ __forceinline__ void reduce_lane_tile(
                 [&](double d0, double d1, double d2, double d3, double x0, double x1, double x2, double x3, double tolp, double& bs,
                     double& bd, int& bi) {
                     const double dv[4] = {d0, d1, d2, d3}, xv[4] = {x0, x1, x2, x3};
-                    ratio(std::false_type{}, dv, xv, tolp, bs, bd, bi);
+                    ratio(std::integral_constant<int, lane::RATIO_WALK>{}, dv, xv, tolp, bs, bd, bi);
                 },
                 any_lane);
         } else {
@@ -415,11 +394,11 @@ __device__ __forceinline__ void reduce_lane_tile(
                 },
                 [&](double d0, double d1, double d2, double x0, double x1, double x2, double tolp, double& bs, double& bd, int& bi) {
                     const double dv[4] = {d0, d1, d2, 0.0}, xv[4] = {x0, x1, x2, 0.0};
-                    ratio(std::false_type{}, dv, xv, tolp, bs, bd, bi);
+                    ratio(std::integral_constant<int, lane::RATIO_WALK>{}, dv, xv, tolp, bs, bd, bi);
                 },
                 [&](double d0, double d1, double d2, double tolp, double& bs, double& bd, int& bi) {
                     const double dv[4] = {d0, d1, d2, 0.0}, xv[4] = {0.0, 0.0, 0.0, 0.0};
-                    ratio(std::true_type{}, dv, xv, tolp, bs, bd, bi);
+                    ratio(std::integral_constant<int, FIRST>{}, dv, xv, tolp, bs, bd, bi);
                 },
                 any_lane);
         }
@@ -462,7 +441,7 @@ __device__ __forceinline__ void reduce_lane_tile(
             const double cs = up ? -1.0 : 1.0;
             LpState S;
             const double cv[4] = {kx == 0 ? cs : 0.0, kx == 1 ? cs : 0.0, kx == 2 ? cs : 0.0, kx == 3 ? cs : 0.0};
-            lane_solve(S, cv, mine, myA, myan, std::false_type{}, -1, nparts, part);
+            lane_solve(S, cv, mine, myA, myan, std::false_type{}, -1, nparts, part, kx < D ? kx : 0, up ? 1.0 : -1.0);
             double xck = 0.0;
 #pragma unroll
             for (int kk = 0; kk < D; ++kk) xck = (kk == kx) ? xc[kk] : xck;
@@ -555,7 +534,7 @@ __device__ __forceinline__ void reduce_lane_tile(
             for (int k = 0; k < R; ++k) cert |= spread_rows<R, GS>(grp_ballot(((okb >> k) & 1u) != 0u, g)) << k;
             keep |= cert;
             todo &= ~cert;
-            ctr_add(ctr, -__popcll(cert), g.gl == 0);
+            presolved = __popcll(cert);   // (no simplex ran for these: taken off the counter at the end)
         }
 #endif
         __syncthreads();
@@ -610,7 +589,7 @@ __device__ __forceinline__ void reduce_lane_tile(
 #pragma unroll
             for (int kk = 0; kk < D; ++kk) c[kk] = -pA[(kr * D + kk) * LS];   // f = -A[k,:]  (:1145)
             LpState S;
-            lane_solve(S, c, mine, pA, pan, std::true_type{}, kr, nparts, part);
+            lane_solve(S, c, mine, pA, pan, std::true_type{}, kr, nparts, part, 0, 0.0);
             // objective - h[k] (:1156):  -fun - hk = (a_k.xc + a_k.x') - hk = a_k.x' - (hk - a_k.xc),  hk = (b_k + 0.1) - 0.1
             // after its round trip (:1149-1151):  hk - a_k.xc = beta_k up to the rounding of that round trip (1e-17)
             double akx = -lane::dot3(c[0], c[1], c[2], S.x0, S.x1, S.x2);
@@ -642,7 +621,7 @@ __device__ __forceinline__ void reduce_lane_tile(
         (flags_out + tile)[gib] = flags;
         (nlp_out + tile)[gib] = nlp;
     }
-    ctr_add(ctr, nlp, valid & (g.gl == 0));   // every LP the reference issues, less the presolved ones
+    ctr_add(ctr, nlp - presolved, valid & (g.gl == 0));   // every LP the reference issues, less the presolved ones: one add per tile
     // Polytopes handed back (an LP that needs Bland's rule, dependent active rows; PLP_REDUCE_RETRY_ALL=1: all of them) are
     // redone HERE by the general engine, four at a time on the wavefront's 64 lanes -- the launch is complete, no second
     // pass follows it.  Rare: the call sits behind a wave-uniform branch and is not inlined.
