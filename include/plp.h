@@ -23,9 +23,14 @@
  *   - function return value: PLP_OK, or PLP_E* for API misuse / HIP errors
  *     (plp_last_error() has the text).  Nothing throws across this boundary.
  *   - "_dev" variants take DEVICE pointers and a HIP stream (void* = hipStream_t, NULL =
- *     default stream), enqueue the work and return without synchronising.  The plain
- *     variants take HOST pointers, copy in/out through the context's scratch buffers and
- *     block until results are host-visible.
+ *     default stream), enqueue the work and return without synchronising.  Every launch,
+ *     memset and copy of a "_dev" call goes to `stream`, and the host does not wait for any
+ *     of it: the results are ordered like any other work on that stream.  (A scratch buffer
+ *     of the context that has to grow is freed after its last user has finished: the call
+ *     then waits for that work, on `stream` or, for the one buffer the streams share, on the
+ *     stream that used it last; a 17th stream on one context waits for the device once.)
+ *     The plain variants take HOST pointers, copy in/out through the context's scratch
+ *     buffers and block until results are host-visible.
  *   - a plp_ctx is not thread safe; use one per thread (the reference is single-threaded).
  */
 #ifndef PLP_H
