@@ -2,14 +2,12 @@
 // the Chebyshev LP on the one-LP-per-wavefront engine (plp_wide.hpp), then the 2d LPs min / max x_k from its centre
 //   WDENSE (d = 5..13): on the same dense engine (wide::solve_dense: wave-uniform pivots, Bland's rule inside),
 //   otherwise (d = 14..16): WITHOUT a stored dictionary (plp_lazy.hpp).
-// d = 9..16 always come here, d = 5..8 with more than 32 rows (the lane-group kernel bbox_r_kernel holds one or two such
-// polytopes per wavefront and pays select chains for the pivot column).  Same contract as bbox_r_kernel
+// d = 9..16 always come here, d = 5..8 by the rule of plan_bbox (plp_lp_plan.hpp: the lane-group kernel bbox_r_kernel holds
+// one or two polytopes of more than 32 rows per wavefront and pays select chains for the pivot column).  Same contract as bbox_r_kernel
 // (plp_cheby_r_impl.hpp, d <= 8): status 0 = lb / ub hold the box (+-inf where an LP is unbounded, :1376 / :1398),
 // status 1 = not handled here (empty / flat / unbounded-ball polytopes, LPs that ask for Bland's rule or run past the
 // step limit): the caller solves the generic LPs for those.
-#include <stdlib.h>
-
-#include "plp_kernels.hpp"
+#include "plp_lp_launch.hpp"
 #include "plp_lazy.hpp"
 #include "plp_wide.hpp"
 
@@ -222,59 +220,19 @@ __global__ __launch_bounds__(64 * NW) void bbox_wsplit_kernel(long long B, int m
     if (centre && (w == 0) && lane < D) centre[(size_t)p * D + lane] = ok ? sx[lane] : qnan;
 }
 
-#ifndef PLP_BBOX_WSPLIT_MAXB
-// Measured (scripts/debug/bbox_wsplit_sweep.py, ms in use / four wavefronts per polytope): (64,8) B = 1 0.094 / 0.051, 500 0.116 /
-// 0.071, 2 000 0.168 / 0.129; (32,6) 500 0.056 / 0.041; (64,12) 500 0.136 / 0.077, 2 000 0.168 / 0.151, 4 000 0.228 / 0.258;
-// (64,16) 1 000 0.144 / 0.098
-#define PLP_BBOX_WSPLIT_MAXB 2000
-#endif
-#ifndef PLP_BBOX_WDENSE_MAXD
-#define PLP_BBOX_WDENSE_MAXD 13  // (as PLP_REDUCE_WDENSE_MAXD: beyond, the LPs are too short to pay for a dictionary reload)
-#endif
-
-template <int D>
-static int launch_bbox_lazy_d(long long B, int m_max, const double* A, const double* b, const int* mrows, double* lb,
-                              double* ub, int* status, hipStream_t st, BoxHandover* ho) {
-    if (B > 2147483647ll) return 1;
-    signed char* b8 = ho ? ho->basis8 : nullptr;
-    double* ctr = ho ? ho->centre : nullptr;
-    if (ho) ho->mode = (b8 && ctr) ? 1 : 0;
-    const char* wd = getenv("PLP_BBOX_WDENSE");  // 0 / 1: never / always the dense engine for the 2d LPs (A/B)
-    // small batches: four wavefronts per polytope (PLP_BBOX_WSPLIT=0 / 1: never / always; PLP_BBOX_WSPLIT_MAXB)
-    const char* ws = getenv("PLP_BBOX_WSPLIT");
-    const char* wb = getenv("PLP_BBOX_WSPLIT_MAXB");
-    const long long maxb = wb ? atoll(wb) : PLP_BBOX_WSPLIT_MAXB;
-    if ((ws && ws[0] == '1') || (!(ws && ws[0] == '0') && B <= maxb)) {
-        if (wd ? wd[0] == '1' : (D <= PLP_BBOX_WDENSE_MAXD))
-            hipLaunchKernelGGL((bbox_wsplit_kernel<D, 4, true>), dim3((unsigned)B), dim3(256), 0, st, B, m_max, A, b, mrows, lb, ub,
-                               status, b8, ctr);
-        else
-            hipLaunchKernelGGL((bbox_wsplit_kernel<D, 4, false>), dim3((unsigned)B), dim3(256), 0, st, B, m_max, A, b, mrows, lb, ub,
-                               status, b8, ctr);
-        return 0;
-    }
-    if (wd ? wd[0] == '1' : (D <= PLP_BBOX_WDENSE_MAXD))
-        hipLaunchKernelGGL((bbox_lazy_kernel<D, true>), dim3((unsigned)(B < 1 ? 1 : B)), dim3(64), 0, st, B, m_max, A, b, mrows,
-                           lb, ub, status, b8, ctr);
-    else
-        hipLaunchKernelGGL((bbox_lazy_kernel<D, false>), dim3((unsigned)(B < 1 ? 1 : B)), dim3(64), 0, st, B, m_max, A, b, mrows,
-                           lb, ub, status, b8, ctr);
-    return 0;
-}
-
-#define PLP_CASE_BL(K) case K: return launch_bbox_lazy_d<K>(B, m_max, A, b, mrows, lb, ub, status, st, ho);
-
-// d = 5..16, m_max <= 64; returns 1 when it does not apply
-int launch_bbox_lazy(long long B, int m_max, int d, const double* A, const double* b, const int* mrows, double* lb,
-                     double* ub, int* status, hipStream_t st, BoxHandover* ho) {
-    if (ho) ho->mode = 0;
-    if (m_max < 1 || m_max > 64 || B < 1) return 1;
-    switch (d) {
-        PLP_CASE_BL(5) PLP_CASE_BL(6) PLP_CASE_BL(7) PLP_CASE_BL(8)
-        PLP_CASE_BL(9) PLP_CASE_BL(10) PLP_CASE_BL(11) PLP_CASE_BL(12)
-        PLP_CASE_BL(13) PLP_CASE_BL(14) PLP_CASE_BL(15) PLP_CASE_BL(16)
-        default: return 1;
-    }
+// L.nw = 4: bbox_wsplit_kernel, a workgroup of four wavefronts per polytope; else bbox_lazy_kernel, one wavefront;
+// L.dense: the 2d LPs with a stored dictionary.  Both leave the bases and the centres for the verifier.
+int launch_bbox_lazy(int d, const LpLaunch& L, const BoxArgs& a, hipStream_t st) {
+    return for_dim<5, MAX_D>(d, [&](auto K) {
+        constexpr int D = decltype(K)::value;
+#define PLP_BBW(KERNEL)                                                                                                       \
+    hipLaunchKernelGGL(KERNEL, dim3((unsigned)L.grid), dim3(L.block), L.lds, st, a.B, a.m_max, a.A, a.b, a.mrows, a.lb, a.ub, \
+                       a.status, a.ho.basis8, a.ho.centre)
+        if (L.nw == 4) { if (L.dense) PLP_BBW((bbox_wsplit_kernel<D, 4, true>)); else PLP_BBW((bbox_wsplit_kernel<D, 4, false>)); }
+        else if (L.dense) PLP_BBW((bbox_lazy_kernel<D, true>));
+        else PLP_BBW((bbox_lazy_kernel<D, false>));
+#undef PLP_BBW
+    });
 }
 
 }  // namespace plp

@@ -3,6 +3,7 @@
 // context, call the *_dev entry point on the context's stream and synchronise.
 #include "plp_hostcall.hpp"
 #include "plp_locate.hpp"
+#include "plp_lp_plan.hpp"
 
 namespace {
 
@@ -291,25 +292,26 @@ int plp_bbox_batch_dev(plp_ctx* ctx, void* stream, int64_t B, int m_max, int d, 
     hipStream_t st = (hipStream_t)stream;  // NULL = the HIP default stream
     // the verifier behind the fused kernels (plp_verify.hip): they hand over each box LP's final basis + the centre, or the
     // point the LP ended on; one buffer per stream: [bases 2 d d bytes | centres d doubles | points 2 d d doubles] per polytope
-    plp::BoxHandover ho{nullptr, nullptr, nullptr, 0};
+    plp::BoxHandover ho{nullptr, nullptr, nullptr};
     void* vsc = nullptr;
+    int mode = 0;   // which of it the planned launch fills: 1 bases + centres, 2 points (the one-LP-per-lane form)
     if (plp::verify_enabled()) {
+        mode = plp::plan_bbox(B, m_max, d, plp::lp_env()).handover;
         const size_t nb8 = ((size_t)B * 2 * d * d + 255) & ~(size_t)255, nct = (size_t)B * d * 8;
-        const bool lane_form = d <= 3 && m_max <= 32;   // (launch_bbox: the shapes bbox_lane_kernel may take)
-        const size_t nxf = lane_form ? (size_t)B * 2 * d * d * 8 : 0;
+        const size_t nxf = mode == 2 ? (size_t)B * 2 * d * d * 8 : 0;
         char* hb = static_cast<char*>(stream_buf(ctx->vf_basis, stream, nb8 + nct + nxf + 256));
         vsc = stream_buf(ctx->vf_scratch, stream, plp::verify_scratch_bytes(B * 2 * d, m_max));
         if (!hb || !vsc) return fail(PLP_EHIP, "verifier: no device memory for its scratch");
         ho.basis8 = reinterpret_cast<signed char*>(hb);
         ho.centre = reinterpret_cast<double*>(hb + nb8);
-        ho.xfin = lane_form ? reinterpret_cast<double*>(hb + nb8 + nct) : nullptr;
+        ho.xfin = mode == 2 ? reinterpret_cast<double*>(hb + nb8 + nct) : nullptr;
     }
     if (plp::launch_bbox(B, m_max, d, A, b, m, lb, ub, status, st, &ho))
         return fail(PLP_EUNSUPPORTED, "bbox kernel: unsupported size");
     rc = check_launch("bbox_r_kernel");
-    if (rc || !ho.mode) return rc;
-    if (plp::launch_verify_box(B, m_max, d, A, b, m, lb, ub, status, ho.mode == 1 ? ho.basis8 : nullptr,
-                               ho.mode == 1 ? ho.centre : nullptr, ho.mode == 2 ? ho.xfin : nullptr, vsc,
+    if (rc || !mode) return rc;
+    if (plp::launch_verify_box(B, m_max, d, A, b, m, lb, ub, status, mode == 1 ? ho.basis8 : nullptr,
+                               mode == 1 ? ho.centre : nullptr, mode == 2 ? ho.xfin : nullptr, vsc,
                                (int)(ctx->vf_scratch[stream].calls++ & 1u), st))
         return fail(PLP_EUNSUPPORTED, "verifier: unsupported size");
     return check_launch("verify_box_kernel");

@@ -2,7 +2,7 @@
 // parallel): stand-alone LP batches with four rows per lane (gfx950): Chebyshev-ball LPs (form F1,
 // polytope/polytope.py:1283-1288) and generic LPs whose origin is feasible:
 //
-//   lp_r_kernel<N,GS>       : lpsolve() batches (solvers.py:76-106), n <= 8, origin feasible (no phase 1)
+//   lp_r_kernel<N,GS>       : lpsolve() batches (solvers.py:76-106), n <= 17, origin feasible (no phase 1)
 //   lp_p1_r_kernel<N,GS>    : the LPs of such a batch that need phase 1 (some h_i < 0)
 //   cheby_r_kernel<D,GS>    : a batch of polytopes (cheby_ball / is_fulldim, :1241-1300, :962-985)
 //   adjacent_r_kernel<D,GS> : all pairs of n cells (is_adjacent(overlap=True), :1843-1866, under the pair
@@ -14,29 +14,16 @@
 // when it ends with ST_RETRY (a dictionary that needs Bland's rule) the wavefront rebuilds the LP and
 // solves it with the general engine, behind a wave-uniform branch that is almost never taken.
 #pragma once
-#include <stdlib.h>
-
-#include "plp_kernels.hpp"
+#include "plp_lp_launch.hpp"
 #include "plp_simplex_r.hpp"
 
 namespace plp {
-// One wavefront per workgroup for the batch kernels of this file (they use no LDS and no barrier): the tail of a
-// launch is balanced wave by wave.  Against 256 threads (rocprofv3 kernel durations): lp_r_kernel<6,8> 271 -> 172 us,
-// <16,32> 103 -> 81, <8,16> 186 -> 142, cheby_r_kernel<16,32> 692 -> 590, adjacent_r_kernel<4,4> 188 -> 181,
-// lp_p1_r_kernel<3,4> 250 -> 199; cheby_r_kernel<3,4> and lp_r_kernel<3,4> at 100 k LPs unchanged.
-#ifndef PLP_R_BLOCK
-#define PLP_R_BLOCK 64
-#endif
-constexpr int RBLK = PLP_R_BLOCK;  // threads per workgroup
-
+// (RBLK threads per workgroup, one wavefront: plp_lp_plan.hpp)
 namespace {
 
-#ifndef PLP_ROWS_BIG_D
-#define PLP_ROWS_BIG_D 2
-#endif
-// rows per lane: 4 for d <= 8; 2 for d = 9..16, where four rows of up to 17 columns would not fit the VGPR file
+// rows per lane: 4 for d <= 8; 2 for d = 9..16 (plp_lp_plan.hpp)
 template <int D>
-struct RowsPerLane { static constexpr int value = D <= 8 ? 4 : PLP_ROWS_BIG_D; };
+struct RowsPerLane { static constexpr int value = lp_rows_per_lane(D); };
 
 // Solve the Chebyshev LP of the rows handed out by `rowA(rr, kk)` / `rowb(rr)` (rr = row index < m).
 // Returns the LP status; x[0..D-1] = centre, x[D] = radius, replicated over the group (valid if status 0).
@@ -371,42 +358,9 @@ __global__ __launch_bounds__(RBLK, (D <= 4 ? 3 : 1)) void adjacent_r_kernel(
     if (t < n) adj[t * n + t] = 1;
 }
 
-// lanes per LP for `rows` rows at R rows per lane: the smallest of 4 / 8 / 16 / 32 that holds them
-#define PLP_DISPATCH_GS(R, rows, CALL)                      \
-    do {                                                    \
-        if ((rows) <= 4 * (R)) { constexpr int GSV = 4; return CALL; }   \
-        if ((rows) <= 8 * (R)) { constexpr int GSV = 8; return CALL; }   \
-        if ((rows) <= 16 * (R)) { constexpr int GSV = 16; return CALL; } \
-        if constexpr ((R) < 4) {                            \
-            if ((rows) <= 32 * (R)) { constexpr int GSV = 32; return CALL; } \
-        }                                                   \
-        if constexpr ((R) < 2) {                            \
-            constexpr int GSV = 64;                         \
-            return CALL;                                    \
-        }                                                   \
-        return 1;                                           \
-    } while (0)
-
-static int force_retry_env() {
-    const char* fr = getenv("PLP_CHEBY_RETRY_ALL");
-    return (fr && fr[0] == '1') ? 1 : 0;
-}
-
-// Where the two-phase run on the fast path pays: measured on MI355X against the one-row-per-lane two-phase
-// kernel (100k LPs, m=16): n=3 1.35x, n=4 1.22x, n=5 1.0x, n=6 0.88x, n=8 0.7x (the extra column, the carried
-// cost row and the sign bookkeeping push four rows per lane past 250 VGPRs: one wave per SIMD), n=2 0.84x.
-// Two rows per lane for n = 5..8 (groups twice as wide, two waves per SIMD) was measured too: 0.84x / 0.82x / 0.66x
-// of the one-row kernel at (16,5) / (16,6) / (32,8) -- bitwise the same results, so the cut-off stays at n = 4.
-#ifndef PLP_P1_FAST_MAXN
-#define PLP_P1_FAST_MAXN 4
-#endif
+// the LPs that need phase 1 stay on the fast path for n = 3..PLP_P1_FAST_MAXN (plp_lp_plan.hpp)
 template <int N>
 struct P1_FAST { static constexpr bool value = (N >= 3 && N <= PLP_P1_FAST_MAXN); };
-// rows per lane of the phase-1 kernel: 4 for n <= 4; 2 beyond (groups twice as wide), which keeps the extra column
-// and the carried cost row within two waves per SIMD
-template <int N>
-struct P1Rows { static constexpr int value = N <= 4 ? 4 : 2; };
-
 // Generic LP  min c'x  s.t.  G x <= h, x free  (solvers.py:76-106) when the origin is feasible (every
 // h_i >= 0): phase 2 starts from the all-slack dictionary, which is what the two-phase kernel of
 // plp_lp.hip does too in that case, so both walk the same path.  LPs that need phase 1 (or, later,

@@ -7,15 +7,10 @@ struct plp_locate_grid;  // include/plp.h
 
 namespace plp {
 
-// lanes per LP group for polytopes with up to m_max rows (-1: unsupported)
-static inline int group_size_for(int m_max) {
-    if (m_max < 0 || m_max > MAX_M) return -1;
-    if (m_max <= 8) return 8;
-    if (m_max <= 16) return 16;
-    if (m_max <= 32) return 32;
-    return 64;
-}
-
+// The stand-alone LP family (plp_lp.hip).  Which kernels a call runs is decided by plan_lp / plan_cheby / plan_bbox /
+// plan_pairs (plp_lp_plan.hpp); these carry the plan out (the launchers of the single engines: plp_lp_launch.hpp).
+// launch_lp_phase: phase 0 everything; phase 1 the fast kernels only, *more = 1 when LPs they hand over (status ST_RETRY)
+// may exist; phase 2 the general kernel's pass over exactly those.  launch_lp is phase 0.
 int launch_lp(long long B, int m_max, int n, const double* c, const double* G, const double* h, const int* mrows,
               double* x, double* fun, int* status, int* iters, hipStream_t st);
 int launch_lp_phase(long long B, int m_max, int n, const double* c, const double* G, const double* h, const int* mrows,
@@ -23,13 +18,6 @@ int launch_lp_phase(long long B, int m_max, int n, const double* c, const double
 
 int launch_cheby(long long B, int m_max, int d, const double* A, const double* b, const int* mrows, double* r,
                  double* xc, int* status, hipStream_t st);
-
-// dictionary in LDS, one LP per wavefront, any row count that fits 160 KB (plp_lds.hip): the engine for m_max > 64
-int launch_lp_lds(long long B, int m_max, int n, const double* c, const double* G, const double* h, const int* mrows,
-                  double* x, double* fun, int* status, int* iters, hipStream_t st);
-int launch_cheby_lds(long long B, int m_max, int d, const double* A, const double* b, const int* mrows, double* r,
-                     double* xc, int* status, hipStream_t st);
-size_t lds_lp_bytes(int m_max, int nc);  // 0: does not fit
 
 // Chebyshev LPs on row subsets rows[off[p] .. off[p+1]) of one resident table (region_diff's search): LPs sel[0..nlp)
 // of the batch; out[p] = radius as cheby_ball reads it (0 unless optimal with r >= 0).  plp_rdiff.hip / plp_lds.hip
@@ -82,42 +70,21 @@ int launch_volume_exact(long long B, int m_max, int d, const double* A, const do
 int launch_reduce_lds(long long B, int m_max, int d, const double* A, const double* b, const int* mrows, double abs_tol,
                       unsigned long long* keep, int* flags, double* r, double* xc, int* nlp, hipStream_t st);
 
-// one LP per wavefront, one row per lane, wave-uniform pivot column (plp_wide.hip): the engine for d >= 9
-int launch_cheby_w(long long B, int m_max, int d, const double* A, const double* b, const int* mrows, double* r,
-                   double* xc, int* status, hipStream_t st);
-
-// generic LPs, one per wavefront, both phases (n = 5..16, m_max <= 64, plp_lp_wide.hip); returns 1 when it does not apply
-int launch_lp_w(long long B, int m_max, int n, const double* c, const double* G, const double* h, const int* mrows,
-                double* x, double* fun, int* status, int* iters, hipStream_t st);
-
-// generic LPs, four rows per lane, origin-feasible ones only (n <= 8, plp_cheby_r.hip): the others get
-// status ST_RETRY for the general kernel; returns 1 when it does not apply
-int launch_lp_r(long long B, int m_max, int n, const double* c, const double* G, const double* h, const int* mrows,
-                double* x, double* fun, int* status, int* iters, hipStream_t st);
-
-// four rows per lane (d <= 8, plp_cheby_r.hip); returns 1 when it does not apply
-int launch_cheby_r(long long B, int m_max, int d, const double* A, const double* b, const int* mrows, double* r,
-                   double* xc, int* status, hipStream_t st);
-
-// bounding boxes, Chebyshev LP + 2d LPs from its centre per polytope (d <= 8, plp_bbox_r.hip): status 0 = lb/ub
-// valid, 1 = polytope left to the generic LPs; returns 1 when the kernel does not apply
+// bounding boxes, Chebyshev LP + 2d LPs from its centre per polytope (m_max = 1..64): status 0 = lb/ub valid, 1 = polytope
+// left to the generic LPs.
 // What the fused bounding-box kernels hand to the verifier (plp_verify.hip), per box LP (2d per polytope, lower_0, upper_0,
 // lower_1, ...): `basis8` -- its final basis, d signed bytes (>= 0: an active row; -1 - j: the free variable x'_j left at the
 // centre) -- with `centre` (d doubles per polytope), or `xfin` -- the point it ended on (d doubles; the one-LP-per-lane
-// kernel, whose walk has no basis of d entries when it ends on a face).  `mode` (out): 0 nothing written, 1 bases, 2 points.
+// kernel, whose walk has no basis of d entries when it ends on a face).  Which of the two a call fills: BoxPlan::handover.
 struct BoxHandover {
     signed char* basis8;
     double* centre;
     double* xfin;
-    int mode;
 };
 int launch_bbox(long long B, int m_max, int d, const double* A, const double* b, const int* mrows, double* lb,
-                double* ub, int* status, hipStream_t st, BoxHandover* ho = nullptr);
-// d = 9..16 (plp_bbox_lazy.hip); same contract
-int launch_bbox_lazy(long long B, int m_max, int d, const double* A, const double* b, const int* mrows, double* lb,
-                     double* ub, int* status, hipStream_t st, BoxHandover* ho = nullptr);
+                double* ub, int* status, hipStream_t st, const BoxHandover* ho = nullptr);
 
-// adjacency of all pairs of n cells (2*m_max <= 64, d <= 8) into the n x n matrix adj (compact == nullptr),
+// adjacency of all pairs of n cells (2*m_max <= 64) into the n x n matrix adj (compact == nullptr),
 // or of the pairs p_lo <= p < p_hi, p = i (i - 1) / 2 + j, j < i, into compact[p - p_lo]
 // a pair counts iff the Chebyshev radius of the two stacked cells, each b inflated by `inflate`, exceeds `thresh`
 // cross_n1 > 0 (compact only): the table holds two lists, n1 cells then n - n1 cells, and pair p = a (n - n1) + c is cell a
@@ -125,11 +92,6 @@ int launch_bbox_lazy(long long B, int m_max, int d, const double* A, const doubl
 int launch_adjacent(int n, int m_max, int d, const double* A, const double* b, const int* mrows, double inflate,
                     double thresh, unsigned char* adj, long long p_lo, long long p_hi, unsigned char* compact,
                     hipStream_t st, int cross_n1 = 0);
-
-// the same, one pair per wavefront (d = 5..16, plp_wide.hip); returns 1 when it does not apply
-int launch_adjacent_w(int n, int m_max, int d, const double* A, const double* b, const int* mrows, double inflate,
-                      double thresh, unsigned char* adj, long long p_lo, long long p_hi, unsigned char* compact,
-                      hipStream_t st, int cross_n1 = 0);
 
 // Fused reduce() of up to 64 rows (plp_reduce.hip).  The batch, the outputs, and what the fast kernels report besides:
 struct ReduceArgs {

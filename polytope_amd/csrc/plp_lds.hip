@@ -14,15 +14,13 @@
 // both engines walks the same vertex path and ends with bitwise the same numbers (tests: PLP_LDS=1).
 #include <stdlib.h>
 
-#include "plp_kernels.hpp"
+#include "plp_lp_launch.hpp"
 #include "plp_wave.hpp"
 #include "plp_simplex.hpp"  // mode names
 
 namespace plp {
 
 namespace {
-
-constexpr int LDS_MAXC = 32;  // column slots (n <= 17 structural + artificial)
 
 struct LdsDict {
     double* T;      // [m][ld]
@@ -833,46 +831,22 @@ __global__ __launch_bounds__(64) void reduce_lds_kernel(long long B, int m_max, 
     }
 }
 
-// LDS bytes one LP of (m_max, columns nc) needs; 0 when it does not fit a workgroup (160 KB per CU on gfx950)
-size_t lds_lp_bytes(int m_max, int nc) {
-    const int ld = nc | 1;
-    const size_t need = (size_t)m_max * ld * 8 + (size_t)m_max * 24 + 3 * LDS_MAXC * 8 + LDS_MAXC * 4 + 64;
-    return need <= 160 * 1024 ? ((need + 15) & ~(size_t)15) : 0;
-}
-
-static int lds_grid(long long B, size_t smem) {
-    // resident wavefronts: limited by LDS per CU and 8 single-wave workgroups per SIMD-set; the loop strides the rest
-    long long per_cu = (long long)(160 * 1024 / smem);
-    if (per_cu > 32) per_cu = 32;
-    if (per_cu < 1) per_cu = 1;
-    long long blocks = 256 * per_cu * 4;
-    if (blocks > B) blocks = B;
-    return (int)(blocks < 1 ? 1 : blocks);
-}
-
-int launch_lp_lds(long long B, int m_max, int n, const double* c, const double* G, const double* h, const int* mrows,
-                  double* x, double* fun, int* status, int* iters, hipStream_t st) {
-    if (n < 1 || n > MAX_D + 1 || m_max < 0) return 2;
-    const size_t smem = lds_lp_bytes(m_max < 1 ? 1 : m_max, n + 1);
-    if (!smem) return 2;
-    if (smem > 48 * 1024)
+// the dictionary of one LP in L.lds bytes of LDS (lds_lp_bytes, plp_lp_plan.hpp), workgroups that take LPs in turn (lds_grid)
+int launch_lp_lds(int n, const LpLaunch& L, const LpArgs& a, hipStream_t st) {
+    if (L.lds > 48 * 1024)
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lp_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)smem);
-    hipLaunchKernelGGL(lp_lds_kernel, dim3(lds_grid(B, smem)), dim3(64), smem, st, B, m_max, n, c, G, h, mrows, x, fun,
-                       status, iters);
+                                  (int)L.lds);
+    hipLaunchKernelGGL(lp_lds_kernel, dim3((unsigned)L.grid), dim3(L.block), L.lds, st, a.B, a.m_max, n, a.c, a.G, a.h, a.mrows,
+                       a.x, a.fun, a.status, a.iters);
     return 0;
 }
 
-int launch_cheby_lds(long long B, int m_max, int d, const double* A, const double* b, const int* mrows, double* r,
-                     double* xc, int* status, hipStream_t st) {
-    if (d < 1 || d > MAX_D || m_max < 0) return 2;
-    const size_t smem = lds_lp_bytes(m_max < 1 ? 1 : m_max, d + 1);
-    if (!smem) return 2;
-    if (smem > 48 * 1024)
+int launch_cheby_lds(int d, const LpLaunch& L, const ChebyArgs& a, hipStream_t st) {
+    if (L.lds > 48 * 1024)
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(cheby_lds_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    hipLaunchKernelGGL(cheby_lds_kernel, dim3(lds_grid(B, smem)), dim3(64), smem, st, B, m_max, d, A, b, mrows, r, xc,
-                       status);
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds);
+    hipLaunchKernelGGL(cheby_lds_kernel, dim3((unsigned)L.grid), dim3(L.block), L.lds, st, a.B, a.m_max, d, a.A, a.b, a.mrows,
+                       a.r, a.xc, a.status);
     return 0;
 }
 

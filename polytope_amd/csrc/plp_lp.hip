@@ -1,53 +1,17 @@
-// plp_lp.hip -- batched stand-alone LP kernels (gfx950).
+// plp_lp.hip -- the stand-alone LP family: the one-row-per-lane kernels and the launchers of the five calls (gfx950).
 //
 //   lp_kernel<N>    : B independent LPs  min c'x s.t. Gx<=h, x free   (solvers.py:76-106,149-158)
 //   cheby_kernel<D> : B Chebyshev-ball LPs (form F1, polytope.py:1283-1288):
 //                     c = -e_{d+1}, G = [A | sqrt(sum(A*A,1))], h = b
 //
-// One LP per lane group (GS lanes, GS >= rows), 64/GS LPs per wavefront, 256-thread
-// workgroups, grid-stride over the batch.  Chebyshev batches with d <= 8 go to the four-rows-per-lane
-// kernels of plp_cheby_r.hip; cheby_kernel here serves d > 8 (and PLP_CHEBY_1ROW=1).
-#include <stdlib.h>
-
-#include "plp_kernels.hpp"
+// One LP per lane group (GS lanes, GS >= rows), 64/GS LPs per wavefront, 256-thread workgroups, grid-stride over the
+// batch.  These are the kernels of the batches no faster engine takes and of the retry pass behind lp_r_kernel; which
+// engine a batch gets is plp_lp_plan.hpp's, and launch_lp_phase / launch_cheby / launch_bbox / launch_adjacent below
+// carry its plan out.
+#include "plp_lp_launch.hpp"
 #include "plp_simplex.hpp"
 
 namespace plp {
-
-// Chebyshev batches on the one-LP-per-wavefront engine (plp_wide.hip): d >= PLP_WIDE_MIN_D and either more than
-// PLP_WIDE_MIN_M rows (the lane groups then hold one or two LPs per wavefront anyway and pay select chains for the
-// entering column) or at most PLP_WIDE_SMALL_B LPs (every LP gets a wavefront slot at once: what counts is the latency
-// of one LP, and a wave-uniform pivot is the shortest).  Measured with scripts/debug/wide_grid.py (round 3, after the
-// pivot loop lost its register copies): (33..64 rows, d = 5..10) 15-40 % faster than the lane groups at B = 20 000,
-// every shape with d >= 5 at B = 2 000; (<= 32 rows, B = 20 000) the lane groups stay 10-45 % ahead.
-#ifndef PLP_WIDE_MIN_D
-#define PLP_WIDE_MIN_D 5
-#endif
-#ifndef PLP_WIDE_MIN_M
-#define PLP_WIDE_MIN_M 32
-#endif
-#ifndef PLP_WIDE_SMALL_B
-#define PLP_WIDE_SMALL_B 4096
-#endif
-
-// Generic LP batches on the one-LP-per-wavefront engine (plp_lp_wide.hip): every batch with n = 5..16.  Measured against
-// the lane-group kernels (scripts/debug/lp_wide_ab.py, 20 000 LPs, ms; x / status / iterations bitwise equal on every
-// input): LPs that need phase 1 (64,16) 1.74 -> 0.34, (64,8) 0.59 -> 0.17, (32,12) 0.48 -> 0.17, (32,6) 0.21 -> 0.09,
-// (16,5) 0.092 -> 0.063; origin-feasible ones (64,16) 0.43 -> 0.25, (32,6) a tie, (16,5) / (24,5) / (32,8) 10-30 % behind
-// (four rows per lane pack several of those per wavefront) -- the mix of a batch is not known to the host, and the
-// reference's LPs are posed in original coordinates, where the origin is rarely feasible.
-// (A two-pass route for large batches of LPs with 32 rows and fewer -- lp_r_kernel for the origin-feasible ones, then this
-// engine on what it hands over -- was measured: the feasible batches win their 15-27 % back, the two-phase ones lose
-// 20-30 % to the extra pass ((32,6): 0.097 -> 0.116 ms); not kept.)
-// PLP_LP_WIDE=0 / 1: never / always (A/B, tests)
-static bool lp_wide_on(long long B, int m_max, int n) {
-    if (n < 5 || n > MAX_D || m_max < 1 || m_max > MAX_M || B > 2147483647ll) return false;  // (what launch_lp_w takes)
-    const char* w = getenv("PLP_LP_WIDE");
-    if (w) return w[0] == '1';
-    const char* one = getenv("PLP_LP_1ROW");
-    if (one && one[0] == '1') return false;
-    return true;
-}
 
 template <int N>
 __global__ __launch_bounds__(BLOCK) void lp_kernel(long long B, int m_max, int gs,
@@ -220,111 +184,89 @@ __global__ __launch_bounds__(BLOCK) void cheby_kernel(long long B, int m_max, in
     }
 }
 
-static inline int pick_grid(long long B, int gs) {
-    const long long gpb = BLOCK / gs;
-    long long blocks = (B + gpb - 1) / gpb;
-    const long long cap = 1ll << 20;  // one LP tile per block: the dispatcher balances uneven pivot counts
-    if (blocks > cap) blocks = cap;
-    if (blocks < 1) blocks = 1;
-    return (int)blocks;
+// one launch of lp_kernel<n> as planned; retry_only: the second pass over the LPs left ST_RETRY
+static int launch_lp_general(int n, const LpLaunch& L, const LpArgs& a, int retry_only, hipStream_t st) {
+    return for_dim<1, MAX_D + 1>(n, [&](auto K) {
+        hipLaunchKernelGGL(lp_kernel<decltype(K)::value>, dim3((unsigned)L.grid), dim3(L.block), L.lds, st, a.B, a.m_max, L.gs,
+                           a.c, a.G, a.h, a.mrows, a.x, a.fun, a.status, a.iters, retry_only);
+    });
 }
 
-template <int N>
-static void launch_lp_n(long long B, int m_max, int gs, const double* c, const double* G, const double* h,
-                        const int* mrows, double* x, double* fun, int* status, int* iters, int retry, hipStream_t st) {
-    int blocks = pick_grid(B, gs);
-    if (retry && blocks > 256 * 8) blocks = 256 * 8;  // second pass: mostly status reads, a grid-stride sweep
-    hipLaunchKernelGGL(lp_kernel<N>, dim3(blocks), dim3(BLOCK), 0, st, B, m_max, gs, c, G, h, mrows, x,
-                       fun, status, iters, retry);
-}
-
-template <int D>
-static void launch_cheby_d(long long B, int m_max, int gs, const double* A, const double* b, const int* mrows,
-                           double* r, double* xc, int* status, hipStream_t st) {
-    hipLaunchKernelGGL(cheby_kernel<D>, dim3(pick_grid(B, gs)), dim3(BLOCK), 0, st, B, m_max, gs, A, b, mrows, r,
-                       xc, status);
-}
-
-#define PLP_CASE_N(K) case K: launch_lp_n<K>(B, m_max, gs, c, G, h, mrows, x, fun, status, iters, retry, st); break;
-#define PLP_CASE_D(K) case K: launch_cheby_d<K>(B, m_max, gs, A, b, mrows, r, xc, status, st); break;
-
-// phase 1: the fast kernels only -- returns 0 with *more = 1 when LPs they hand over (status ST_RETRY) may exist and the
-// caller has to look; phase 2: the general kernel over exactly those.  (launch_lp below = both, back to back.)  The
-// synchronous host entry point uses the phases for small batches: the normally idle general pass is a launch saved.
+// phase 0: everything, back to back.  phase 1: the fast kernels only -- *more = 1 when LPs they hand over (status ST_RETRY)
+// may exist and the caller has to look; phase 2: the general kernel over exactly those.  The synchronous host entry point
+// uses the phases for small batches: the normally idle general pass is a launch saved.
 int launch_lp_phase(long long B, int m_max, int n, const double* c, const double* G, const double* h, const int* mrows,
                     double* x, double* fun, int* status, int* iters, hipStream_t st, int phase, int* more) {
     if (more) *more = 0;
-    const char* lds = getenv("PLP_LDS");
-    if (m_max > MAX_M || (lds && lds[0] == '1')) {
-        if (phase == 2) return 0;
-        return launch_lp_lds(B, m_max, n, c, G, h, mrows, x, fun, status, iters, st);
-    }
-    const int gs = group_size_for(m_max);
-    if (gs < 0 || n < 1 || n > MAX_D + 1) return 2;
-    if (lp_wide_on(B, m_max, n)) {  // both phases in one kernel: nothing is handed over
-        if (phase == 2) return 0;
-        if (launch_lp_w(B, m_max, n, c, G, h, mrows, x, fun, status, iters, st) == 0) return 0;
-    }
-    const char* one = getenv("PLP_LP_1ROW");
-    int retry = 0;
-    if (phase == 2) retry = 1;
-    else if (!(one && one[0] == '1') && launch_lp_r(B, m_max, n, c, G, h, mrows, x, fun, status, iters, st) == 0) {
-        if (more) *more = 1;
-        return 0;
-    }
-    switch (n) {
-        PLP_CASE_N(1) PLP_CASE_N(2) PLP_CASE_N(3) PLP_CASE_N(4) PLP_CASE_N(5) PLP_CASE_N(6)
-        PLP_CASE_N(7) PLP_CASE_N(8) PLP_CASE_N(9) PLP_CASE_N(10) PLP_CASE_N(11) PLP_CASE_N(12)
-        PLP_CASE_N(13) PLP_CASE_N(14) PLP_CASE_N(15) PLP_CASE_N(16) PLP_CASE_N(17)
+    const LpPlan p = plan_lp(B, m_max, n, lp_env());
+    const LpArgs a{B, m_max, c, G, h, mrows, x, fun, status, iters};
+    if (phase == 2)   // (the LDS and the one-LP-per-wavefront engines hand nothing over)
+        return (p.first.engine == LE_LDS || p.first.engine == LE_WIDE) ? 0 : p.first.engine == LE_NONE ? 2
+                                                                            : launch_lp_general(n, p.retry, a, 1, st);
+    switch (p.first.engine) {
+        case LE_LDS: return launch_lp_lds(n, p.first, a, st);
+        case LE_WIDE: return launch_lp_w(n, p.first, a, st);
+        case LE_GENERAL: return launch_lp_general(n, p.first, a, 0, st);
+        case LE_GROUP:
+            if (launch_lp_r(n, p.first, p.p1 ? &p.p1_launch : nullptr, a, st)) return 2;
+            if (phase == 1) {
+                if (more) *more = 1;
+                return 0;
+            }
+            return launch_lp_general(n, p.retry, a, 1, st);
         default: return 2;
     }
-    return 0;
 }
 
 int launch_lp(long long B, int m_max, int n, const double* c, const double* G, const double* h, const int* mrows,
               double* x, double* fun, int* status, int* iters, hipStream_t st) {
-    // more than 64 rows (or PLP_LDS=1: A/B, tests): the LDS-resident engine, one LP per wavefront (plp_lds.hip)
-    const char* lds = getenv("PLP_LDS");
-    if (m_max > MAX_M || (lds && lds[0] == '1')) return launch_lp_lds(B, m_max, n, c, G, h, mrows, x, fun, status, iters, st);
-    const int gs = group_size_for(m_max);
-    if (gs < 0 || n < 1 || n > MAX_D + 1) return 2;
-    if (lp_wide_on(B, m_max, n) && launch_lp_w(B, m_max, n, c, G, h, mrows, x, fun, status, iters, st) == 0) return 0;
-    // n <= 8: LPs whose origin is feasible (no phase 1) are solved by the four-rows-per-lane fast path
-    // (plp_cheby_r.hip); it marks the others ST_RETRY and the launch below redoes exactly those
-    // (PLP_LP_1ROW=1 keeps everything on this file's kernel: A/B, tests).
-    const char* one = getenv("PLP_LP_1ROW");
-    int retry = 0;
-    if (!(one && one[0] == '1') && launch_lp_r(B, m_max, n, c, G, h, mrows, x, fun, status, iters, st) == 0) retry = 1;
-    switch (n) {
-        PLP_CASE_N(1) PLP_CASE_N(2) PLP_CASE_N(3) PLP_CASE_N(4) PLP_CASE_N(5) PLP_CASE_N(6)
-        PLP_CASE_N(7) PLP_CASE_N(8) PLP_CASE_N(9) PLP_CASE_N(10) PLP_CASE_N(11) PLP_CASE_N(12)
-        PLP_CASE_N(13) PLP_CASE_N(14) PLP_CASE_N(15) PLP_CASE_N(16) PLP_CASE_N(17)
-        default: return 2;
-    }
-    return 0;
+    return launch_lp_phase(B, m_max, n, c, G, h, mrows, x, fun, status, iters, st, 0, nullptr);
 }
 
 int launch_cheby(long long B, int m_max, int d, const double* A, const double* b, const int* mrows, double* r,
                  double* xc, int* status, hipStream_t st) {
-    const char* lds = getenv("PLP_LDS");
-    if (m_max > MAX_M || (lds && lds[0] == '1')) return launch_cheby_lds(B, m_max, d, A, b, mrows, r, xc, status, st);
-    const int gs = group_size_for(m_max);
-    if (gs < 0 || d < 1 || d > MAX_D) return 2;
-    // large shapes: one LP per wavefront with a wave-uniform pivot column (plp_wide.hip); PLP_CHEBY_WIDE=0 keeps the
-    // lane-group kernels, PLP_CHEBY_WIDE=1 sends every shape it supports (d >= 5) there: A/B, tests
-    const char* wide = getenv("PLP_CHEBY_WIDE");
-    const bool wide_on = wide ? wide[0] == '1' : (d >= PLP_WIDE_MIN_D && (m_max > PLP_WIDE_MIN_M || B <= PLP_WIDE_SMALL_B));
-    if (wide_on && !(wide && wide[0] == '0') && launch_cheby_w(B, m_max, d, A, b, mrows, r, xc, status, st) == 0) return 0;
-    // d <= 8: four rows per lane (PLP_CHEBY_1ROW=1 keeps the one-row-per-lane kernel: A/B, tests)
-    const char* one = getenv("PLP_CHEBY_1ROW");
-    if (!(one && one[0] == '1') && launch_cheby_r(B, m_max, d, A, b, mrows, r, xc, status, st) == 0) return 0;
-    switch (d) {
-        PLP_CASE_D(1) PLP_CASE_D(2) PLP_CASE_D(3) PLP_CASE_D(4) PLP_CASE_D(5) PLP_CASE_D(6)
-        PLP_CASE_D(7) PLP_CASE_D(8) PLP_CASE_D(9) PLP_CASE_D(10) PLP_CASE_D(11) PLP_CASE_D(12)
-        PLP_CASE_D(13) PLP_CASE_D(14) PLP_CASE_D(15) PLP_CASE_D(16)
+    const ChebyPlan p = plan_cheby(B, m_max, d, lp_env());
+    const LpLaunch& L = p.first;
+    const ChebyArgs a{B, m_max, A, b, mrows, r, xc, status};
+    switch (L.engine) {
+        case LE_LDS: return launch_cheby_lds(d, L, a, st);
+        case LE_WIDE: return launch_cheby_w(d, L, a, st);
+        case LE_GROUP: return launch_cheby_r(d, L, p.force_retry, a, st);
+        case LE_GENERAL:
+            return for_dim<1, MAX_D>(d, [&](auto K) {
+                hipLaunchKernelGGL(cheby_kernel<decltype(K)::value>, dim3((unsigned)L.grid), dim3(L.block), L.lds, st, B, m_max,
+                                   L.gs, A, b, mrows, r, xc, status);
+            });
         default: return 2;
     }
-    return 0;
+}
+
+// `ho`: where the launch leaves what the verifier takes (plan_bbox's hand-over mode says which of it), or nullptr
+int launch_bbox(long long B, int m_max, int d, const double* A, const double* b, const int* mrows, double* lb,
+                double* ub, int* status, hipStream_t st, const BoxHandover* ho) {
+    const BoxPlan p = plan_bbox(B, m_max, d, lp_env());
+    const BoxArgs a{B, m_max, A, b, mrows, lb, ub, status, ho ? *ho : BoxHandover{nullptr, nullptr, nullptr}};
+    switch (p.first.engine) {
+        case LE_LANE: return launch_bbox_lane(d, p.first, a, st);
+        case LE_WIDE: return launch_bbox_lazy(d, p.first, a, st);
+        case LE_SPLIT:
+        case LE_GROUP: return launch_bbox_r(d, p.first, p.force_retry, a, st);
+        default: return 2;
+    }
+}
+
+// compact == nullptr: all pairs into the n x n matrix adj; else pairs [p_lo, p_hi) into compact[p - p_lo]
+int launch_adjacent(int n, int m_max, int d, const double* A, const double* b, const int* mrows, double inflate,
+                    double thresh, unsigned char* adj, long long p_lo, long long p_hi, unsigned char* compact,
+                    hipStream_t st, int cross_n1) {
+    const PairPlan p = plan_pairs(n, m_max, d, p_lo, p_hi, compact != nullptr, cross_n1, lp_env());
+    const PairArgs a{n, m_max, A, b, mrows, inflate, thresh, adj, p.p_lo, p.p_hi, compact, cross_n1};
+    switch (p.first.engine) {
+        case LE_EMPTY: return 0;
+        case LE_WIDE: return launch_adjacent_w(d, p.first, a, st);
+        case LE_GROUP: return launch_adjacent_r(d, p.first, p.force_retry, a, st);
+        default: return 2;
+    }
 }
 
 }  // namespace plp

@@ -14,7 +14,7 @@
 // one-row-per-lane lane-group kernel (lp_kernel<N>, plp_lp.hip), which at 33..64 rows holds one LP per wavefront as well.
 #include <stdlib.h>
 
-#include "plp_kernels.hpp"
+#include "plp_lp_launch.hpp"
 #include "plp_wave.hpp"
 #include "plp_wide.hpp"
 
@@ -297,26 +297,12 @@ __global__ __launch_bounds__(64, 4) void lp_w_kernel(long long B, int m_max, con
     }
 }
 
-template <int N>
-static int launch_lp_w_n(long long B, int m_max, const double* c, const double* G, const double* h, const int* mrows,
-                         double* x, double* fun, int* status, int* iters, hipStream_t st) {
-    if (B > 2147483647ll) return 1;
-    hipLaunchKernelGGL((lp_w_kernel<N>), dim3((unsigned)(B < 1 ? 1 : B)), dim3(64), 0, st, B, m_max, c, G, h, mrows, x, fun,
-                       status, iters);
-    return 0;
-}
-
-#define PLP_CASE_LW(K) case K: return launch_lp_w_n<K>(B, m_max, c, G, h, mrows, x, fun, status, iters, st);
-
-// one LP per wavefront, n = 5..16, m_max <= 64; returns 1 when it does not apply
-int launch_lp_w(long long B, int m_max, int n, const double* c, const double* G, const double* h, const int* mrows,
-                double* x, double* fun, int* status, int* iters, hipStream_t st) {
-    if (m_max < 1 || m_max > 64) return 1;
-    switch (n) {
-        PLP_CASE_LW(5) PLP_CASE_LW(6) PLP_CASE_LW(7) PLP_CASE_LW(8) PLP_CASE_LW(9) PLP_CASE_LW(10)
-        PLP_CASE_LW(11) PLP_CASE_LW(12) PLP_CASE_LW(13) PLP_CASE_LW(14) PLP_CASE_LW(15) PLP_CASE_LW(16)
-        default: return 1;
-    }
+// one LP per wavefront, both phases, n = 5..16
+int launch_lp_w(int n, const LpLaunch& L, const LpArgs& a, hipStream_t st) {
+    return for_dim<5, MAX_D>(n, [&](auto K) {
+        hipLaunchKernelGGL((lp_w_kernel<decltype(K)::value>), dim3((unsigned)L.grid), dim3(L.block), L.lds, st, a.B, a.m_max, a.c,
+                           a.G, a.h, a.mrows, a.x, a.fun, a.status, a.iters);
+    });
 }
 
 }  // namespace plp

@@ -99,7 +99,7 @@ static int launch_gather_d(long long n0, long long n1, long long n2, const int* 
                         b2 = (n2 + RBLK / 64 - 1) / (RBLK / 64);
         if (b0 + b1 + b2 < 1) return 0;
         hipLaunchKernelGGL((cheby_gather_r1_kernel<D>), dim3((unsigned)(b0 + b1 + b2)), dim3(RBLK), 0, st, (int)b0, (int)b1, n0,
-                           n1, n2, off, rows, sel, A, b, out, force_retry_env());
+                           n1, n2, off, rows, sel, A, b, out, lp_force_retry(lp_env()));
         return 0;
     }
     const long long nb0 = (n0 + RBLK / 4 - 1) / (RBLK / 4), nb1 = (n1 + RBLK / 8 - 1) / (RBLK / 8),
@@ -108,7 +108,7 @@ static int launch_gather_d(long long n0, long long n1, long long n2, const int* 
     if (blocks < 1) return 0;
     if (blocks > 2147483647ll) return 2;
     hipLaunchKernelGGL((cheby_gather_r_kernel<D>), dim3((unsigned)blocks), dim3(RBLK), 0, st, (int)nb0, (int)nb1, n0, n1, n2,
-                       off, rows, sel, A, b, out, force_retry_env());
+                       off, rows, sel, A, b, out, lp_force_retry(lp_env()));
     return 0;
 }
 
@@ -313,7 +313,7 @@ int launch_rdiff_server(int d, int nwg, const unsigned long long* mail, const in
 #define PLP_SRV(K)                                                                                                      \
     case K:                                                                                                             \
         hipLaunchKernelGGL((rdiff_server_kernel<K>), dim3((unsigned)nwg), dim3(64), 0, st, mail, rec,                    \
-                           static_cast<ulonglong2*>(out), alive, dstate, A, b, last_word, idle_polls, force_retry_env(), wide_engine); \
+                           static_cast<ulonglong2*>(out), alive, dstate, A, b, last_word, idle_polls, lp_force_retry(lp_env()), wide_engine); \
         return 0;
     switch (d) {
         PLP_SRV(1) PLP_SRV(2) PLP_SRV(3) PLP_SRV(4)

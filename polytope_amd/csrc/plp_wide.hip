@@ -18,7 +18,7 @@
 // "r enters, row argmin b_i/||a_i|| leaves" for F1.
 #include <stdlib.h>
 
-#include "plp_kernels.hpp"
+#include "plp_lp_launch.hpp"
 #include "plp_wave.hpp"
 #include "plp_wide.hpp"
 
@@ -236,62 +236,20 @@ __global__ __launch_bounds__(64) void adjacent_w_kernel(int n, int m_max, const 
     }
 }
 
-template <int D>
-static int launch_adjacent_w_d(int n, int m_max, const double* A, const double* b, const int* mrows, double inflate,
-                               double thresh, unsigned char* adj, long long p_lo, long long p_hi, unsigned char* compact,
-                               int cross_n1, hipStream_t st) {
-    long long blocks = p_hi - p_lo;
-    const long long bdiag = compact ? 0 : ((long long)n + 63) / 64;
-    if (blocks < bdiag) blocks = bdiag;
-    if (blocks < 1) blocks = 1;
-    if (blocks > 2147483647ll) return 2;
-    hipLaunchKernelGGL((adjacent_w_kernel<D>), dim3((unsigned)blocks), dim3(64), 0, st, n, m_max, A, b, mrows, inflate, thresh,
-                       adj, p_lo, p_hi, compact, cross_n1);
-    return 0;
+// one pair per wavefront, d = 5..16: L.grid covers the pairs and, in the matrix form, the diagonal
+int launch_adjacent_w(int d, const LpLaunch& L, const PairArgs& a, hipStream_t st) {
+    return for_dim<5, MAX_D>(d, [&](auto K) {
+        hipLaunchKernelGGL((adjacent_w_kernel<decltype(K)::value>), dim3((unsigned)L.grid), dim3(L.block), L.lds, st, a.n, a.m_max,
+                           a.A, a.b, a.mrows, a.inflate, a.thresh, a.adj, a.p_lo, a.p_hi, a.compact, a.cross_n1);
+    });
 }
 
-#define PLP_CASE_AW(K) \
-    case K: return launch_adjacent_w_d<K>(n, m_max, A, b, mrows, inflate, thresh, adj, p_lo, p_hi, compact, cross_n1, st);
-
-// pairs [p_lo, p_hi) of n cells, 2 * m_max <= 64, d = 5..16; returns 1 when it does not apply
-int launch_adjacent_w(int n, int m_max, int d, const double* A, const double* b, const int* mrows, double inflate,
-                      double thresh, unsigned char* adj, long long p_lo, long long p_hi, unsigned char* compact,
-                      hipStream_t st, int cross_n1) {
-    switch (d) {
-        PLP_CASE_AW(5) PLP_CASE_AW(6) PLP_CASE_AW(7) PLP_CASE_AW(8) PLP_CASE_AW(9) PLP_CASE_AW(10)
-        PLP_CASE_AW(11) PLP_CASE_AW(12) PLP_CASE_AW(13) PLP_CASE_AW(14) PLP_CASE_AW(15) PLP_CASE_AW(16)
-        default: return 1;
-    }
-}
-
-template <int D>
-static int launch_cheby_w_d(long long B, int m_max, const double* A, const double* b, const int* mrows, double* r,
-                            double* xc, int* status, hipStream_t st) {
-    if (B > 2147483647ll) return 2;
-    hipLaunchKernelGGL((cheby_w_kernel<D>), dim3((unsigned)(B < 1 ? 1 : B)), dim3(64), 0, st, B, m_max, A, b, mrows, r, xc,
-                       status);
-    return 0;
-}
-
-// one LP per wavefront (m_max <= 64); returns 1 when it does not apply
-int launch_cheby_w(long long B, int m_max, int d, const double* A, const double* b, const int* mrows, double* r,
-                   double* xc, int* status, hipStream_t st) {
-    if (m_max < 1 || m_max > 64) return 1;
-    switch (d) {
-        case 5: return launch_cheby_w_d<5>(B, m_max, A, b, mrows, r, xc, status, st);
-        case 6: return launch_cheby_w_d<6>(B, m_max, A, b, mrows, r, xc, status, st);
-        case 7: return launch_cheby_w_d<7>(B, m_max, A, b, mrows, r, xc, status, st);
-        case 8: return launch_cheby_w_d<8>(B, m_max, A, b, mrows, r, xc, status, st);
-        case 9: return launch_cheby_w_d<9>(B, m_max, A, b, mrows, r, xc, status, st);
-        case 10: return launch_cheby_w_d<10>(B, m_max, A, b, mrows, r, xc, status, st);
-        case 11: return launch_cheby_w_d<11>(B, m_max, A, b, mrows, r, xc, status, st);
-        case 12: return launch_cheby_w_d<12>(B, m_max, A, b, mrows, r, xc, status, st);
-        case 13: return launch_cheby_w_d<13>(B, m_max, A, b, mrows, r, xc, status, st);
-        case 14: return launch_cheby_w_d<14>(B, m_max, A, b, mrows, r, xc, status, st);
-        case 15: return launch_cheby_w_d<15>(B, m_max, A, b, mrows, r, xc, status, st);
-        case 16: return launch_cheby_w_d<16>(B, m_max, A, b, mrows, r, xc, status, st);
-        default: return 1;
-    }
+// one LP per wavefront, d = 5..16
+int launch_cheby_w(int d, const LpLaunch& L, const ChebyArgs& a, hipStream_t st) {
+    return for_dim<5, MAX_D>(d, [&](auto K) {
+        hipLaunchKernelGGL((cheby_w_kernel<decltype(K)::value>), dim3((unsigned)L.grid), dim3(L.block), L.lds, st, a.B, a.m_max, a.A,
+                           a.b, a.mrows, a.r, a.xc, a.status);
+    });
 }
 
 }  // namespace plp

@@ -15,22 +15,24 @@ c. members do not see each other: the batch reversed and rolled by 3 gives the s
 d. an outside reference on the live rows only: the oracle for the LP family, contains and the pair kernels, the oracle's
    simplex for support, exact rational arithmetic for the vertices and facets of the lattice cases.
 
-Kernels covered (the plan of tests/cabi/reduce_plan_host.cpp is asked for the fused reduce; test_engine_coverage asserts it):
+Kernels covered (the plans of tests/cabi/reduce_plan_host.cpp and tests/cabi/lp_plan_host.cpp are asked which engines the
+cases below reach; test_engine_coverage and test_lp_engine_coverage assert it against REQUIRED / LP_REQUIRED):
   plp_reduce_batch       GENERAL (reduce_kernel), LANE at 16 / 8 / 4 lanes per polytope and 16 / 32 row slots
                          (reduce_lane_kernel), LANE_MIX (reduce_lane_mix_kernel, its default thresholds: 16 001 and 40 001
                          members), GROUP at 4 x 4 and 8 x 2 (reduce_r_kernel), GROUP_MIX half tiles and full + half tiles
                          (reduce_r_mix_kernel, 70 000 members), SPLIT (reduce_split_kernel), WDENSE, LAZY, WSPLIT at 2 and 4
                          wavefronts, with and without a stored dictionary
   plp_reduce_wide_batch  reduce_lds_kernel (70 rows), one member per workgroup and members in turn (33 025 members)
-  plp_lp_solve_batch     lp_r_kernel + lp_kernel (n <= 4), lp_kernel alone (PLP_LP_1ROW), lp_w_kernel (n = 5 .. 16), the
-                         lane groups at n = 8 (PLP_LP_WIDE=0) and n = 17, lp_lds_kernel beyond 64 rows and with members in
-                         turn (PLP_LDS, 33 025 members)
-  plp_cheby_batch        cheby_r_kernel, cheby_kernel (PLP_CHEBY_1ROW), cheby_w_kernel (d = 9), cheby_lds_kernel likewise
-  plp_bbox_batch         bbox_lane_kernel, bbox_split_kernel, bbox_r_kernel, bbox_wsplit / one polytope per wavefront dense
-                         and lazy (PLP_BBOX_WIDE, PLP_BBOX_WDENSE), d = 14
+  plp_lp_solve_batch     GROUP with the phase-1 kernel and the retry pass (lp_r_kernel + lp_p1_r_kernel + lp_kernel), without
+                         phase 1 at four and at two rows per lane, GENERAL alone (lp_kernel), WIDE (lp_w_kernel), LDS
+                         (lp_lds_kernel) beyond 64 rows and with members in turn (PLP_LDS, 33 025 members)
+  plp_cheby_batch        GROUP at four and two rows per lane (cheby_r_kernel), GENERAL (cheby_kernel), WIDE (cheby_w_kernel),
+                         LDS (cheby_lds_kernel) likewise
+  plp_bbox_batch         LANE (bbox_lane_kernel), SPLIT (bbox_split_kernel), GROUP (bbox_r_kernel), WIDE on four wavefronts
+                         and on one (bbox_wsplit_kernel, bbox_lazy_kernel), each with and without a stored dictionary
   plp_contains           both modes
   plp_adjacent_pairs, plp_adjacent_pairs_range, plp_overlap_pairs, plp_overlap_cross
-                         adjacent_r_kernel at d = 2, 4, 8 (PLP_ADJ_WIDE=0), adjacent_w_kernel at d = 5, 12; empty (by two
+                         GROUP (adjacent_r_kernel) at 4, 8 and 16 lanes per pair, WIDE (adjacent_w_kernel); empty (by two
                          rows, by a zero row), flat and unbounded cells among the bounded ones, up to 257 cells
   plp_fm_count / plp_fm_emit   with m alone and with keep / flags of a reduce, first on and off, col < 0; one member per
                          workgroup and members in turn (33 025 members)
@@ -56,6 +58,7 @@ import extreme_host as xh  # noqa: E402
 import hull_host as hh  # noqa: E402
 import support_host as sh  # noqa: E402
 from test_reduce_plan import ENGINES, FIELDS, plan as reduce_plan  # noqa: E402,F401 (a fixture: the compiled plan)
+from test_lp_plan import ENGINES as LP_ENGINES, plan as lp_plan  # noqa: E402,F401 (likewise, for the LP family)
 
 pytestmark = pytest.mark.gpu
 
@@ -344,7 +347,7 @@ STRIDE_ALONE = (0, 5, GRID_CAP + 5, STRIDE_B - 1)
 REQUIRED = {("GENERAL", 0), ("LANE", 4), ("LANE", 8), ("LANE", 16), ("LANE_MIX", 0), ("GROUP", 0), ("GROUP_MIX", 0),
             ("SPLIT", 0), ("WDENSE", 0), ("LAZY", 0), ("WSPLIT", 2), ("WSPLIT", 4)}
 
-LP = [   # (m_max, n, switches): the kernels the launchers of plp_lp.hip can pick
+LP = [   # (m_max, n, switches)
     (16, 3, {}), (16, 3, {"PLP_LP_1ROW": 1}), (24, 8, {}), (24, 8, {"PLP_LP_WIDE": 0}), (40, 17, {}), (70, 4, {}),
     (16, 3, {"PLP_LDS": 1}),
 ]
@@ -353,8 +356,18 @@ BBOX = [
     (16, 3, {}), (16, 3, {"PLP_BBOX_LANE": 0}), (16, 3, {"PLP_BBOX_LANE": 0, "PLP_BBOX_SPLIT": 0}), (24, 6, {}),
     (24, 6, {"PLP_BBOX_WIDE": 1, "PLP_BBOX_WDENSE": 1}), (24, 6, {"PLP_BBOX_WIDE": 1, "PLP_BBOX_WDENSE": 0}),
     (24, 6, {"PLP_BBOX_WIDE": 0, "PLP_BBOX_SPLIT": 0}), (40, 14, {}),
+    (24, 6, {"PLP_BBOX_WIDE": 1, "PLP_BBOX_WSPLIT": 0}), (40, 14, {"PLP_BBOX_WSPLIT": 0}),   # one wavefront per polytope
 ]
 PAIRS = [(6, 2, {}), (10, 4, {}), (20, 8, {"PLP_ADJ_WIDE": 0}), (14, 5, {}), (28, 12, {})]   # (m_max, d, switches)
+# What the plan of the LP family (plp_lp_plan.hpp) must say the lists above reach, at the sizes the tests run them:
+# lp (engine, rows per lane, the phase-1 kernel follows), cheby (engine, rows per lane), bbox (engine, wavefronts per
+# polytope, stored dictionary), pairs (engine, lanes per pair)
+LP_REQUIRED = {
+    "lp": {("LDS", 1, 0), ("WIDE", 1, 0), ("GROUP", 4, 1), ("GROUP", 4, 0), ("GROUP", 2, 0), ("GENERAL", 1, 0)},
+    "cheby": {("LDS", 1), ("WIDE", 1), ("GROUP", 4), ("GROUP", 2), ("GENERAL", 1)},
+    "bbox": {("LANE", 0, 0), ("SPLIT", 0, 0), ("GROUP", 0, 0), ("WIDE", 4, 1), ("WIDE", 4, 0), ("WIDE", 1, 1), ("WIDE", 1, 0)},
+    "pairs": {("GROUP", 4), ("GROUP", 8), ("GROUP", 16), ("WIDE", 64)},
+}
 ENUM_SHAPES = [(5, 2), (16, 3), (12, 4), (64, 2)]
 # (m_max, d, K): 16 / 32 / 64 row slots at K = 5 (8 lanes and 8 polytopes per workgroup), and the other steps of
 # support::polytopes_per_group: K = 1 (one lane each: 64 per workgroup, 16 at 64 row slots, where np_cap holds), K = 33
@@ -412,6 +425,36 @@ def test_engine_coverage(plan):
         seen.add((engine, 0))
     assert seen >= REQUIRED, REQUIRED - seen
     assert {ENGINES.index(e) for e, _ in REQUIRED} == set(range(1, len(ENGINES)))
+
+
+def test_lp_engine_coverage(lp_plan):
+    """The LP, CHEBY, BBOX and PAIRS cases below reach every engine of the LP family's plan, in each of its forms, at the
+    sizes the tests run them (the pair calls: the matrix, the range 3 .. npairs - 2 and the cross pairs of raw_pairs)."""
+    def ask(call, sizes, env):
+        launches, _ = lp_plan(call, sizes, {k[len("PLP_"):]: str(v) for k, v in env.items()})
+        assert launches, (call, sizes, env)
+        return launches
+    seen = {call: set() for call in LP_REQUIRED}
+    for B in SIZES:
+        for m_max, n, env in LP:
+            L = ask("lp", (B, m_max, n), env)
+            seen["lp"].add((L[0]["engine"], L[0]["rows"], int(len(L) == 3)))
+            assert len(L) == 1 or (L[0]["engine"], L[-1]["engine"]) == ("GROUP", "GENERAL")
+        for m_max, d, env in CHEBY:
+            L = ask("cheby", (B, m_max, d), env)[0]
+            seen["cheby"].add((L["engine"], L["rows"]))
+        for m_max, d, env in BBOX:
+            L = ask("bbox", (B, m_max, d), env)[0]
+            seen["bbox"].add((L["engine"], L["nw"], L["dense"]))
+    for n in (5, 20, 257):
+        npairs, n1 = n * (n - 1) // 2, n // 3 + 1
+        for m_max, d, env in PAIRS:
+            for sizes in ((n, m_max, d, 0, 0, 0, 0), (n, m_max, d, 3, npairs - 2, 1, 0), (n, m_max, d, 0, n1 * (n - n1), 1, n1)):
+                L = ask("pairs", sizes, env)[0]
+                seen["pairs"].add((L["engine"], L["gs"]))
+    for call, want in LP_REQUIRED.items():
+        assert seen[call] >= want, (call, want - seen[call])
+    assert {e[0] for want in LP_REQUIRED.values() for e in want} == set(LP_ENGINES) - {"NONE", "EMPTY"}
 
 
 @pytest.mark.parametrize("m_max,d,env,engine,shape", REDUCE, ids=ids(REDUCE))
