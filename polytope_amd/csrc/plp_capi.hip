@@ -1483,382 +1483,11 @@ int plp_selftest(plp_ctx* ctx, int group_size, double* out_d, uint32_t* out_u) {
 // ------------------------------------------------------------------------------- region_diff search
 }  // extern "C"
 
-struct plp_rdiff_result {
-    std::vector<int32_t> kind;   // per leaf: 0 = piece as is (ref :2229), 1 = piece to be reduce()d (ref :2276)
-    std::vector<int32_t> off;    // leaf k holds rows[off[k] .. off[k+1])
-    std::vector<int32_t> rows;
-    long long n_lps = 0, n_batches = 0, n_requests = 0, n_scan_miss = 0, n_node_miss = 0;
-};
+// The search is host code of its own (plp_rdiff_search.hpp: state, moves, radius memo, speculation); its batches of LPs
+// are solved by the device backend (plp_rdiff_host.hpp: resident LP server or a launch per batch).
+#include "plp_rdiff_host.hpp"
 
-namespace {
-
-// 128-bit order-dependent hash of a row list, extendable by a suffix (lists are "current rows + a few more")
-struct Key {
-    uint64_t a, b;
-    bool operator==(const Key& o) const { return a == o.a && b == o.b; }
-};
-inline Key key_push(Key k, int32_t r) {
-    k.a = (k.a ^ (uint64_t)(uint32_t)(r + 1)) * 0x9E3779B97F4A7C15ull;
-    k.a ^= k.a >> 29;
-    k.b = (k.b + (uint64_t)(uint32_t)(r + 1)) * 0xC2B2AE3D27D4EB4Full;
-    k.b ^= k.b >> 31;
-    return k;
-}
-inline Key key_of_list(const int32_t* r, size_t n) {
-    Key k{0x243F6A8885A308D3ull, 0x13198A2E03707344ull};
-    for (size_t i = 0; i < n; ++i) k = key_push(k, r[i]);
-    return k;
-}
-
-// open-addressing table Key -> radius; grows by rehashing, clear() touches only the occupied slots
-struct RadiusTable {
-    std::vector<Key> keys;
-    std::vector<double> vals;
-    std::vector<unsigned char> used;
-    std::vector<uint32_t> slots;   // occupied positions, in insertion order
-    size_t count = 0, mask = 0;
-    void reset(size_t cap_pow2) {
-        keys.assign(cap_pow2, Key{0, 0});
-        vals.assign(cap_pow2, 0.0);
-        used.assign(cap_pow2, 0);
-        slots.clear();
-        count = 0;
-        mask = cap_pow2 - 1;
-    }
-    void clear() {
-        for (uint32_t i : slots) used[i] = 0;
-        slots.clear();
-        count = 0;
-    }
-    const double* find(const Key& k) const {
-        for (size_t i = (size_t)k.a & mask;; i = (i + 1) & mask) {
-            if (!used[i]) return nullptr;
-            if (keys[i] == k) return &vals[i];
-        }
-    }
-    void put(const Key& k, double v) {
-        if ((count + 1) * 2 > mask) grow();
-        for (size_t i = (size_t)k.a & mask;; i = (i + 1) & mask) {
-            if (!used[i]) { used[i] = 1; keys[i] = k; vals[i] = v; ++count; slots.push_back((uint32_t)i); return; }
-            if (keys[i] == k) { vals[i] = v; return; }
-        }
-    }
-    void grow() {
-        std::vector<Key> ok;
-        std::vector<double> ov;
-        ok.reserve(count);
-        ov.reserve(count);
-        for (uint32_t i : slots) { ok.push_back(keys[i]); ov.push_back(vals[i]); }
-        reset((mask + 1) * 2);
-        for (size_t t = 0; t < ok.size(); ++t) put(ok[t], ov[t]);
-    }
-};
-
-// The Chebyshev radii the search asks for, keyed by the row list, filled by batches of LPs that are solved on the
-// device straight from the resident table (plp_rdiff.hip).  A miss triggers ONE batch holding the missing list
-// plus whatever the search will need next if the current node is not empty (speculation), so the search pays one
-// launch + one synchronisation per visited node instead of one per LP (the reference) or per scan.
-struct RadiusOracle {
-    plp_ctx* ctx;
-    int d;
-    long long nrows;
-    double *dA = nullptr, *dB = nullptr, *dOut = nullptr;
-    char* pin = nullptr;          // host-mapped block: [index block | radii | sequence word]
-    char* pin_dev = nullptr;      // the same block as the device sees it
-    volatile unsigned long long* flag = nullptr;
-    unsigned long long seq = 0;
-    size_t cap_lp = 0, cap_rows = 0;
-    RadiusTable memo, pending;    // pending: key -> position in the batch being assembled
-    std::vector<int32_t> prow, poff;
-    std::vector<Key> pkey;
-    long long n_lps = 0, n_batches = 0;
-    long long n_lps_long = 0, n_batches_long = 0;  // LPs of more than 64 rows (LDS engine) / batches that hold at least one (stats)
-    double t_launch = 0.0, t_wait = 0.0;  // seconds spent enqueueing / waiting for the device (PLP_RDIFF_STATS=1 prints them)
-    double t_store = 0.0;                 // ... and putting the radii of a batch into the memo
-    // ---- resident LP server (d <= 4; PLP_RDIFF_SERVER=0: every batch a launch, as in round 3)
-    static constexpr size_t SRV_MAXLP = 2048, SRV_OUT = 128, SRV_REC = SRV_OUT + SRV_MAXLP * 16;
-    static constexpr size_t SRV_BYTES = SRV_REC + SRV_MAXLP * 66 * 4;
-    static constexpr unsigned long long SRV_EXIT = ~0ull;
-    bool srv_on = false, srv_running = false;
-    long long n_srv_batches = 0, n_srv_starts = 0;
-    volatile unsigned long long* srv_mail() { return reinterpret_cast<volatile unsigned long long*>(ctx->rd_srv); }
-    volatile unsigned long long* srv_done() { return reinterpret_cast<volatile unsigned long long*>(ctx->rd_srv + 64); }
-    int srv_init() {
-        const char* e = getenv("PLP_RDIFF_SERVER");
-        if ((e && e[0] == '0') || d > 4) return PLP_OK;
-        if (!ctx->rd_srv) {
-            char *hp = nullptr, *hp_dev = nullptr;
-            unsigned long long* st8 = nullptr;
-            hipError_t err = hipHostMalloc(reinterpret_cast<void**>(&hp), SRV_BYTES, hipHostMallocMapped | hipHostMallocCoherent);
-            if (err == hipSuccess) err = hipHostGetDevicePointer(reinterpret_cast<void**>(&hp_dev), hp, 0);
-            if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&st8), 64);
-            if (err != hipSuccess) {
-                if (hp) (void)hipHostFree(hp);
-                (void)hipGetLastError();
-                return PLP_OK;   // no server: the launch path serves the search
-            }
-            memset(hp, 0, 128);
-            ctx->rd_srv = hp;
-            ctx->rd_srv_dev = hp_dev;
-            ctx->rd_srv_state = st8;
-            ctx->rd_srv_seq = 0;
-            ctx->rd_srv_word = 0;
-        }
-        srv_on = true;
-        return PLP_OK;
-    }
-    // last: the sequence number of the last batch that was answered.  pending: batch last + 1 is in the mailbox already
-    // (the server retired while it was on its way) -- the new server finds it there; else the mailbox says "nothing new".
-    int srv_start(unsigned long long last, bool pending) {
-        if (!pending) __atomic_store_n(srv_mail(), last, __ATOMIC_RELEASE);
-        __atomic_store_n(srv_done() + 1, 1ull, __ATOMIC_RELEASE);
-        ctx->rd_srv_init[0] = ctx->rd_srv_init[2] = ctx->rd_srv_init[3] = 0ull;   // word 0: "retire" flag
-        ctx->rd_srv_init[1] = last;                                                // word 1: the mailbox as the device republishes it
-        HIP_TRY(hipMemcpyAsync(ctx->rd_srv_state, ctx->rd_srv_init, 32, hipMemcpyHostToDevice, ctx->stream));
-        const char* ip = getenv("PLP_RDIFF_SERVER_IDLE");
-        const unsigned idle = ip ? (unsigned)atoi(ip) : 1500u;   // empty mailbox polls (~2 us each) before it retires
-        const char* wg = getenv("PLP_RDIFF_SERVER_WGS");
-        // workgroups (one wavefront each: 4 / 2 / 1 lists per round).  Measured at config 4 (751 batches, ~120 lists each, a
-        // few of up to 2048): waiting for the device 22.4 / 16.6 / 14.1 / 12.7 / 12.3 ms with 32 / 64 / 128 / 256 / 1024
-        // (the launch path: 4.3 ms of launches + 11.3 ms of waiting)
-        const int nwg = wg ? atoi(wg) : 256;
-        if (plp::launch_rdiff_server(d, nwg < 1 ? 1 : nwg, reinterpret_cast<const unsigned long long*>(ctx->rd_srv_dev),
-                                     reinterpret_cast<const int*>(ctx->rd_srv_dev + SRV_REC),
-                                     ctx->rd_srv_dev + SRV_OUT,
-                                     reinterpret_cast<unsigned long long*>(ctx->rd_srv_dev + 64 + 8), ctx->rd_srv_state, dA, dB,
-                                     last, idle, ctx->stream))
-            return fail(PLP_EUNSUPPORTED, "region_diff: no LP server for d=%d", d);
-        int rc = check_launch("rdiff_server");
-        if (rc) return rc;
-        srv_running = true;
-        ++n_srv_starts;
-        return PLP_OK;
-    }
-    void srv_stop() {
-        if (!srv_running) return;
-        __atomic_store_n(srv_mail(), SRV_EXIT, __ATOMIC_RELEASE);
-        (void)hipStreamSynchronize(ctx->stream);
-        srv_running = false;
-    }
-
-    int init(plp_ctx* c, int d_, long long nrows_, const double* A, const double* b) {
-        ctx = c; d = d_; nrows = nrows_;
-        cap_lp = 1 << 15;
-        cap_rows = (size_t)cap_lp * 64;
-        memo.reset(1 << 14);
-        pending.reset(1 << 12);
-        poff.assign(1, 0);
-        const size_t blk = (2 * cap_lp + 1 + cap_rows) * 4;
-        if (!ctx->rd_pin) {
-            // host-mapped, coherent: the kernels read the index block and publish the radii through it (no copies, no
-            // stream synchronisation per batch: the host spins on a sequence word the last kernel of the batch raises).
-            // Allocated into locals and committed to the context only when all three calls succeeded.
-            char *hp = nullptr, *hp_dev = nullptr;
-            double* dout = nullptr;
-            hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&hp), blk + cap_lp * 8 + 64,
-                                         hipHostMallocMapped | hipHostMallocCoherent);
-            if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&hp_dev), hp, 0);
-            if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&dout), cap_lp * 8);
-            if (e != hipSuccess) {
-                if (hp) (void)hipHostFree(hp);
-                (void)hipGetLastError();
-                return fail(PLP_EHIP, "region_diff: staging buffers: %s", hipGetErrorString(e));
-            }
-            *reinterpret_cast<volatile unsigned long long*>(hp + blk + cap_lp * 8) = 0ull;
-            ctx->rd_pin = hp;
-            ctx->rd_pin_dev = hp_dev;
-            ctx->rd_out = dout;
-            ctx->rd_seq = 0;
-        }
-        const size_t need = (size_t)nrows * (d + 1) * 8 + 64;
-        if (need > ctx->rd_tab_bytes) {
-            if (ctx->rd_tab) HIP_TRY(hipFree(ctx->rd_tab));
-            ctx->rd_tab = nullptr;
-            ctx->rd_tab_bytes = 0;
-            HIP_TRY(hipMalloc(reinterpret_cast<void**>(&ctx->rd_tab), need + need / 2));
-            ctx->rd_tab_bytes = need + need / 2;
-        }
-        pin = ctx->rd_pin;
-        pin_dev = ctx->rd_pin_dev;
-        dOut = ctx->rd_out;
-        dA = ctx->rd_tab;
-        dB = ctx->rd_tab + (size_t)nrows * d;
-        flag = reinterpret_cast<volatile unsigned long long*>(pin + blk + cap_lp * 8);
-        seq = ctx->rd_seq;
-        HIP_TRY(hipMemcpyAsync(dA, A, (size_t)nrows * d * 8, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(dB, b, (size_t)nrows * 8, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        return srv_init();
-    }
-    void release() {
-        if (ctx) { srv_stop(); (void)hipStreamSynchronize(ctx->stream); ctx->rd_seq = seq; }
-    }
-    // queue the list base[0..nb) + suf[0..ns) (key given) for the next batch unless known or queued already
-    // `required`: the search cannot continue without this radius; only speculative lists are subject to the bound
-    // on one batch
-    void want(const Key& k, const int32_t* base, size_t nb, const int32_t* suf, size_t ns, bool required = false) {
-        if (memo.find(k) || pending.find(k)) return;
-        if (!required && pkey.size() >= (1u << 16)) return;
-        pending.put(k, (double)pkey.size());
-        pkey.push_back(k);
-        prow.insert(prow.end(), base, base + nb);
-        prow.insert(prow.end(), suf, suf + ns);
-        poff.push_back((int32_t)prow.size());
-    }
-    // solve everything queued; results go to the memo
-    int flush() {
-        const size_t total = pkey.size();
-        size_t done = 0;
-        // radii are consumed soon after they are computed.  The memo is emptied only BEFORE the first sub-batch, never
-        // between two of them, so everything this call stores is there when it returns (a caller that skipped a list
-        // because it was known before the call asks again: see the retry loops of the search)
-        if (memo.count + total > (1u << 20)) memo.clear();
-        while (done < total) {
-            size_t n = 0, nr = 0;
-            while (done + n < total && n < cap_lp && nr + (size_t)(poff[done + n + 1] - poff[done + n]) <= cap_rows) {
-                nr += (size_t)(poff[done + n + 1] - poff[done + n]);
-                ++n;
-            }
-            if (n == 0) return fail(PLP_EUNSUPPORTED, "region_diff: a row list of %d rows exceeds the staging buffer", poff[done + 1] - poff[done]);
-            // one contiguous block per batch: [off (n + 1) | sel (n) | rows (nr)] -> ONE copy across PCIe
-            int32_t* off = reinterpret_cast<int32_t*>(pin);
-            int32_t* sel = off + n + 1;
-            int32_t* rows = sel + n;
-            const int32_t base0 = poff[done];
-            memcpy(rows, prow.data() + base0, nr * 4);
-            int cnt[5] = {0, 0, 0, 0, 0};
-            int max_len = 0;
-            for (size_t k = 0; k <= n; ++k) off[k] = poff[done + k] - base0;
-            // size classes: 0 / 1 / 2 = lists of up to 16 / 32 / 64 rows on the lane-group kernels (d <= 4), 3 = beyond 64 rows
-            // (LDS engine), 4 = d >= 5, up to 64 rows: one LP per wavefront (cheby_gather_w_kernel; PLP_RDIFF_WIDE=0: d = 5..8
-            // on the lane groups, d >= 9 on the LDS engine, as before round 3)
-            const char* rw_env = getenv("PLP_RDIFF_WIDE");
-            const bool rdiff_wide = !(rw_env && rw_env[0] == '0');
-            const char* rwm_env = getenv("PLP_RDIFF_WIDE_MIND");  // (A/B: smallest d that takes the one-LP-per-wavefront kernel)
-            const int rdiff_wide_mind = rwm_env ? atoi(rwm_env) : 5;
-            auto cls_of = [&](int len) {
-                if (len > 64) return 3;
-                if (d >= rdiff_wide_mind && rdiff_wide) return 4;
-                return d > 8 ? 3 : (len > 32 ? 2 : (len > 16 ? 1 : 0));
-            };
-            for (size_t k = 0; k < n; ++k) {
-                const int len = off[k + 1] - off[k];
-                max_len = len > max_len ? len : max_len;
-                cnt[cls_of(len)]++;
-            }
-            if (srv_on && n <= SRV_MAXLP && !cnt[3] && !cnt[4]) {
-                // ---- the resident server takes the batch: records by size class, header, sequence word; spin on done_seq
-                const auto tp0 = std::chrono::steady_clock::now();
-                int32_t* rec = reinterpret_cast<int32_t*>(ctx->rd_srv + SRV_REC);
-                int32_t* rc_[3] = {rec, rec + (size_t)cnt[0] * 18, rec + (size_t)cnt[0] * 18 + (size_t)cnt[1] * 34};
-                static const int cap_[3] = {16, 32, 64};
-                for (size_t k = 0; k < n; ++k) {
-                    const int len = off[k + 1] - off[k];
-                    const int c = cls_of(len);
-                    int32_t* r = rc_[c];
-                    r[0] = (int32_t)k;
-                    r[1] = len;
-                    memcpy(r + 2, prow.data() + base0 + off[k], (size_t)len * 4);
-                    rc_[c] = r + cap_[c] + 2;
-                }
-                if (!srv_running || __atomic_load_n(srv_done() + 1, __ATOMIC_ACQUIRE) == 0ull) {
-                    if (srv_running) { (void)hipStreamSynchronize(ctx->stream); srv_running = false; }   // it retired (idle)
-                    int rc = srv_start(ctx->rd_srv_word, false);
-                    if (rc) return rc;
-                }
-                // one word: [batch number : 28 | n2 : 12 | n1 : 12 | n0 : 12] (never 0, never all ones)
-                const unsigned long long last_word = ctx->rd_srv_word;
-                ctx->rd_srv_seq = (ctx->rd_srv_seq % 0xffffff0ull) + 1ull;
-                const unsigned long long sq = (ctx->rd_srv_seq << 36) | ((unsigned long long)cnt[2] << 24) |
-                                              ((unsigned long long)cnt[1] << 12) | (unsigned long long)cnt[0];
-                __atomic_store_n(srv_mail(), sq, __ATOMIC_RELEASE);
-                const auto tp1 = std::chrono::steady_clock::now();
-                // every radius arrives beside the batch's word (one 16-byte store of the lane group that solved it)
-                const volatile unsigned long long* sres = reinterpret_cast<const volatile unsigned long long*>(ctx->rd_srv + SRV_OUT);
-                unsigned long long spins = 0;
-                for (size_t k = 0; k < n;) {
-                    if (__atomic_load_n(&sres[2 * k + 1], __ATOMIC_ACQUIRE) == sq) { ++k; continue; }
-                    if ((++spins & 0x3fffull) == 0ull) {
-                        if (__atomic_load_n(srv_done() + 1, __ATOMIC_ACQUIRE) == 0ull) {
-                            // the server retired while the batch was on its way (or part of it did the batch and part did
-                            // not): start it again, it finds the batch in the mailbox and solves it (again)
-                            (void)hipStreamSynchronize(ctx->stream);
-                            int rc = srv_start(last_word, true);
-                            if (rc) return rc;
-                        }
-                        if (spins > 4000000000ull) return fail(PLP_EHIP, "region_diff: the LP server did not answer batch %llu", sq);
-                    }
-                }
-                const auto tp2 = std::chrono::steady_clock::now();
-                t_launch += std::chrono::duration<double>(tp1 - tp0).count();
-                t_wait += std::chrono::duration<double>(tp2 - tp1).count();
-                ctx->rd_srv_word = sq;
-                const double* sout = reinterpret_cast<const double*>(ctx->rd_srv + SRV_OUT);
-                for (size_t k = 0; k < n; ++k) memo.put(pkey[done + k], sout[2 * k]);
-                t_store += std::chrono::duration<double>(std::chrono::steady_clock::now() - tp2).count();
-                n_lps += (long long)n;
-                n_batches += 1;
-                n_srv_batches += 1;
-                done += n;
-                continue;
-            }
-            srv_stop();   // (a batch the server does not take: the launches below queue behind it on the same stream)
-            size_t start[5], fill[5];
-            start[0] = 0;
-            for (int c = 1; c < 5; ++c) start[c] = start[c - 1] + cnt[c - 1];
-            for (int c = 0; c < 5; ++c) fill[c] = start[c];
-            for (size_t k = 0; k < n; ++k) sel[fill[cls_of(off[k + 1] - off[k])]++] = (int32_t)k;
-            hipStream_t st = ctx->stream;
-            const auto tp0 = std::chrono::steady_clock::now();
-            const int32_t* d_off = reinterpret_cast<const int32_t*>(pin_dev);
-            const int32_t* d_sel = d_off + n + 1;
-            const int32_t* d_rows = d_sel + n;
-            if ((cnt[0] | cnt[1] | cnt[2]) &&
-                plp::launch_cheby_gather_r(d, cnt[0], cnt[1], cnt[2], d_off, d_rows, d_sel, dA, dB, dOut, st))
-                return fail(PLP_EUNSUPPORTED, "region_diff: gather kernel does not apply (d=%d)", d);
-            if (cnt[3] && plp::launch_cheby_gather_lds(d, max_len, cnt[3], d_off, d_rows, d_sel + start[3], dA, dB, dOut, st))
-                return fail(PLP_EUNSUPPORTED, "region_diff: a stack of %d rows does not fit the LDS engine", max_len);
-            if (cnt[4] && plp::launch_cheby_gather_w(d, cnt[4], d_off, d_rows, d_sel + start[4], dA, dB, dOut, st))
-                return fail(PLP_EUNSUPPORTED, "region_diff: gather kernel does not apply (d=%d)", d);
-            double* out = reinterpret_cast<double*>(pin + (2 * cap_lp + 1 + cap_rows) * 4);
-            double* out_dev = reinterpret_cast<double*>(pin_dev + (2 * cap_lp + 1 + cap_rows) * 4);
-            ++seq;
-            plp::launch_rdiff_publish((long long)n, dOut, out_dev,
-                                      reinterpret_cast<unsigned long long*>(pin_dev + (2 * cap_lp + 1 + cap_rows) * 4 + cap_lp * 8),
-                                      seq, st);
-            int rc = check_launch("cheby_gather");
-            if (rc) return rc;
-            const auto tp1 = std::chrono::steady_clock::now();
-            // spin on the sequence word (bounded: fall back to a stream synchronisation, which also reports errors)
-            {
-                unsigned long long spins = 0;
-                while (__atomic_load_n(const_cast<const unsigned long long*>(flag), __ATOMIC_ACQUIRE) != seq) {
-                    if (++spins > 400000000ull) { HIP_TRY(hipStreamSynchronize(st)); break; }
-                }
-                if (__atomic_load_n(const_cast<const unsigned long long*>(flag), __ATOMIC_ACQUIRE) != seq) {
-                    HIP_TRY(hipStreamSynchronize(st));
-                    if (*flag != seq) return fail(PLP_EHIP, "region_diff: batch %llu did not complete", seq);
-                }
-            }
-            const auto tp2 = std::chrono::steady_clock::now();
-            t_launch += std::chrono::duration<double>(tp1 - tp0).count();
-            t_wait += std::chrono::duration<double>(tp2 - tp1).count();
-            for (size_t k = 0; k < n; ++k) memo.put(pkey[done + k], out[k]);
-            n_lps += (long long)n;
-            n_batches += 1;
-            n_lps_long += cnt[3];
-            n_batches_long += cnt[3] ? 1 : 0;
-            done += n;
-        }
-        pkey.clear();
-        prow.clear();
-        poff.assign(1, 0);
-        pending.clear();
-        return PLP_OK;
-    }
-};
-
-}  // namespace
+struct plp_rdiff_result : plp::rdiff::Result { long long n_lps = 0, n_batches = 0; };
 
 extern "C" {
 
@@ -1868,321 +1497,28 @@ int plp_region_diff_search(plp_ctx* ctx, int d, int m, int N, const int32_t* mi,
     if (d < 1 || d > plp::MAX_D || m < 0 || N < 1) return fail(PLP_EINVAL, "bad sizes d=%d m=%d N=%d", d, m, N);
     *out = nullptr;
     long long M = 0;
-    std::vector<long long> beg(N);
     for (int j = 0; j < N; ++j) {
         if (mi[j] < 1) return fail(PLP_EINVAL, "mi[%d] = %d (a cell without a new constraint covers the polytope)", j, mi[j]);
-        beg[j] = m + M;
         M += mi[j];
     }
-    const long long nrows = m + 2 * M;
     HIP_TRY(hipSetDevice(ctx->device));
-    RadiusOracle R;
-    int rc = R.init(ctx, d, nrows, A, b);
-    if (rc) { R.release(); return rc; }
+    RdiffBackend be;
+    int rc = be.init(ctx, d, m + 2 * M, A, b);
+    if (rc) { be.release(); return rc; }
     plp_rdiff_result* res = new plp_rdiff_result();
-    res->off.push_back(0);
-    // Python's negative indexing of counter / mi / beg_mi (level == -1 reads the LAST cell, ref :2231) and of the
-    // table rows (an index that went below zero after "- M" wraps to the end of A, ref :2233)
-    auto at = [&](long long level) { return (int)(level < 0 ? level + N : level); };
-    std::vector<int> counter(N, 0);
-    std::vector<long long> idx(m);       // the reference's INDICES (may hold wrapped / out-of-range values)
-    for (int i = 0; i < m; ++i) idx[i] = i;
-    long long level = 0;
-    std::vector<int32_t> cur, suf;        // cur = idx resolved to table rows
-    bool cur_ok = true;
-    auto resolve = [&]() {
-        cur.resize(idx.size());
-        cur_ok = true;
-        for (size_t k = 0; k < idx.size(); ++k) {
-            long long r = idx[k] < 0 ? idx[k] + nrows : idx[k];
-            if (r < 0 || r >= nrows) { cur_ok = false; r = 0; }
-            cur[k] = (int32_t)r;
-        }
-    };
-    auto emit = [&](int kind) {
-        res->kind.push_back(kind);
-        res->rows.insert(res->rows.end(), cur.begin(), cur.end());
-        res->off.push_back((int32_t)res->rows.size());
-    };
-    // open cells (counter != 0) in ascending order and the sum of the counters, kept incrementally
-    std::vector<int> open_cells;
-    long long sumc = 0;
-    auto set_counter = [&](int L, int v) {
-        const int old = counter[L];
-        sumc += v - old;
-        counter[L] = v;
-        if (old == 0 && v != 0) open_cells.insert(std::lower_bound(open_cells.begin(), open_cells.end(), L), L);
-        else if (old != 0 && v == 0) open_cells.erase(std::lower_bound(open_cells.begin(), open_cells.end(), L));
-    };
-    // the move after a piece was emitted (ref :2230-2245: "level - 1", then re-open the cell there) on an explicit state
-    auto leaf_on = [&](std::vector<int>& cnt, std::vector<int>& open, std::vector<long long>& ix, long long& lvl,
-                       long long& sc) -> bool {
-        lvl = lvl - 1;
-        const int nz = (int)open.size();
-        for (int t = 0; t < nz; ++t) {
-            const int L = at(lvl);
-            if (cnt[L] <= mi[L]) {
-                ix.back() -= M;
-                ix.push_back(beg[L] + cnt[L] + M);
-                return false;
-            }
-            sc -= cnt[L];
-            cnt[L] = 0;
-            open.erase(std::lower_bound(open.begin(), open.end(), L));
-            const long long keep_n = m + sc;
-            if ((long long)ix.size() > keep_n) ix.resize(keep_n < 0 ? 0 : keep_n);
-            if (lvl == -1) return true;
-        }
-        return false;
-    };
-    // the "next sibling" move (ref :2246-2271) on an explicit state, so that it can also be run on a COPY to see which
-    // nodes follow when the current one turns out empty; returns true when the search ends
-    auto advance_on = [&](std::vector<int>& cnt, std::vector<int>& open, std::vector<long long>& ix, long long& lvl,
-                          long long& sc) -> bool {
-        auto setc = [&](int L, int v) {
-            const int old = cnt[L];
-            sc += v - old;
-            cnt[L] = v;
-            if (old == 0 && v != 0) open.insert(std::lower_bound(open.begin(), open.end(), L), L);
-            else if (old != 0 && v == 0) open.erase(std::lower_bound(open.begin(), open.end(), L));
-        };
-        while (!open.empty()) {   // deepest open cell first (the reference walks nzcount backwards)
-            lvl = open.back();
-            setc((int)lvl, cnt[lvl] + 1);
-            if (cnt[lvl] <= mi[lvl]) {
-                ix.back() -= M;
-                ix.push_back(beg[lvl] + cnt[lvl] + M - 1);
-                return false;
-            }
-            setc((int)lvl, 0);
-            const long long keep_n = m + sc;
-            if ((long long)ix.size() > keep_n) ix.resize(keep_n < 0 ? 0 : keep_n);
-            lvl = lvl - 1;
-            if (lvl == -1) return true;
-        }
-        return false;
-    };
-    // ---- what earlier scans already decided.  A cell whose stack with the rows of an ANCESTOR node had radius
-    // <= abs_tol / 2 cannot reach abs_tol with more rows added (the set only shrinks; LP values are exact to ~1e-12),
-    // so its LP is not issued again below that node: it counts as "no hit", which is what the reference would find.
-    // A frame = the rows a scan was made with + the cells that stayed alive; it is used only while the current rows
-    // contain all of its rows (checked, because the reference's INDICES arithmetic does not always nest).
-    struct Frame { std::vector<int32_t> rows; std::vector<int> alive; };
-    std::vector<Frame> frames;
-    std::vector<int> mult(nrows, 0);
-    std::vector<int> all_cells(N);
-    for (int j = 0; j < N; ++j) all_cells[j] = j;
-    auto alive_now = [&]() -> const std::vector<int>& {  // needs `cur` resolved
-        for (int32_t r : cur) mult[r]++;
-        while (!frames.empty()) {
-            bool sub = true;
-            for (int32_t r : frames.back().rows) if (!mult[r]) { sub = false; break; }
-            if (sub) break;
-            frames.pop_back();
-        }
-        for (int32_t r : cur) mult[r]--;
-        return frames.empty() ? all_cells : frames.back().alive;
-    };
-    // How far the speculation goes (A/B knobs; scripts/debug/rdiff_spec_sweep.sh).  Rounds 3-4 tuned it for the
-    // fewest batches (SIB = 600, DEEP = 1: 751 batches of 89 724 LPs at config 4); the host pays ~50 ns per speculated list
-    // (assembling + storing) and only 8 833 radii are ever read.  Measured: SIB = 100, DEEP = 0 -> 808 batches of 41 335 LPs,
-    // the call 21.2-23 -> 18.8-19.2 ms; no speculation beyond the chain (SIB = 0): 985 batches, 19.8-20.6 ms.
-    auto env_int = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
-    const int spec_sib = env_int("PLP_RDIFF_SPEC_SIB", 100);        // bound on the lists of a cell's sibling chain
-    const int spec_chain_scan = env_int("PLP_RDIFF_SPEC_CHAIN_SCAN", 6), spec_chain_node = env_int("PLP_RDIFF_SPEC_CHAIN_NODE", 8);
-    const int spec_deep = env_int("PLP_RDIFF_SPEC_DEEP", 0);        // the first alive cell's child scan one level down
-    const int spec_child = env_int("PLP_RDIFF_SPEC_CHILD", 1);      // the first child of every alive cell with a scan
-    // queue, for every alive cell j >= from: the stack of the current rows with ALL its new rows (the scan, ref
-    // :2212-2224) and with its first new row negated (the node the search enters when j is the first hit)
-    std::vector<int32_t> child;
-    // `required`: the scan lists are what the search is waiting for (queued first, exempt from the bound on a batch);
-    // the first children are speculation
-    auto queue_scan1 = [&](const std::vector<int>& alive, long long from, const Key& kbase, const std::vector<int32_t>& base,
-                           bool required) {
-        for (int j : alive) {
-            if (j < from) continue;
-            suf.resize(mi[j]);
-            Key k = kbase;
-            for (int t = 0; t < mi[j]; ++t) { suf[t] = (int32_t)(beg[j] + t); k = key_push(k, suf[t]); }
-            R.want(k, base.data(), base.size(), suf.data(), suf.size(), required);
-        }
-        if (spec_child)
-        for (int j : alive) {
-            if (j < from) continue;
-            const int32_t neg = (int32_t)(beg[j] + M);
-            R.want(key_push(kbase, neg), base.data(), base.size(), &neg, 1);
-        }
-    };
-    // ... and the same one level further down for the cell the scan will most likely stop at (the first one still
-    // alive): when that guess is right the search descends two levels on one batch
-    auto queue_scan = [&](const std::vector<int>& alive, long long from, const Key& kbase, bool required) {
-        queue_scan1(alive, from, kbase, cur, required);
-        for (int j : alive) {
-            if (j < from) continue;
-            if (j < N - 1 && spec_deep) {
-                child = cur;
-                child.push_back((int32_t)(beg[j] + M));
-                queue_scan1(alive, (long long)j + 1, key_push(kbase, (int32_t)(beg[j] + M)), child, false);
-            }
-            // ... and its whole sibling chain (rows 1..c-1 of the cell kept, row c negated) with the scans they need when
-            // they are not empty, as long as that stays a few hundred lists
-            long long n_after = 0;
-            for (int a : alive) n_after += a > j;
-            if ((long long)mi[j] * (2 * n_after + 1) <= spec_sib) {
-                child = cur;
-                Key kc = kbase;
-                for (int c = 2; c <= mi[j]; ++c) {
-                    child.push_back((int32_t)(beg[j] + c - 2));
-                    kc = key_push(kc, (int32_t)(beg[j] + c - 2));
-                    const int32_t neg = (int32_t)(beg[j] + c - 1 + M);
-                    R.want(key_push(kc, neg), child.data(), child.size(), &neg, 1);
-                    if (j < N - 1) {
-                        child.push_back(neg);
-                        queue_scan1(alive, (long long)j + 1, key_push(kc, neg), child, false);
-                        child.pop_back();
-                    }
-                }
-            }
-            break;
-        }
-    };
-    // queue the nodes the search visits from the state (c2, o2, i2, l2, s2) on while every node turns out empty: its own
-    // moves run on the copy, so the lists are exactly the ones it will form (odd turns of the INDICES arithmetic included)
-    std::vector<int32_t> sim;
-    auto want_state = [&](const std::vector<long long>& i2) -> bool {
-        sim.resize(i2.size());
-        for (size_t k = 0; k < i2.size(); ++k) {
-            long long r = i2[k] < 0 ? i2[k] + nrows : i2[k];
-            if (r < 0 || r >= nrows) return false;
-            sim[k] = (int32_t)r;
-        }
-        R.want(key_of_list(sim.data(), sim.size()), sim.data(), sim.size(), nullptr, 0);
-        return true;
-    };
-    auto queue_empty_chain = [&](std::vector<int>& c2, std::vector<int>& o2, std::vector<long long>& i2, long long l2,
-                                 long long s2, int steps) {
-        for (int step = 0; step < steps; ++step) {
-            if (l2 == -1 || c2[at(l2)] == 0) break;               // the next move would be a scan (or the end)
-            if (advance_on(c2, o2, i2, l2, s2)) break;
-            if (!want_state(i2)) break;
-        }
-    };
-    rc = PLP_OK;
-    bool bad_index = false;
+    plp::rdiff::Search<RdiffBackend> search(m, N, mi, abs_tol, be.env.spec, be, *res);
     const auto t_search0 = std::chrono::steady_clock::now();
-    double t_spec = 0.0;   // seconds spent assembling the lists of a batch (PLP_RDIFF_STATS)
-    while (level != -1 && rc == PLP_OK) {
-        if (counter[at(level)] == 0) {
-            // ---- scan: first cell j >= level whose stack with the current rows is full-dimensional
-            resolve();
-            if (!cur_ok) { bad_index = true; break; }
-            const Key kbase = key_of_list(cur.data(), cur.size());
-            const std::vector<int>& alive = alive_now();
-            bool have_all = false;
-            for (int attempt = 0; attempt < 3; ++attempt) {  // (a full memo is emptied by flush(): ask again then)
-                bool miss = false;
-                for (int j : alive) {
-                    if (j < level) continue;
-                    Key k = kbase;
-                    for (int t = 0; t < mi[j]; ++t) k = key_push(k, (int32_t)(beg[j] + t));
-                    if (!R.memo.find(k)) { miss = true; break; }
-                }
-                if (!miss) { have_all = true; break; }
-                res->n_scan_miss++;
-                const auto ts0 = std::chrono::steady_clock::now();
-                queue_scan(alive, level, kbase, true);
-                {   // the outcome "no cell hits": a piece is emitted, then the node the search re-opens and what follows it
-                    std::vector<int> c2 = counter, o2 = open_cells;
-                    std::vector<long long> i2 = idx;
-                    long long l2 = level, s2 = sumc;
-                    if (!leaf_on(c2, o2, i2, l2, s2) && want_state(i2)) queue_empty_chain(c2, o2, i2, l2, s2, spec_chain_scan);
-                }
-                t_spec += std::chrono::duration<double>(std::chrono::steady_clock::now() - ts0).count();
-                rc = R.flush();
-                if (rc) break;
-            }
-            if (rc) break;
-            if (!have_all) {   // the last attempt flushed: everything it stored is in the memo unless the memo cannot hold one scan
-                for (int j : alive) {
-                    if (j < level) continue;
-                    Key k = kbase;
-                    for (int t = 0; t < mi[j]; ++t) k = key_push(k, (int32_t)(beg[j] + t));
-                    if (!R.memo.find(k)) { rc = fail(PLP_EUNSUPPORTED, "region_diff: a scan over %d cells does not fit the radius memo", N); break; }
-                }
-                if (rc) break;
-            }
-            double Rl = 0.0;  // the reference's R after the loop: the radius of the LAST cell looked at
-            Frame fr;
-            fr.rows = cur;
-            long long hit = -1;
-            for (int j : alive) {
-                if (j < level) continue;
-                Key k = kbase;
-                for (int t = 0; t < mi[j]; ++t) k = key_push(k, (int32_t)(beg[j] + t));
-                const double Rraw = *R.memo.find(k);
-                // NaN = the LP ended without a verdict (unbounded ball, iteration limit): the reference reads radius 0
-                // there (ref :1294-1297) and solves the cell again at every node below, so only a cell whose LP was
-                // SOLVED with a radius <= abs_tol / 2 is dropped from the scans below this node
-                if (!(Rraw <= 0.5 * abs_tol)) fr.alive.push_back(j);
-                const double Rj = Rraw != Rraw ? 0.0 : Rraw;
-                if (hit < 0) {
-                    res->n_requests++;
-                    if (Rj > abs_tol) { hit = j; Rl = Rj; }
-                    else if (j == N - 1) Rl = Rj;
-                }
-            }
-            frames.push_back(std::move(fr));
-            if (hit >= 0) {
-                level = hit;
-                set_counter((int)level, 1);
-                idx.push_back(beg[level] + M);
-            }
-            if (Rl < abs_tol) {  // nothing left to subtract: the current rows are a piece (ref :2226-2245)
-                emit(0);
-                if (leaf_on(counter, open_cells, idx, level, sumc)) break;
-            }
-        } else {
-            // ---- next sibling of the deepest open cell, closing exhausted cells on the way (ref :2246-2271)
-            if (advance_on(counter, open_cells, idx, level, sumc)) break;
-        }
-        // ---- the node itself
-        resolve();
-        if (!cur_ok) { bad_index = true; break; }
-        const Key knode = key_of_list(cur.data(), cur.size());
-        if (!R.memo.find(knode)) {
-            res->n_node_miss++;
-            const auto ts0 = std::chrono::steady_clock::now();
-            R.want(knode, cur.data(), cur.size(), nullptr, 0, true);
-            {
-                std::vector<int> c2 = counter, o2 = open_cells;
-                std::vector<long long> i2 = idx;
-                queue_empty_chain(c2, o2, i2, level, sumc, spec_chain_node);
-            }
-            // what it needs next when it is NOT empty: its scan and the first child of every cell still alive
-            if (level >= 0 && level < N - 1) queue_scan(alive_now(), level + 1, knode, false);
-            t_spec += std::chrono::duration<double>(std::chrono::steady_clock::now() - ts0).count();
-            rc = R.flush();
-            if (rc) break;
-        }
-        const double* pnode = R.memo.find(knode);
-        if (!pnode) { rc = fail(PLP_EHIP, "region_diff: the radius of the current node is missing after its batch"); break; }
-        const double rcv = *pnode != *pnode ? 0.0 : *pnode;
-        res->n_requests++;
-        if (rcv > abs_tol) {
-            if (level == N - 1) emit(1);
-            else level = level + 1;
-        }
-    }
-    res->n_lps = R.n_lps;
-    res->n_batches = R.n_batches;
-    if (getenv("PLP_RDIFF_STATS"))
+    rc = search.run();
+    res->n_lps = be.n_lps;
+    res->n_batches = be.n_batches;
+    if (be.env.stats)
         fprintf(stderr, "plp_region_diff_search: %lld LPs, %lld batches (%lld scan misses, %lld node misses), %lld requests, launch %.1f ms, device wait %.1f ms; beyond 64 rows: %lld LPs in %lld batches; resident server: %lld batches, %lld starts; search loop %.1f ms of which assembling the batches' lists %.1f ms, storing results %.1f ms\n",
-                R.n_lps, R.n_batches, res->n_scan_miss, res->n_node_miss, res->n_requests, R.t_launch * 1e3, R.t_wait * 1e3,
-                R.n_lps_long, R.n_batches_long, R.n_srv_batches, R.n_srv_starts,
-                std::chrono::duration<double>(std::chrono::steady_clock::now() - t_search0).count() * 1e3, t_spec * 1e3, R.t_store * 1e3);
-    R.release();
-    if (rc == PLP_OK && bad_index) rc = fail(PLP_EINVAL, "region_diff: row index out of range (the reference raises IndexError here)");
-    if (rc) { delete res; return rc; }
+                be.n_lps, be.n_batches, res->n_scan_miss, res->n_node_miss, res->n_requests, be.t_launch * 1e3, be.t_wait * 1e3,
+                be.n_lps_long, be.n_batches_long, be.n_srv_batches, be.n_srv_starts,
+                std::chrono::duration<double>(std::chrono::steady_clock::now() - t_search0).count() * 1e3, search.t_spec * 1e3,
+                search.R.t_store * 1e3);
+    be.release();
+    if (rc) { delete res; return rdiff_fail(rc, N, search.R.too_long); }
     *out = res;
     return PLP_OK;
 }

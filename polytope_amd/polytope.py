@@ -1759,7 +1759,7 @@ def region_diff(poly, reg, abs_tol=ABS_TOL, intersect_tol=ABS_TOL, save=False, _
         scale = 1 / norms
         An, Bn = A * scale[:, None], B * scale
     if packed and abs_tol > 0 and not save and _RDIFF_NATIVE:
-        # The search itself runs in the library (csrc/plp_capi.hip: plp_region_diff_search): the reference's
+        # The search itself runs in the library (plp_region_diff_search; csrc/plp_rdiff_search.hpp): the reference's
         # visiting order and tests, LPs gathered on the device from the resident table by row index, one launch and
         # one synchronisation per visited node.  What comes back are the pieces as row lists, in order.
         from .batch import region_diff_search
@@ -1808,7 +1808,7 @@ def region_diff(poly, reg, abs_tol=ABS_TOL, intersect_tol=ABS_TOL, save=False, _
                 res[k] = np.double(out["r"][t]) if ok[t] else (0 if out["status"][t] == 0 else float("nan"))
         return res
 
-    # Host twin of the library's search (csrc/plp_capi.hip, plp_region_diff_search): the same state, moves and
+    # Host twin of the library's search (csrc/plp_rdiff_search.hpp, plp_region_diff_search): the same state, moves and
     # inheritance of empty cells, driven through `radii_rows` -- what the non-'hip' backends run, and the A/B partner
     # of the library search on the GPU (tests: both must return the same pieces).
     search = _DiffSearch(m, mi, beg, M, abs_tol, radii_rows, look_ahead=packed)
