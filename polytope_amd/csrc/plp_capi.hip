@@ -1385,11 +1385,22 @@ static int check_pair_range(plp_ctx* ctx, int n, int m_max, int d, const double*
     return PLP_OK;
 }
 
+// the scratch of the pair calls' careful pass (plp_verify.hip: launch_careful_pairs); nullptr, no such pass, with PLP_VERIFY=0
+static int pair_scratch(plp_ctx* ctx, void* stream, void** sc) {
+    *sc = nullptr;
+    if (!plp::verify_enabled()) return PLP_OK;
+    *sc = stream_buf(ctx->vf_scratch, stream, plp::pair_careful_scratch_bytes());
+    if (!*sc) return fail(PLP_EHIP, "pair LPs: no device memory for the careful pass (%zu bytes)", plp::pair_careful_scratch_bytes());
+    return PLP_OK;
+}
+
 int plp_adjacent_pairs_dev(plp_ctx* ctx, void* stream, int n, int m_max, int d, const double* A, const double* b,
                            const int32_t* m, double abs_tol, uint8_t* adj) {
     int rc = check_pairs(ctx, n < 0, n == 0, m_max, d, A, b, adj);
     if (rc || n == 0) return rc;
-    if (plp::launch_adjacent(n, m_max, d, A, b, m, abs_tol, abs_tol / 10, adj, 0, 0, nullptr, (hipStream_t)stream))
+    void* sc;
+    if ((rc = pair_scratch(ctx, stream, &sc))) return rc;
+    if (plp::launch_adjacent(n, m_max, d, A, b, m, abs_tol, abs_tol / 10, adj, 0, 0, nullptr, (hipStream_t)stream, 0, sc))
         return fail(PLP_EUNSUPPORTED, "adjacent kernel: unsupported size");
     return check_launch("adjacent_r_kernel");
 }
@@ -1398,7 +1409,9 @@ int plp_overlap_pairs_dev(plp_ctx* ctx, void* stream, int n, int m_max, int d, c
                           const int32_t* m, double abs_tol, uint8_t* out) {
     int rc = check_pairs(ctx, n < 0, n == 0, m_max, d, A, b, out);
     if (rc || n == 0) return rc;
-    if (plp::launch_adjacent(n, m_max, d, A, b, m, 0.0, abs_tol, out, 0, 0, nullptr, (hipStream_t)stream))
+    void* sc;
+    if ((rc = pair_scratch(ctx, stream, &sc))) return rc;
+    if (plp::launch_adjacent(n, m_max, d, A, b, m, 0.0, abs_tol, out, 0, 0, nullptr, (hipStream_t)stream, 0, sc))
         return fail(PLP_EUNSUPPORTED, "adjacent kernel: unsupported size");
     return check_launch("adjacent_r_kernel");
 }
@@ -1407,8 +1420,10 @@ int plp_overlap_cross_dev(plp_ctx* ctx, void* stream, int n1, int n2, int m_max,
                           const int32_t* m, double thresh, uint8_t* out) {
     int rc = check_cross(ctx, n1, n2, m_max, d, A, b, out);
     if (rc || n1 == 0 || n2 == 0) return rc;
+    void* sc;
+    if ((rc = pair_scratch(ctx, stream, &sc))) return rc;
     if (plp::launch_adjacent(n1 + n2, m_max, d, A, b, m, 0.0, thresh, nullptr, 0, (long long)n1 * n2, out,
-                             (hipStream_t)stream, n1))
+                             (hipStream_t)stream, n1, sc))
         return fail(PLP_EUNSUPPORTED, "adjacent kernel: unsupported size");
     return check_launch("adjacent_r_kernel");
 }
@@ -1418,8 +1433,10 @@ int plp_adjacent_pairs_range_dev(plp_ctx* ctx, void* stream, int n, int m_max, i
                                  int64_t pair_hi, uint8_t* out) {
     int rc = check_pair_range(ctx, n, m_max, d, A, b, pair_lo, pair_hi, out, true);
     if (rc || pair_lo == pair_hi) return rc;
+    void* sc;
+    if ((rc = pair_scratch(ctx, stream, &sc))) return rc;
     if (plp::launch_adjacent(n, m_max, d, A, b, m, abs_tol, abs_tol / 10, nullptr, pair_lo, pair_hi, out,
-                             (hipStream_t)stream))
+                             (hipStream_t)stream, 0, sc))
         return fail(PLP_EUNSUPPORTED, "adjacent kernel: unsupported size");
     return check_launch("adjacent_r_kernel");
 }

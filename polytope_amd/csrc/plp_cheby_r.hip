@@ -21,7 +21,7 @@ int launch_adjacent_r(int d, const LpLaunch& L, int force_retry, const PairArgs&
         return for_gs<RowsPerLane<D>::value>(L.gs, [&](auto G) {
             hipLaunchKernelGGL((adjacent_r_kernel<D, decltype(G)::value>), dim3((unsigned)L.grid), dim3(L.block), L.lds, st, a.n,
                                a.m_max, a.A, a.b, a.mrows, a.inflate, a.thresh, a.adj, a.p_lo, a.p_hi, a.compact, force_retry,
-                               a.cross_n1);
+                               a.cross_n1, a.mark);
         });
     });
 }

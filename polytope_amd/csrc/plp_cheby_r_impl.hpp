@@ -317,7 +317,7 @@ template <int D, int GS>
 __global__ __launch_bounds__(RBLK, (D <= 4 ? 3 : 1)) void adjacent_r_kernel(
     int n, int m_max, const double* __restrict__ A, const double* __restrict__ b, const int* __restrict__ mrows,
     double inflate, double thresh, unsigned char* __restrict__ adj, long long p_lo, long long p_hi,
-    unsigned char* __restrict__ compact, int force_retry, int cross_n1) {
+    unsigned char* __restrict__ compact, int force_retry, int cross_n1, int mark) {
     const Grp g(GS);
     constexpr int gpb = RBLK / GS;
     const int gib = threadIdx.x / GS;
@@ -345,13 +345,15 @@ __global__ __launch_bounds__(RBLK, (D <= 4 ? 3 : 1)) void adjacent_r_kernel(
         [&](int rr) { return b[((rr < mi) ? i : j) * m_max + ((rr < mi) ? rr : rr - mi)] + inflate; },  // b1 += abs_tol; b2 += abs_tol
         x, force_retry);
     const bool yes = (st == ST_OPT) & (x[D] > thresh);
+    // (mark: "unbounded" / the iteration limit is not a verdict -- the careful pass that follows decides, plp_kernels.hpp)
+    const unsigned char verdict = yes ? 1 : ((mark != 0) & ((st == ST_UNBND) | (st == ST_ITER)) ? PAIR_OPEN : 0);
     if (compact) {
-        if (valid & (g.gl == 0)) compact[p - p_lo] = yes ? 1 : 0;
+        if (valid & (g.gl == 0)) compact[p - p_lo] = verdict;
         return;
     }
     if (valid & (g.gl == 0)) {
-        adj[i * n + j] = yes ? 1 : 0;
-        adj[j * n + i] = yes ? 1 : 0;
+        adj[i * n + j] = verdict;
+        adj[j * n + i] = verdict;
     }
     // diagonal
     const long long t = (long long)blockIdx.x * RBLK + threadIdx.x;

@@ -89,9 +89,19 @@ int launch_bbox(long long B, int m_max, int d, const double* A, const double* b,
 // a pair counts iff the Chebyshev radius of the two stacked cells, each b inflated by `inflate`, exceeds `thresh`
 // cross_n1 > 0 (compact only): the table holds two lists, n1 cells then n - n1 cells, and pair p = a (n - n1) + c is cell a
 // of the first list stacked on cell c of the second (p_lo <= p < p_hi within [0, n1 (n - n1)))
+// careful_scratch (pair_careful_scratch_bytes() bytes of device memory, or nullptr): a pair whose stacked LP the engines end
+// "unbounded" or at their iteration limit is written as PAIR_OPEN and solved again by the careful engine of plp_verify.hpp in
+// a launch that follows (launch_careful_pairs) -- on rows a hair apart the engines' "unbounded" can be a bounded LP, and the
+// stand-alone Chebyshev batches send every such answer there too; nullptr: those pairs count as "no" (PLP_VERIFY=0)
+constexpr unsigned char PAIR_OPEN = 2;
 int launch_adjacent(int n, int m_max, int d, const double* A, const double* b, const int* mrows, double inflate,
                     double thresh, unsigned char* adj, long long p_lo, long long p_hi, unsigned char* compact,
-                    hipStream_t st, int cross_n1 = 0);
+                    hipStream_t st, int cross_n1 = 0, void* careful_scratch = nullptr);
+size_t pair_careful_scratch_bytes();
+// what launch_adjacent wrote with the pairs marked PAIR_OPEN: those pairs decided by the careful engine, one pair per thread
+void launch_careful_pairs(int n, int m_max, int d, const double* A, const double* b, const int* mrows, double inflate,
+                          double thresh, unsigned char* adj, long long p_lo, long long p_hi, unsigned char* compact,
+                          int cross_n1, void* scratch, hipStream_t st);
 
 // Fused reduce() of up to 64 rows (plp_reduce.hip).  The batch, the outputs, and what the fast kernels report besides:
 struct ReduceArgs {

@@ -258,15 +258,19 @@ int launch_bbox(long long B, int m_max, int d, const double* A, const double* b,
 // compact == nullptr: all pairs into the n x n matrix adj; else pairs [p_lo, p_hi) into compact[p - p_lo]
 int launch_adjacent(int n, int m_max, int d, const double* A, const double* b, const int* mrows, double inflate,
                     double thresh, unsigned char* adj, long long p_lo, long long p_hi, unsigned char* compact,
-                    hipStream_t st, int cross_n1) {
+                    hipStream_t st, int cross_n1, void* careful_scratch) {
     const PairPlan p = plan_pairs(n, m_max, d, p_lo, p_hi, compact != nullptr, cross_n1, lp_env());
-    const PairArgs a{n, m_max, A, b, mrows, inflate, thresh, adj, p.p_lo, p.p_hi, compact, cross_n1};
+    const PairArgs a{n, m_max, A, b, mrows, inflate, thresh, adj, p.p_lo, p.p_hi, compact, cross_n1, careful_scratch ? 1 : 0};
+    int rc;
     switch (p.first.engine) {
         case LE_EMPTY: return 0;
-        case LE_WIDE: return launch_adjacent_w(d, p.first, a, st);
-        case LE_GROUP: return launch_adjacent_r(d, p.first, p.force_retry, a, st);
+        case LE_WIDE: rc = launch_adjacent_w(d, p.first, a, st); break;
+        case LE_GROUP: rc = launch_adjacent_r(d, p.first, p.force_retry, a, st); break;
         default: return 2;
     }
+    if (rc == 0 && careful_scratch)
+        launch_careful_pairs(n, m_max, d, A, b, mrows, inflate, thresh, adj, p.p_lo, p.p_hi, compact, cross_n1, careful_scratch, st);
+    return rc;
 }
 
 }  // namespace plp

@@ -24,6 +24,7 @@ struct PairArgs {
     long long p_lo, p_hi;
     unsigned char* compact;
     int cross_n1;
+    int mark;   // an LP that ends "unbounded" or at the iteration limit is written as PAIR_OPEN (the careful pass follows), not 0
 };
 
 // f(std::integral_constant<int, K>()) for K == d in LO .. HI -> what f returns (0 when nothing); 2 when d is outside (the

@@ -375,6 +375,65 @@ __global__ __launch_bounds__(VBLK) void careful_kernel(int m_max, int n, const d
     }
 }
 
+// ---- the pair calls (launch_adjacent, plp_lp.hip): the pairs the engines left PAIR_OPEN -- their stacked Chebyshev LP ended
+// "unbounded" or at the iteration limit -- one pair per thread: the two cells' live rows stacked into the thread's staging
+// rows with b + inflate, solved from scratch by careful_solve, the pair counts iff optimal with r > thresh (what the engines'
+// kernels write for an LP they do solve).  Every thread strides over the pairs and reads their bytes; no list, no counter.
+constexpr long long PAIR_SLOTS = 1024;
+constexpr size_t PAIR_STAGE = (size_t)MAX_M * (MAX_D + 1);   // doubles per thread: 64 rows of up to 16 entries, then 64 right-hand sides
+
+__global__ __launch_bounds__(VBLK) void careful_pairs_kernel(int n, int m_max, int d, const double* __restrict__ A,
+                                                             const double* __restrict__ b, const int* __restrict__ mrows,
+                                                             double inflate, double thresh, unsigned char* __restrict__ adj,
+                                                             long long p_lo, long long p_hi, unsigned char* __restrict__ compact,
+                                                             int cross_n1, double* hi, double* lo, int* rowinfo, double* stage) {
+    const long long slot = (long long)blockIdx.x * VBLK + threadIdx.x;
+    if (slot >= PAIR_SLOTS) return;
+    CarefulMem M{hi + slot, lo + slot, rowinfo + slot, PAIR_SLOTS};
+    double* G = stage + (size_t)slot * PAIR_STAGE;
+    double* h = G + (size_t)MAX_M * MAX_D;
+    for (long long p = p_lo + slot; p < p_hi; p += PAIR_SLOTS) {
+        // p -> (i, j) as the engines' kernels map it (adjacent_r_kernel, plp_cheby_r_impl.hpp)
+        long long i = (long long)((1.0 + sqrt(1.0 + 8.0 * (double)p)) * 0.5);
+        while (i * (i - 1) / 2 > p) --i;
+        while ((i + 1) * i / 2 <= p) ++i;
+        long long j = p - i * (i - 1) / 2;
+        if (cross_n1 > 0) {
+            const long long n2 = n - cross_n1;
+            i = p / n2;
+            j = cross_n1 + (p - i * n2);
+        }
+        unsigned char* out = compact ? compact + (p - p_lo) : adj + i * n + j;
+        if (*out != PAIR_OPEN) continue;
+        const int mi = mrows ? mrows[i] : m_max, mj = mrows ? mrows[j] : m_max;
+        const int m = mi + mj;
+        bool yes = false;
+        if (mi >= 0 && mj >= 0 && m <= MAX_M && d >= 1 && d <= MAX_D) {
+            for (int r = 0; r < m; ++r) {
+                const long long src = (r < mi) ? i * m_max + r : j * m_max + (r - mi);
+                for (int k = 0; k < d; ++k) G[(size_t)r * d + k] = A[src * d + k];
+                h[r] = b[src] + inflate;
+            }
+            LpView lp;
+            lp.m = m;
+            lp.n = d + 1;
+            lp.kind = LP_CHEBY;
+            lp.side = 0;
+            lp.G = G;
+            lp.h = h;
+            lp.c = nullptr;
+            double xo[VNMAX], f = 0.0;
+            int st = careful_solve(lp, M, xo, &f, nullptr);
+            double xm = 0.0;
+            for (int k = 0; k <= d; ++k) xm = fmax(xm, fabs(xo[k]));
+            st = range_rule(lp, st, f, xm);
+            yes = (st == V_OPT) && (xo[d] > thresh);
+        }
+        *out = yes ? 1 : 0;
+        if (!compact) adj[j * n + i] = yes ? 1 : 0;
+    }
+}
+
 bool verify_off() {
     static const int off = [] {
         const char* e = getenv("PLP_VERIFY");
@@ -392,6 +451,31 @@ size_t verify_scratch_bytes(long long nlp, int m_max) {
 }
 
 bool verify_enabled() { return !verify_off(); }
+
+// the careful pass of the pair calls: [256 bytes of the verifier's counters, left alone | hi | lo | row info | staging rows]
+size_t pair_careful_scratch_bytes() {
+    const size_t nd = careful_doubles_per_lp(MAX_M) * PAIR_SLOTS;
+    return 256 + 2 * pad256(nd * 8) + pad256((size_t)(MAX_M + 2) * PAIR_SLOTS * 4) + pad256(PAIR_STAGE * PAIR_SLOTS * 8) + 256;
+}
+
+void launch_careful_pairs(int n, int m_max, int d, const double* A, const double* b, const int* mrows, double inflate,
+                          double thresh, unsigned char* adj, long long p_lo, long long p_hi, unsigned char* compact,
+                          int cross_n1, void* scratch, hipStream_t st) {
+    if (p_hi <= p_lo) return;
+    const size_t nd = careful_doubles_per_lp(MAX_M) * PAIR_SLOTS;
+    char* p = static_cast<char*>(scratch) + 256;
+    double* hi = reinterpret_cast<double*>(p);
+    p += pad256(nd * 8);
+    double* lo = reinterpret_cast<double*>(p);
+    p += pad256(nd * 8);
+    int* rowinfo = reinterpret_cast<int*>(p);
+    p += pad256((size_t)(MAX_M + 2) * PAIR_SLOTS * 4);
+    double* stage = reinterpret_cast<double*>(p);
+    long long blocks = (p_hi - p_lo + VBLK - 1) / VBLK;
+    if (blocks > PAIR_SLOTS / VBLK) blocks = PAIR_SLOTS / VBLK;
+    hipLaunchKernelGGL(careful_pairs_kernel, dim3((unsigned)blocks), dim3(VBLK), 0, st, n, m_max, d, A, b, mrows, inflate, thresh,
+                       adj, p_lo, p_hi, compact, cross_n1, hi, lo, rowinfo, stage);
+}
 
 // ---- the same for LPs of N <= 5 columns (d <= 4: most of what the library is asked): ONE LP PER LANE, the column count a
 // compile-time constant, the certificate's arrays in registers (Cert<N, 1, N>: static indices only) -- no LDS, no

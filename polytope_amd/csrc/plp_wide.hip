@@ -167,7 +167,7 @@ __global__ __launch_bounds__(64) void adjacent_w_kernel(int n, int m_max, const 
                                                         const double* __restrict__ b, const int* __restrict__ mrows,
                                                         double inflate, double thresh, unsigned char* __restrict__ adj,
                                                         long long p_lo, long long p_hi, unsigned char* __restrict__ compact,
-                                                        int cross_n1) {
+                                                        int cross_n1, int mark) {
     constexpr int NC = D + 1;
     __shared__ WideShared<NC> sh;
     const int lane = threadIdx.x;
@@ -226,12 +226,14 @@ __global__ __launch_bounds__(64) void adjacent_w_kernel(int n, int m_max, const 
     const uint64_t ob = __ballot(rowvar == D);
     const double r = ob ? uniform_lane(mine, __ffsll((long long)ob) - 1) : 0.0;
     const bool yes = (st == ST_OPT) & (r > thresh);
+    // (mark: "unbounded" / the iteration limit is not a verdict -- the careful pass that follows decides, plp_kernels.hpp)
+    const unsigned char verdict = yes ? 1 : ((mark != 0) & ((st == ST_UNBND) | (st == ST_ITER)) ? PAIR_OPEN : 0);
     if (lane == 0) {
         if (compact) {
-            compact[p - p_lo] = yes ? 1 : 0;
+            compact[p - p_lo] = verdict;
         } else {
-            adj[i * n + j] = yes ? 1 : 0;
-            adj[j * n + i] = yes ? 1 : 0;
+            adj[i * n + j] = verdict;
+            adj[j * n + i] = verdict;
         }
     }
 }
@@ -240,7 +242,7 @@ __global__ __launch_bounds__(64) void adjacent_w_kernel(int n, int m_max, const 
 int launch_adjacent_w(int d, const LpLaunch& L, const PairArgs& a, hipStream_t st) {
     return for_dim<5, MAX_D>(d, [&](auto K) {
         hipLaunchKernelGGL((adjacent_w_kernel<decltype(K)::value>), dim3((unsigned)L.grid), dim3(L.block), L.lds, st, a.n, a.m_max,
-                           a.A, a.b, a.mrows, a.inflate, a.thresh, a.adj, a.p_lo, a.p_hi, a.compact, a.cross_n1);
+                           a.A, a.b, a.mrows, a.inflate, a.thresh, a.adj, a.p_lo, a.p_hi, a.compact, a.cross_n1, a.mark);
     });
 }
 

@@ -6,7 +6,12 @@ runs every case of the table with at most MAX_MEMBERS members on the device-poin
 another, with PLP_VERIFY=0 and the switches of the case in the environment, and the library's selftest kernel between them.
 The trace is then cut at the selftest kernels and written as {"cases": {case id: [[kernel, workgroups, threads per workgroup,
 LDS bytes], ...]}} -- kernel names as scripts/debug/trace_summary.py shortens them.  Only public entry points are used, so
-the same file runs on a tree from before the plan (profiles/lp_plan_trace_before.json) and after it (..._after.json)."""
+the same file runs on a tree from before the plan (profiles/lp_plan_trace_before.json) and after it (..._after.json).
+
+  python scripts/trace_lp_plan.py --instances OUT.json
+The same for the table of tests/instance_cases.py (one case per kernel instance of the fused reduce and of the four calls
+above, profiles/kernel_instances.json): every case's batch through the Python calls on CUDA tensors under the case's switches
+-> profiles/kernel_instances_trace.json, which tests/test_kernel_instances_host.py compares with the table."""
 import csv
 import glob
 import json
@@ -22,14 +27,57 @@ LIMIT_S = 420
 SEPARATOR = "selftest_kernel"
 
 
+INSTANCES = "--instances" in sys.argv
+
+
 def runnable():
     """The cases the C ABI can pose, small enough to run (the matrix form of the pair calls has no cross pairs)."""
+    if INSTANCES:
+        import instance_cases as ic
+        return [(ic.case_id(c), c) for c in ic.CASES]
     from test_lp_plan import CASES, case_id
     return [(case_id(c), c) for c, _ in CASES if (c[1][0] if c[0] != "pairs" else c[1][0] ** 2 // 2) <= MAX_MEMBERS
             and not (c[0] == "pairs" and c[1][6] and not c[1][5])]
 
 
+def instance_worker():
+    """One call per case of tests/instance_cases.py: CASES (the pair cases: the adjacency matrix), the selftest kernel between."""
+    os.environ["PLP_VERIFY"] = "0"
+    import numpy as np
+    import torch
+    import instance_cases as ic
+    import polytope_amd as pa
+    from polytope_amd import _lib
+    lib, ctx = _lib.load(), _lib.context(0)
+    sep_d, sep_u = np.zeros(128), np.zeros(128, np.uint32)
+    for cid, case in runnable():
+        assert lib.plp_selftest(ctx.handle, 8, sep_d.ctypes.data, sep_u.ctypes.data) == 0
+        call, switches = case[0], case[4]
+        mem = ic.members(case)
+        A, b, m = (torch.as_tensor(np.ascontiguousarray(mem[k])).to("cuda:0") for k in ("A", "b", "m"))
+        os.environ.update(switches)
+        try:
+            if call == "reduce":
+                pa.reduce_batch(A, b, m)
+            elif call == "cheby":
+                pa.cheby_ball_batch(A, b, m=m)
+            elif call == "bbox":
+                pa.bbox_batch(A, b, m)
+            elif call == "lp":
+                pa.lpsolve_batch(torch.as_tensor(mem["c"]).to("cuda:0"), A, b, m)
+            else:
+                pa.adjacent_pairs(A, b, m)
+            torch.cuda.synchronize()
+        finally:
+            for key in switches:
+                del os.environ[key]
+        print("case %s" % cid, flush=True)
+    assert lib.plp_selftest(ctx.handle, 8, sep_d.ctypes.data, sep_u.ctypes.data) == 0
+
+
 def worker():
+    if INSTANCES:
+        return instance_worker()
     os.environ["PLP_VERIFY"] = "0"
     import ctypes as C
     import numpy as np
@@ -119,12 +167,12 @@ def reduce_trace(directory):
 
 
 def main():
-    if sys.argv[1:] == ["--worker"]:
+    if "--worker" in sys.argv[1:]:
         return worker()
-    out = sys.argv[1]
+    out = [a for a in sys.argv[1:] if not a.startswith("--")][0]
     with tempfile.TemporaryDirectory() as tmp:
         cmd = ["timeout", "-k", "10", str(LIMIT_S), "rocprofv3", "--kernel-trace", "--output-format", "csv", "-d", tmp, "-o", "lp_plan",
-               "--", sys.executable, os.path.abspath(__file__), "--worker"]
+               "--", sys.executable, os.path.abspath(__file__), "--worker"] + (["--instances"] if INSTANCES else [])
         log = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
         if log.returncode:
             sys.stdout.write(log.stdout[-4000:])

@@ -28,6 +28,18 @@ def pa():
     return pa
 
 
+from test_reduce_plan import plan as reduce_plan, planned_kernels  # noqa: E402,F401 (reduce_plan: a fixture, the compiled plan)
+
+
+@pytest.fixture(scope="module")
+def reduce_kernels(reduce_plan):  # noqa: F811
+    """The kernels a fused reduce of (B, m_max, d) launches under PLP_REDUCE_* switches, in order, by the plan the library
+    carries out (polytope_amd/csrc/plp_reduce_plan.hpp, compiled for the host by tests/test_reduce_plan.py)."""
+    def ask(B, m_max, d, env):
+        return planned_kernels(reduce_plan, B, m_max, d, {k[len("PLP_REDUCE_"):]: str(v) for k, v in env.items()})
+    return ask
+
+
 # ------------------------------------------------------------------------------ primitives
 @pytest.mark.parametrize("gs", [8, 16, 32, 64])
 def test_group_primitives(pa, gs):
@@ -877,19 +889,46 @@ def test_reduce_degenerate_vertices(pa, oracle):
             assert abs(res["r"][k] - o["r"]) <= TOL and int(res["nlp"][k]) == o["nlp"]
 
 
+def _two_rows_family(variant, m, d):
+    """What each variant of test_reduce_two_rows_per_lane runs first at (m rows, d = 9..16), batches of a few tens."""
+    if variant == "PLP_REDUCE_LAZY=0,PLP_REDUCE_SPLIT=0":
+        return "reduce_r_kernel<%d, %d, 2>" % (d, 16 if m <= 32 else 32)      # two rows per lane, the batch form
+    if variant == "PLP_REDUCE_LAZY=0" or (variant == "PLP_REDUCE_R1=1" and m <= 32):
+        return "reduce_split_kernel<%d, %d, 2>" % (d, 16 if m <= 32 else 32)  # ... its latency form (small batches)
+    if variant == "PLP_REDUCE_R1=1":
+        return "reduce_r_kernel<%d, 64, 1>" % d                               # the one-row-per-lane twin (more than 32 rows)
+    if variant == "PLP_REDUCE_R2=0":
+        return "reduce_kernel<%d>" % d                                        # the general kernel alone
+    if variant == "PLP_REDUCE_LAZY=1,PLP_REDUCE_WSPLIT=0":                    # one polytope per wavefront: dense LPs up to d = 13,
+        return ("reduce_wdense_kernel<%d>" if d <= 13 else "reduce_lazy_kernel<%d>") % d   # without a stored dictionary beyond
+    # no switch, PLP_REDUCE_RETRY_ALL, PLP_REDUCE_LAZY=1: a small batch, one polytope per workgroup of four wavefronts
+    return "reduce_wsplit_kernel<%d, 4, %s>" % (d, "true" if d <= 13 else "false")
+
+
 @pytest.mark.parametrize("variant", [None, "PLP_REDUCE_RETRY_ALL", "PLP_REDUCE_R2=0", "PLP_REDUCE_LAZY=0", "PLP_REDUCE_LAZY=1",
-                                     "PLP_REDUCE_R1=1"])
-def test_reduce_two_rows_per_lane(pa, oracle, variant, monkeypatch):
-    """d = 9..16: the fused reduce on two rows per lane (groups of 16 / 32 lanes; PLP_REDUCE_LAZY=0: also beyond 32 rows),
-    on the kernel without a stored dictionary (default beyond 32 rows; PLP_REDUCE_LAZY=1: always), its one-row-per-lane
-    arithmetic twin (PLP_REDUCE_R1), the hand-over to the general engine, and the one-row-per-lane kernel of round 1 --
-    random, degenerate and ragged polytopes vs the oracle."""
+                                     "PLP_REDUCE_R1=1", "PLP_REDUCE_LAZY=0,PLP_REDUCE_SPLIT=0",
+                                     "PLP_REDUCE_LAZY=1,PLP_REDUCE_WSPLIT=0"])
+def test_reduce_two_rows_per_lane(pa, oracle, reduce_kernels, variant, monkeypatch):
+    """d = 9..16, random, degenerate and ragged polytopes vs the oracle on every engine of the fused reduce for these
+    dimensions; which kernel a variant runs is asserted through the plan (_two_rows_family):
+      PLP_REDUCE_LAZY=0,PLP_REDUCE_SPLIT=0   two rows per lane, groups of 16 / 32 lanes (reduce_r_kernel<D, 16 | 32, 2>: the
+                                             default for up to 32 rows beyond PLP_REDUCE_WG_MAXB polytopes)
+      PLP_REDUCE_LAZY=0                      its latency form (reduce_split_kernel<D, 16 | 32, 2>)
+      PLP_REDUCE_R1=1                        the one-row-per-lane arithmetic twin beyond 32 rows (reduce_r_kernel<D, 64, 1>)
+      PLP_REDUCE_LAZY=1,PLP_REDUCE_WSPLIT=0  one polytope per wavefront, with a stored dictionary up to d = 13 and without beyond
+      none, PLP_REDUCE_LAZY=1                one polytope per workgroup of four wavefronts (reduce_wsplit_kernel: what batches
+                                             this small get by default)
+      PLP_REDUCE_RETRY_ALL                   the hand-over of every polytope to the general engine
+      PLP_REDUCE_R2=0                        the one-row-per-lane kernel of round 1 alone."""
     from polytope_amd.synth import random_hpolytopes
-    if variant:
-        name, _, val = variant.partition("=")
+    env = {}
+    for part in (variant.split(",") if variant else ()):
+        name, _, val = part.partition("=")
+        env[name] = val or "1"
         monkeypatch.setenv(name, val or "1")
     rng = np.random.default_rng(77)
     for (m, d, B) in [(30, 9, 24), (32, 12, 20), (64, 13, 10), (50, 16, 10), (18, 10, 30), (64, 16, 8)]:
+        assert reduce_kernels(B, m, d, env)[0] == _two_rows_family(variant, m, d), (variant, m, d, reduce_kernels(B, m, d, env))
         A, b = random_hpolytopes(B, m, d, seed=3 * m + d, bounded=True)
         for k in range(0, B, 4):
             j = rng.integers(m)
@@ -1181,23 +1220,33 @@ def test_contains_vs_oracle(pa, oracle):
     assert np.array_equal(pa.contains_batch(A, b, X, abs_tol=1e-7, region=False), o)
 
 
-def test_reduce_latency_form_bitwise(pa, monkeypatch):
+def test_reduce_latency_form_bitwise(pa, reduce_kernels, monkeypatch):
     """Small batches take the latency form of the fused reduce (reduce_split_kernel: one polytope per wavefront, every
     lane group runs F1 / dedupe on the same rows, then the 2d box LPs and the redundancy LPs are spread over the groups;
     the in-place h[k] +- 0.1 round trip becomes a rule).  Same engine per LP: every output bitwise equal to the batch
-    form -- d = 1..16, 3..64 rows, ragged, duplicated and infeasible rows, pyramids, golden fixture g2, batch sizes
-    around the switch-over."""
+    form (reduce_r_kernel) -- d = 1..16, 3..64 rows, ragged, duplicated and infeasible rows, pyramids, golden fixture g2,
+    batch sizes around the switch-over.  With more than 32 rows, and from d = 9 on, both forms run only under
+    PLP_REDUCE_LAZY=0 (the default there is one polytope per wavefront or workgroup, whatever PLP_REDUCE_SPLIT says); that
+    the two arms are the two kernels is asserted through the plan for every batch."""
     from polytope_amd.synth import random_hpolytopes
     rng = np.random.default_rng(9)
 
     def both(A, b, m=None):
+        B, m_max, d = A.shape
+        common = {"PLP_REDUCE_HALF": "0"}   # (the batch form on full tiles: the same rows per lane as the latency form)
+        if m_max > 32 or d >= 9:
+            common["PLP_REDUCE_LAZY"] = "0"
+        arms = [reduce_kernels(B, m_max, d, dict(common, PLP_REDUCE_SPLIT=v))[0] for v in ("0", "1")]
+        assert arms[0].startswith("reduce_r_kernel<") and arms[1].startswith("reduce_split_kernel<"), (B, m_max, d, arms)
+        for k, v in common.items():
+            monkeypatch.setenv(k, v)
         monkeypatch.setenv("PLP_REDUCE_SPLIT", "0")
-        monkeypatch.setenv("PLP_REDUCE_HALF", "0")   # (the batch form on full tiles: the same rows per lane as the latency form)
         batch = pa.reduce_batch(A, b, m=m)
         monkeypatch.setenv("PLP_REDUCE_SPLIT", "1")
         lat = pa.reduce_batch(A, b, m=m)
         monkeypatch.delenv("PLP_REDUCE_SPLIT")
-        monkeypatch.delenv("PLP_REDUCE_HALF")
+        for k in common:
+            monkeypatch.delenv(k)
         for key in batch:
             assert np.array_equal(batch[key].view(np.uint8), lat[key].view(np.uint8)), key
         return lat
@@ -1255,27 +1304,46 @@ def test_reduce_latency_form_bitwise(pa, monkeypatch):
                 assert np.array_equal(ref[key].view(np.uint8), got[key].view(np.uint8)), (B, key)
 
 
-def test_reduce_without_stored_dictionary_bitwise(pa, oracle, monkeypatch):
+def test_reduce_without_stored_dictionary_bitwise(pa, oracle, reduce_kernels, monkeypatch):
     """reduce_lazy_kernel (plp_lazy.hpp) evaluates the entering column and the leaving row of every F2 / F3 pivot from
     the polytope's rows and the pivots so far with the operations, in the order, the dense engine applies to its stored
     dictionary: every output must be bit-identical to the one-row-per-lane instance of that engine, and to the
     two-rows-per-lane kernel in everything but the last bit of a Chebyshev centre -- ragged, duplicated, infeasible rows; pyramids (degenerate vertices: Bland hand-over); shapes whose LPs run past
     the four pivots kept in registers into the private-array steps; a sample against the oracle.  reduce_wdense_kernel (the
     same kernel with the F3 / F2 LPs on the dense one-LP-per-wavefront engine, wide::solve_dense -- the default for more
-    than 32 rows up to d = 13) must agree with it in every bit as well, d = 5..16, Bland's rule inside the LP included."""
+    than 32 rows up to d = 13) must agree with it in every bit as well, d = 5..16, Bland's rule inside the LP included.
+    The four arms' kernels are asserted through the plan.  Both one-polytope-per-wavefront arms carry PLP_REDUCE_WSPLIT=0:
+    without it batches this small run reduce_wsplit_kernel in one of them (kept at two shapes, the same comparison)."""
     from polytope_amd.synth import random_hpolytopes
     rng = np.random.default_rng(5)
 
-    def four(A, b, m=None):
+    def four(A, b, m=None, wsplit="0"):
+        """wsplit "0": the two one-polytope-per-wavefront arms with PLP_REDUCE_WSPLIT=0, so that they are reduce_lazy_kernel and
+        reduce_wdense_kernel at every d and batch size; None: the switch unset, where the arm whose engine matches the
+        dimension's default runs on reduce_wsplit_kernel instead"""
+        B, m_max, d = A.shape
+        wave = {} if wsplit is None else {"PLP_REDUCE_WSPLIT": wsplit}
+        envs = ({"PLP_REDUCE_LAZY": "0"}, {"PLP_REDUCE_LAZY": "0", "PLP_REDUCE_R1": "1"},
+                dict(wave, PLP_REDUCE_LAZY="1", PLP_REDUCE_WDENSE="0"), dict(wave, PLP_REDUCE_LAZY="1", PLP_REDUCE_WDENSE="1"))
+        names = [reduce_kernels(B, m_max, d, env)[0] for env in envs]
+        rows2 = "reduce_%%s_kernel<%d, %d, %d>" % ((d, 16 if m_max <= 32 else 32, 2) if d > 8 else
+                                                   (d, 4 if m_max <= 16 else 8 if m_max <= 32 else 16, 4))
+        assert names[0] in (rows2 % "r", rows2 % "split") or (d <= 8 and names[0].startswith("reduce_r_kernel<%d, " % d)), names
+        assert names[1] == ("reduce_r_kernel<%d, 64, 1>" % d if d > 8 and m_max > 32 else names[0]), names
+        if wsplit == "0":
+            assert names[2:] == ["reduce_lazy_kernel<%d>" % d, "reduce_wdense_kernel<%d>" % d], names
+        else:
+            assert sorted(n.split("<")[0] for n in names[2:]) == \
+                ["reduce_lazy_kernel" if d <= 13 else "reduce_wdense_kernel", "reduce_wsplit_kernel"], names
         out = []
-        for env in ({"PLP_REDUCE_LAZY": "0"}, {"PLP_REDUCE_LAZY": "0", "PLP_REDUCE_R1": "1"},
-                    {"PLP_REDUCE_LAZY": "1", "PLP_REDUCE_WDENSE": "0"}, {"PLP_REDUCE_LAZY": "1", "PLP_REDUCE_WDENSE": "1"}):
-            for k in ("PLP_REDUCE_LAZY", "PLP_REDUCE_R1", "PLP_REDUCE_WDENSE"):
+        switches = ("PLP_REDUCE_LAZY", "PLP_REDUCE_R1", "PLP_REDUCE_WDENSE", "PLP_REDUCE_WSPLIT")
+        for env in envs:
+            for k in switches:
                 monkeypatch.delenv(k, raising=False)
             for k, v in env.items():
                 monkeypatch.setenv(k, v)
             out.append(pa.reduce_batch(A, b, m=m))
-        for k in ("PLP_REDUCE_LAZY", "PLP_REDUCE_R1", "PLP_REDUCE_WDENSE"):
+        for k in switches:
             monkeypatch.delenv(k, raising=False)
         return out
 
@@ -1304,6 +1372,8 @@ def test_reduce_without_stored_dictionary_bitwise(pa, oracle, monkeypatch):
             b[k, 0] = -4.0
         rows = rng.integers(max(d + 2, m - 9), m + 1, B).astype(np.int32)
         for mr in (None, rows):
+            if (B, m, d) in ((600, 64, 12), (400, 36, 14)):   # the switch unset: reduce_wsplit_kernel, dense / not, in one arm
+                compare(*four(A, b, mr, wsplit=None), d, (B, m, d, "wsplit"))
             dense, one_row, lazy, wdense = four(A, b, mr)
             compare(dense, one_row, lazy, wdense, d, (B, m, d))
         masks = pa.keep_to_bool(wdense["keep"], m)

@@ -238,6 +238,7 @@ def plan(tmp_path_factory):
         for L in launches:
             L["engine"] = ENGINES[L["engine"]]
         return launches, tuple(o[1:4])
+    run.lib = lib   # (lp_plan_thresholds, lp_plan_sweep: tests/instance_cases.py)
     return run
 
 

@@ -80,6 +80,31 @@ CASES = [
 ]
 
 
+def kernel_name(d, L):
+    """The kernel a planned launch stands for, as a trace names it (the templates of plp_reduce_launch.hpp).  L: a dict with
+    engine (its name), gs, rows, nw."""
+    e = L["engine"]
+    if e == "GENERAL":
+        return "reduce_kernel<%d>" % d
+    if e == "LANE":
+        return "reduce_lane_kernel<%d, %d, %d>" % (d, L["gs"], L["rows"])
+    if e == "LANE_MIX":
+        return "reduce_lane_mix_kernel<%d, %d, %d, %d>" % (d, L["rows"], L["gs"], 2 * L["gs"])
+    if e in ("GROUP", "SPLIT"):
+        return "reduce_%s_kernel<%d, %d, %d>" % ("r" if e == "GROUP" else "split", d, L["gs"], L["rows"])
+    if e == "WSPLIT":   # (with the dense LPs up to PLP_REDUCE_WDENSE_MAXD and without beyond: the plan's `dense` says which)
+        return "reduce_wsplit_kernel<%d, %d, %s>" % (d, L["nw"], "true" if L["dense"] else "false")
+    return {"GROUP_MIX": "reduce_r_mix_kernel<%d>", "WDENSE": "reduce_wdense_kernel<%d>", "LAZY": "reduce_lazy_kernel<%d>"}[e] % d
+
+
+def planned_kernels(plan, B, m, d, env):
+    """The kernels of a call in launch order: the first launch, then reduce_kernel<D> where the second pass follows."""
+    got = dict(zip(FIELDS, plan(B, m, d, env)))
+    if got["engine"] == "NONE":
+        return None
+    return [kernel_name(d, got)] + (["reduce_kernel<%d>" % d] if got["second"] else [])
+
+
 @pytest.fixture(scope="module")
 def plan(tmp_path_factory):
     out = str(tmp_path_factory.mktemp("plan") / "libreduce_plan.so")
@@ -95,7 +120,18 @@ def plan(tmp_path_factory):
         o = (C.c_longlong * len(FIELDS))()
         L.reduce_plan(B, m, d, arr, o)
         return (ENGINES[o[0]],) + tuple(o[1:])
+    run.lib = L   # (reduce_plan_thresholds, reduce_plan_sweep: tests/instance_cases.py)
     return run
+
+
+def test_kernel_names(plan):
+    assert planned_kernels(plan, 100000, 16, 3, {}) == ["reduce_lane_mix_kernel<3, 16, 4, 8>"]
+    assert planned_kernels(plan, 16001, 24, 3, {}) == ["reduce_lane_mix_kernel<3, 32, 8, 16>"]
+    assert planned_kernels(plan, 300, 32, 12, {"LAZY": "0", "SPLIT": "0"}) == ["reduce_r_kernel<12, 16, 2>", "reduce_kernel<12>"]
+    assert planned_kernels(plan, 300, 32, 9, {"LAZY": "1", "WSPLIT": "0"}) == ["reduce_wdense_kernel<9>"]
+    assert planned_kernels(plan, 3000, 48, 14, {}) == ["reduce_wsplit_kernel<14, 2, false>", "reduce_kernel<14>"]
+    assert planned_kernels(plan, 1000, 16, 9, {"WSPLIT": "2"}) == ["reduce_wsplit_kernel<9, 2, true>"]
+    assert planned_kernels(plan, 10, 65, 3, {}) is None
 
 
 @pytest.mark.parametrize("case,want", CASES, ids=["%d-%d-%d-%s" % (c[0][0], c[0][1], c[0][2], ",".join(
