@@ -18,7 +18,9 @@
 // a run of degenerate steps (cycling risk), active rows that are numerically dependent, the iteration cap.
 //
 // The same source compiles for the host (g++, tests/cabi/lane_lp_host.cpp: the engine against the oracle's simplex on
-// millions of LPs without a GPU) and for the device.
+// millions of LPs without a GPU) and for the device.  -DPLP_LANE_PLAIN_WALK: walk3 as one general loop behind its first
+// pass (A/B builds; tests/cabi/lane_walk_ab_host.cpp holds the default form, with its second and third pass peeled, to the
+// same bits).
 #pragma once
 #include <math.h>
 
@@ -98,6 +100,111 @@ PLP_LANE_FN void proj1(const double c0, const double c1, const double c2, const 
 // drift below 1e-10 of the step.  (The fused reduce removes rows closer than 4.5e-4 rad before any LP runs, ref :1094-1110.)
 constexpr double LANE_PAIR_SIN2 = 1e-10;
 
+// Where a walk ends, drops a row or which kind of pass it takes: a host build that wants to count them defines
+// PLP_LANE_TALLY(e) before it includes this header (tests/cabi/lane_walk_ab_host.cpp); everywhere else it is nothing.
+enum : int {
+    WE_OPT1 = 0, WE_OPT2, WE_OPT3,                       // ST_OPT with one, two, three active rows
+    WE_UNBND,                                            // a descent ray that no row stops
+    WE_RETRY_PAIR, WE_RETRY_TRIPLE, WE_RETRY_DEGEN,      // handed back: parallel pair, dependent triple, degenerate run / cap
+    WE_DROP2, WE_DROP3,                                  // a row dropped at an edge / at a vertex
+    WE_PASS_FACET, WE_PASS_EDGE, WE_PASS_GENERAL,        // passes by kind (the first one is not counted)
+    WE_COUNT
+};
+#ifndef PLP_LANE_TALLY
+#define PLP_LANE_TALLY(e) ((void)0)
+#endif
+
+// The step every pass ends with, for the lanes in `step`: to the row the ratio test found (bs / bd / bi), which becomes
+// active row number `slot` (S.nact before the step), or ST_UNBND where no row stops the ray.  CAPS: hand the LP back after a
+// run of degenerate steps or at the iteration cap (the passes that run second and third cannot reach either).
+template <bool CAPS>
+PLP_LANE_FN void step3(Lp3& S, const bool step, const double d0, const double d1, const double d2, const double dn1,
+                       const double bs, const double bd, const int bi, const int slot) {
+    static_assert(BLAND_AFTER > 3 && LANE_MAX_ITERS > 3, "passes 2 and 3 of a walk from the centre reach neither cap");
+    if (step) {
+        ++S.iters;
+        if (bi < 0) {
+            S.status = ST_UNBND;     // a descent ray that no row stops
+            PLP_LANE_TALLY(WE_UNBND);
+        } else {
+            const double t = bs / bd;
+            S.x0 = fma(t, d0, S.x0);
+            S.x1 = fma(t, d1, S.x1);
+            S.x2 = fma(t, d2, S.x2);
+            if (slot == 0) S.w0 = bi;
+            else if (slot == 1) S.w1 = bi;
+            else S.w2 = bi;
+            S.nact = slot + 1;
+            S.ndeg = (t * dn1 <= DEGEN_EPS) ? S.ndeg + 1 : 0;
+            if (CAPS && (S.ndeg >= BLAND_AFTER || S.iters >= LANE_MAX_ITERS)) {
+                S.status = ST_RETRY;
+                PLP_LANE_TALLY(WE_RETRY_DEGEN);
+            }
+        }
+    }
+}
+
+#ifndef PLP_LANE_PLAIN_WALK
+// The passes of an ordinary walk, each with the code of its own case only (the general pass of walk3 carries all four,
+// twice).  A lane performs in them exactly the arithmetic, in the same order, that the general pass performs for it; a
+// lane the pass is not for keeps its state and is picked up by the general pass.  Rows are read from clamped indices,
+// unconditionally and all before their first use (a read under a condition is a branch and an LDS round trip of its own).
+
+// Second pass of a walk from the centre: lanes that run with ONE active row, from the facet along the projected -c to an
+// edge.  A lane with no descent left on its facet (the stall test) sits it out.
+template <class RowF, class RatioF, class AnyF>
+PLP_LANE_FN void facet_pass3(Lp3& S, const double c0, const double c1, const double c2, const double cn1, RowF ROWS,
+                             RatioF RATIO, AnyF ANY) {
+    const bool on = S.status < 0 && S.nact == 1;
+    double n0, n1, n2;
+    ROWS(on ? S.w0 : 0, n0, n1, n2);
+    const double nn = dot3(n0, n1, n2, n0, n1, n2);
+    double d0, d1, d2, sc;
+    proj1(c0, c1, c2, cn1, n0, n1, n2, nn, d0, d1, d2, sc, ANY);
+    const double dn1 = fabs(d0) + fabs(d1) + fabs(d2);
+    const bool step = on && (dn1 > LANE_TOL_D * (sc * cn1));
+    if (ANY(step)) {
+        double bs = 1.0, bd = 0.0;
+        int bi = -1;
+        RATIO(d0, d1, d2, S.x0, S.x1, S.x2, LANE_TOL_PIV * dn1, bs, bd, bi);
+        if (step) PLP_LANE_TALLY(WE_PASS_FACET);
+        step3<false>(S, step, d0, d1, d2, dn1, bs, bd, bi, 1);
+    }
+}
+
+// Third pass: lanes that run with TWO active rows, along their edge to a vertex.  The pair test hands parallel rows back;
+// a lane with no descent left along its edge sits the pass out.
+template <class RowF, class RatioF, class AnyF>
+PLP_LANE_FN void edge_pass3(Lp3& S, const double c0, const double c1, const double c2, const double cn1, RowF ROWS,
+                            RatioF RATIO, AnyF ANY) {
+    const bool on = S.status < 0 && S.nact == 2;
+    double n00, n01, n02, n10, n11, n12;
+    ROWS(on ? S.w0 : 0, n00, n01, n02);
+    ROWS(on ? S.w1 : 0, n10, n11, n12);
+    double e0, e1, e2;
+    cross3(n00, n01, n02, n10, n11, n12, e0, e1, e2);
+    const double ce = dot3(c0, c1, c2, e0, e1, e2);
+    const double d0 = -(ce * e0), d1 = -(ce * e1), d2 = -(ce * e2);
+    const double ee = dot3(e0, e1, e2, e0, e1, e2);
+    const double nn0 = dot3(n00, n01, n02, n00, n01, n02), nn1 = dot3(n10, n11, n12, n10, n11, n12);
+    const bool edge = ee > LANE_PAIR_SIN2 * nn0 * nn1;
+    if (on && !edge) {
+        S.status = ST_RETRY;
+        PLP_LANE_TALLY(WE_RETRY_PAIR);
+        PLP_LANE_TALLY(WE_PASS_EDGE);
+    }
+    const double dn1 = fabs(d0) + fabs(d1) + fabs(d2);
+    const bool step = on && edge && (dn1 > LANE_TOL_D * (ee * cn1));
+    if (ANY(step)) {
+        double bs = 1.0, bd = 0.0;
+        int bi = -1;
+        RATIO(d0, d1, d2, S.x0, S.x1, S.x2, LANE_TOL_PIV * dn1, bs, bd, bi);
+        if (step) PLP_LANE_TALLY(WE_PASS_EDGE);
+        step3<false>(S, step, d0, d1, d2, dn1, bs, bd, bi, 2);
+    }
+}
+#endif   // !PLP_LANE_PLAIN_WALK
+
 // One LP, to the end.  ROWS(i, a0, a1, a2): row i of the polytope (zeroed rows allowed: they never block).
 // RATIO(d0, d1, d2, x0, x1, x2, tolp, bs, bd, bi): the ratio test -- over the rows with a.d > tolp the one with the smallest
 // (beta_i - a_i.x)+ / a_i.d, the FIRST such row on ties; bs / bd its slack and a.d, bi its index (-1: none).  The caller
@@ -135,6 +242,7 @@ PLP_LANE_FN void walk3(Lp3& S, const double c0, const double c1, const double c2
             S.iters = 1;
             if (bi < 0) {
                 S.status = ST_UNBND;
+                PLP_LANE_TALLY(WE_UNBND);
             } else {
                 const double t = bs / bd;
                 S.x0 = fma(t, d0, 0.0);
@@ -146,16 +254,30 @@ PLP_LANE_FN void walk3(Lp3& S, const double c0, const double c1, const double c2
             }
         }
     }
+#ifndef PLP_LANE_PLAIN_WALK
+    // ---------------- second and third pass, for the lanes on the ordinary track: facet -> edge -> vertex.  Finished and
+    // unbounded lanes, lanes stalled on a facet or an edge (boxes and prisms end there) and warm-started walks sit them out.
+    if (!warm && ANY(S.status < 0 && S.nact == 1)) facet_pass3(S, c0, c1, c2, cn1, ROWS, RATIO, ANY);
+    if (!warm && ANY(S.status < 0 && S.nact == 2)) edge_pass3(S, c0, c1, c2, cn1, ROWS, RATIO, ANY);
+#endif
     while (ANY(S.status < 0)) {
         const bool run = S.status < 0;
+        if (run) PLP_LANE_TALLY(WE_PASS_GENERAL);
         // ---------------- direction: -c projected onto the planes of the active rows (scaled by positive factors)
         double d0 = -c0, d1 = -c1, d2 = -c2;
         double n00 = 0, n01 = 0, n02 = 0, n10 = 0, n11 = 0, n12 = 0, n20 = 0, n21 = 0, n22 = 0;
+#ifdef PLP_LANE_PLAIN_WALK
         if (ANY(run && S.nact >= 1)) {
             if (S.nact >= 1) ROWS(S.w0, n00, n01, n02);
             if (S.nact >= 2) ROWS(S.w1, n10, n11, n12);
             if (S.nact >= 3) ROWS(S.w2, n20, n21, n22);
         }
+#else
+        // (all three slots at once, an inactive one reads row 0: its values are never used)
+        ROWS(S.nact >= 1 ? S.w0 : 0, n00, n01, n02);
+        ROWS(S.nact >= 2 ? S.w1 : 0, n10, n11, n12);
+        ROWS(S.nact >= 3 ? S.w2 : 0, n20, n21, n22);
+#endif
         bool stalled = false;      // no descent left inside the active planes: look at the multipliers
         double dscale = cn1;       // |d|_1 of a direction that is "as long as c" (what TOL_D is relative to)
         if (S.nact == 1) {
@@ -173,7 +295,10 @@ PLP_LANE_FN void walk3(Lp3& S, const double c0, const double c1, const double c2
             dscale = dot3(e0, e1, e2, e0, e1, e2) * cn1;
             // the two active rows (numerically) parallel: their planes do not define an edge
             const double nn0 = dot3(n00, n01, n02, n00, n01, n02), nn1 = dot3(n10, n11, n12, n10, n11, n12);
-            if (run && !(dot3(e0, e1, e2, e0, e1, e2) > LANE_PAIR_SIN2 * nn0 * nn1)) S.status = ST_RETRY;
+            if (run && !(dot3(e0, e1, e2, e0, e1, e2) > LANE_PAIR_SIN2 * nn0 * nn1)) {
+                S.status = ST_RETRY;
+                PLP_LANE_TALLY(WE_RETRY_PAIR);
+            }
         } else if (S.nact == 3) {
             d0 = d1 = d2 = 0.0;
         }
@@ -190,7 +315,7 @@ PLP_LANE_FN void walk3(Lp3& S, const double c0, const double c1, const double c2
                     S.status = ST_OPT;   // (c ~ 0 relative to itself cannot happen; kept for completeness)
                 } else if (S.nact == 1) {
                     const double cn = dot3(c0, c1, c2, n00, n01, n02);
-                    if (cn <= 0.0) S.status = ST_OPT;           // lambda = -c.n / n.n >= 0
+                    if (cn <= 0.0) { S.status = ST_OPT; PLP_LANE_TALLY(WE_OPT1); }   // lambda = -c.n / n.n >= 0
                     else { S.nact = 0; d0 = -c0; d1 = -c1; d2 = -c2; }   // (leaves the row; cannot follow a step onto it)
                 } else if (S.nact == 2) {
                     const double g00 = dot3(n00, n01, n02, n00, n01, n02), g11 = dot3(n10, n11, n12, n10, n11, n12);
@@ -202,8 +327,9 @@ PLP_LANE_FN void walk3(Lp3& S, const double c0, const double c1, const double c2
                     // equal for unit rows, a little stricter otherwise) and det <= g00 g11
                     const double w0 = 0.5 * (1.0 + g00), w1 = 0.5 * (1.0 + g11);
                     const double tol0 = LANE_TOL_D * g11 * w0 * cn1, tol1 = LANE_TOL_D * g00 * w1 * cn1;
-                    if (l0 >= -tol0 && l1 >= -tol1) S.status = ST_OPT;
+                    if (l0 >= -tol0 && l1 >= -tol1) { S.status = ST_OPT; PLP_LANE_TALLY(WE_OPT2); }
                     else {
+                        PLP_LANE_TALLY(WE_DROP2);
                         // drop the more negative one (as weighted multipliers; a row with a negative one either way)
                         const bool drop0 = l0 * w0 < l1 * w1;
                         if (drop0) { S.w0 = S.w1; n00 = n10; n01 = n11; n02 = n12; }
@@ -221,6 +347,7 @@ PLP_LANE_FN void walk3(Lp3& S, const double c0, const double c1, const double c2
                     const double g22 = dot3(n20, n21, n22, n20, n21, n22);
                     if (!(det * det > 1e-18 * (g00 * g11 * g22))) {
                         S.status = ST_RETRY;   // three active planes that (nearly) share a line
+                        PLP_LANE_TALLY(WE_RETRY_TRIPLE);
                     } else {
                         // lambda_j = -(c.u_j) / det ; compare sign-corrected numerators lambda_j |det| = -(c.u_j) sgn(det)
                         const double sg = det > 0.0 ? 1.0 : -1.0;
@@ -230,8 +357,9 @@ PLP_LANE_FN void walk3(Lp3& S, const double c0, const double c1, const double c2
                         // lambda_j |n_j| / |c|  =  l_j |n_j| / (|det| |c|), with w_j = (1 + n_j.n_j) / 2 >= |n_j| in its place
                         const double a0 = l0 * (0.5 * (1.0 + g00)), a1 = l1 * (0.5 * (1.0 + g11)), a2 = l2 * (0.5 * (1.0 + g22));
                         const double tol = LANE_TOL_D * fabs(det) * cn1;
-                        if (a0 >= -tol && a1 >= -tol && a2 >= -tol) S.status = ST_OPT;
+                        if (a0 >= -tol && a1 >= -tol && a2 >= -tol) { S.status = ST_OPT; PLP_LANE_TALLY(WE_OPT3); }
                         else {
+                            PLP_LANE_TALLY(WE_DROP3);
                             // most negative goes; the edge of the other two, oriented off the dropped row: -sgn(det) u_j
                             int j = 0;
                             double am = a0;
@@ -242,7 +370,10 @@ PLP_LANE_FN void walk3(Lp3& S, const double c0, const double c1, const double c2
                             else if (j == 1) { d0 = -sg * u10; d1 = -sg * u11; d2 = -sg * u12; S.w1 = S.w2; gg = g22 * g00; }
                             else { d0 = -sg * u20; d1 = -sg * u21; d2 = -sg * u22; gg = g00 * g11; }
                             S.nact = 2;
-                            if (!(dot3(d0, d1, d2, d0, d1, d2) > LANE_PAIR_SIN2 * gg)) S.status = ST_RETRY;
+                            if (!(dot3(d0, d1, d2, d0, d1, d2) > LANE_PAIR_SIN2 * gg)) {
+                                S.status = ST_RETRY;
+                                PLP_LANE_TALLY(WE_RETRY_PAIR);
+                            }
                         }
                     }
                 }
@@ -255,23 +386,7 @@ PLP_LANE_FN void walk3(Lp3& S, const double c0, const double c1, const double c2
         double bs = 1.0, bd = 0.0;   // best slack / best a.d  (ratio bs / bd; bd = 0: none yet)
         int bi = -1;
         if (ANY(step)) RATIO(d0, d1, d2, S.x0, S.x1, S.x2, tolp, bs, bd, bi);
-        if (step) {
-            ++S.iters;
-            if (bi < 0) {
-                S.status = ST_UNBND;     // a descent ray that no row stops
-            } else {
-                const double t = bs / bd;
-                S.x0 = fma(t, d0, S.x0);
-                S.x1 = fma(t, d1, S.x1);
-                S.x2 = fma(t, d2, S.x2);
-                if (S.nact == 0) S.w0 = bi;
-                else if (S.nact == 1) S.w1 = bi;
-                else S.w2 = bi;
-                S.nact += 1;
-                S.ndeg = (t * dn1 <= DEGEN_EPS) ? S.ndeg + 1 : 0;
-                if (S.ndeg >= BLAND_AFTER || S.iters >= LANE_MAX_ITERS) S.status = ST_RETRY;
-            }
-        }
+        step3<true>(S, step, d0, d1, d2, dn1, bs, bd, bi, S.nact);
     }
 }
 
