@@ -563,6 +563,49 @@ int plp_rdiff_result_sizes(const plp_rdiff_result *r, int64_t *n_leaves, int64_t
 int plp_rdiff_result_copy(const plp_rdiff_result *r, int32_t *kind, int32_t *off, int32_t *rows);
 int plp_rdiff_result_free(plp_rdiff_result *r);
 
+/*
+ * B set differences in one launch: problem p is the minuend A[p] (m[p] rows) minus the cells cell_idx[cell_off[p] ..
+ * cell_off[p + 1]), in that order, of the shared packed cell table CA[Nc][mc_max][d], Cb[Nc][mc_max], mc[Nc] (NULL =
+ * mc_max).  All rows are unit length already (Polytope.__init__, :130-138) and the cells are sorted as region_diff sorts
+ * them (:2153-2157).  One wavefront builds the table of its problem (region_diff :2166-2183: a cell row is new when
+ * sum_k |row_c[k] - row_p[k]| over (a, b) is >= abs_tol for every minuend row p) and runs the whole search of
+ * plp_region_diff_search on it, one Chebyshev LP per radius it reads; no host round trip.
+ * Caps per problem: d <= 4, m <= 64, at most 64 cells of at most 64 rows, m + 2M <= 256 table rows, lists of <= 64 rows.
+ * Out, per problem: the pieces in the reference's order as lists of LOCAL table rows (0 .. m - 1 the minuend's, m + k new
+ *      row k, m + M + k its negation): kind[B][p_max] (0 = as is, 1 = to be reduce()d), off[B][p_max + 1],
+ *      rows[B][r_max]; count[B] / nrows[B] pieces and rows produced; nlp[B] LPs run; mi[B][n_max] new rows per cell;
+ *      src[B][M_max] the cell-table row c * mc_max + r of new row k; status[B]:
+ *        PLP_RD_OK;
+ *        PLP_RD_OVERFLOW     more than p_max pieces or r_max rows: count / nrows hold what is needed, what fits is written;
+ *        PLP_RD_COVERED      a listed cell has no new row: the difference is empty, count 0;
+ *        PLP_RD_LONG         a list of more than 64 rows;
+ *        PLP_RD_BUDGET       max_lps LPs did not finish the search;
+ *        PLP_RD_INDEX        the reference raises IndexError here (its index arithmetic on INDICES left the table);
+ *        PLP_RD_UNSUPPORTED  a cap on m / the cells / M, or a cell index outside the table: nothing is run.
+ * cell_off[B + 1] must be non-decreasing from cell_off[0] >= 0, and cell_idx must hold cell_off[B] entries: the host-pointer
+ * form returns PLP_EINVAL otherwise; the _dev form cannot see the arrays, ends a problem whose own two entries are negative
+ * or decreasing as PLP_RD_UNSUPPORTED, and relies on the caller for the length of cell_idx.
+ * B = 0: returns PLP_OK, nothing runs.  d > 4: PLP_EUNSUPPORTED.
+ */
+#define PLP_RD_OK 0
+#define PLP_RD_OVERFLOW 1
+#define PLP_RD_COVERED 2
+#define PLP_RD_LONG 3
+#define PLP_RD_BUDGET 4
+#define PLP_RD_INDEX 5
+#define PLP_RD_UNSUPPORTED 6
+int plp_region_diff_batch(plp_ctx *ctx, int64_t B, int m_max, int d, const double *A, const double *b, const int32_t *m,
+                          int64_t Nc, int mc_max, const double *CA, const double *Cb, const int32_t *mc,
+                          const int32_t *cell_off, const int32_t *cell_idx, double abs_tol, int max_lps, int p_max, int r_max,
+                          int n_max, int M_max, int32_t *kind, int32_t *off, int32_t *rows, int32_t *count, int32_t *nrows,
+                          int32_t *nlp, int32_t *status, int32_t *mi, int32_t *src);
+int plp_region_diff_batch_dev(plp_ctx *ctx, void *stream, int64_t B, int m_max, int d, const double *A, const double *b,
+                              const int32_t *m, int64_t Nc, int mc_max, const double *CA, const double *Cb,
+                              const int32_t *mc, const int32_t *cell_off, const int32_t *cell_idx, double abs_tol,
+                              int max_lps, int p_max, int r_max, int n_max, int M_max, int32_t *kind, int32_t *off,
+                              int32_t *rows, int32_t *count, int32_t *nrows, int32_t *nlp, int32_t *status, int32_t *mi,
+                              int32_t *src);
+
 /* cross-lane primitive self-test (group size 8/16/32/64); host out_d[128], out_u[128] */
 int plp_selftest(plp_ctx *ctx, int group_size, double *out_d, uint32_t *out_u);
 

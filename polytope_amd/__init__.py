@@ -36,5 +36,6 @@ from .batch import (  # noqa: F401
     verify_careful_lps, lp_histograms, projection_batch, volume_batch, support_batch, subset_batch, extreme_batch, hull_batch,
     volume_exact_batch, locate_batch, locate_grid,
 )
+from .polytope import region_diff_batch  # noqa: F401,E402  (the Polytope-level call; the packed one is batch.region_diff_batch)
 
 __version__ = "0.1.0"

@@ -1204,6 +1204,242 @@ def region_diff_search(A, b, m, mi, abs_tol=1e-7):
     return pieces, dict(lps=int(nlp.value), batches=int(nb.value))
 
 
+# ------------------------------------------------------------------ region_diff, many searches in one launch
+RD_OK, RD_OVERFLOW, RD_COVERED, RD_LONG, RD_BUDGET, RD_INDEX, RD_UNSUPPORTED = range(7)   # include/plp.h: PLP_RD_*
+RD_MAX_CELLS, RD_MAX_NEW = 64, 127   # the widths of mi[B, .] and src[B, .]: the kernel's caps on N and M
+_RD_P_MAX, _RD_R_MAX = 32, 1024      # what the first launch has room for when the caller does not say
+
+
+def _host(a):
+    return a.cpu().numpy() if _is_torch(a) else np.asarray(a)
+
+
+def _rdiff_launch(be, A, b, m, dims, CA, Cb, mc, cdims, cell_off, cell_idx, abs_tol, max_lps, p_max, r_max):
+    (B, m_max, d), (Nc, mc_max) = dims, cdims
+
+    def zeros(shape):   # (a problem that ends early leaves its slots unwritten)
+        return be.torch.zeros(shape, dtype=be.torch.int32, device=be.device) if be.torch is not None else np.zeros(shape, np.int32)
+    res = dict(kind=zeros((B, p_max)), off=zeros((B, p_max + 1)), rows=zeros((B, r_max)), count=zeros((B,)), nrows=zeros((B,)),
+               nlp=zeros((B,)), status=zeros((B,)), mi=zeros((B, RD_MAX_CELLS)), src=zeros((B, RD_MAX_NEW)))
+    be.call("plp_region_diff_batch", B, m_max, d, A, b, m, Nc, mc_max, CA, Cb, mc, cell_off, cell_idx, float(abs_tol),
+            int(max_lps), int(p_max), int(r_max), RD_MAX_CELLS, RD_MAX_NEW, res["kind"], res["off"], res["rows"], res["count"],
+            res["nrows"], res["nlp"], res["status"], res["mi"], res["src"], h2d=(A, b, m, CA, Cb, mc, cell_off, cell_idx))
+    return res
+
+
+def region_diff_search_batch(A, b, m, CA, Cb, mc, cell_off, cell_idx, abs_tol=1e-7, p_max=None, r_max=None, max_lps=1 << 16):
+    """B region_diff searches in one launch (include/plp.h: plp_region_diff_batch), one per wavefront: problem p is the
+    minuend A[p] (m[p] rows) minus the cells cell_idx[cell_off[p] : cell_off[p + 1]], in that order, of the packed cell table
+    CA[Nc, mc_max, d], Cb[Nc, mc_max], mc[Nc].  Rows are unit length already, the cells sorted as region_diff sorts them.
+
+    -> dict(kind int32[B, p_max], off[B, p_max + 1], rows[B, r_max], count[B], nrows[B], nlp[B], status[B] (RD_*),
+            mi[B, 64], src[B, 127]): the pieces of problem p as lists of its LOCAL table rows, in the reference's order
+    (`region_diff_leaves` reads them); src[p, k] = the cell-table row c * mc_max + r of its new row k.
+    With p_max and r_max given the call is enqueued and returns (numpy: blocks, as every host-pointer call); an
+    RD_OVERFLOW problem then holds what fitted, and count / nrows say what it needs.  With either None it launches with
+    room for 32 pieces / 1024 rows, reads the status, and launches once more for the RD_OVERFLOW problems only, sized by
+    their count / nrows."""
+    be = _Backend(A)
+    A, b, m, dims = _packed(be, A, b, m)
+    CA, Cb, mc, (Nc, mc_max, dc) = _packed(be, CA, Cb, mc, "CA")
+    if dc != dims[2]:
+        raise ValueError("region_diff_search_batch: minuends and cells must have the same dimension")
+    B = dims[0]
+    cell_off, cell_idx = be.arr(cell_off, np.int32, (B + 1,)), be.arr(cell_idx, np.int32)
+    fixed = p_max is not None and r_max is not None
+    p1, r1 = int(_RD_P_MAX if p_max is None else p_max), int(_RD_R_MAX if r_max is None else r_max)
+    if p1 < 1 or r1 < 1:
+        raise ValueError("region_diff_search_batch: p_max and r_max must be at least 1")
+    res = _rdiff_launch(be, A, b, m, dims, CA, Cb, mc, (Nc, mc_max), cell_off, cell_idx, abs_tol, max_lps, p1, r1)
+    if fixed or B == 0:
+        return res
+    sel = np.nonzero(_host(res["status"]) == RD_OVERFLOW)[0]
+    if sel.size == 0:
+        return res
+    p2, r2 = max(p1, int(_host(res["count"])[sel].max())), max(r1, int(_host(res["nrows"])[sel].max()))
+    off_h = _host(cell_off).astype(np.int64)
+    pos = np.concatenate([np.arange(off_h[s], off_h[s + 1]) for s in sel]).astype(np.int64)
+    off2 = np.concatenate([[0], np.cumsum(off_h[sel + 1] - off_h[sel])]).astype(np.int32)
+    if be.torch is not None:
+        ix, posx = be.torch.as_tensor(sel, device=be.device), be.torch.as_tensor(pos, device=be.device)
+        off2 = be.torch.as_tensor(off2, device=be.device)
+    else:
+        ix, posx = sel, pos
+    sub_dims = (int(sel.size), dims[1], dims[2])
+    sub = _rdiff_launch(be, be.arr(A[ix]), be.arr(b[ix]), None if m is None else be.arr(m[ix], np.int32), sub_dims, CA, Cb, mc,
+                        (Nc, mc_max), off2, be.arr(cell_idx[posx], np.int32), abs_tol, max_lps, p2, r2)
+    for key, width in (("kind", p2), ("off", p2 + 1), ("rows", r2)):
+        big = sub[key].new_zeros((B, width)) if be.torch is not None else np.zeros((B, width), np.int32)
+        big[:, :res[key].shape[1]] = res[key]
+        res[key] = big
+    for key in res:
+        res[key][ix] = sub[key]
+    return res
+
+
+def region_diff_leaves(res, p):
+    """The pieces of problem p of a region_diff_search_batch result that were written -> [(kind, rows int32 array)]."""
+    n = min(int(res["count"][p]), res["kind"].shape[1])
+    off, rows, kind = _host(res["off"][p]), _host(res["rows"][p]), _host(res["kind"][p])
+    for k in range(n):   # RD_OVERFLOW: what fits is written -- the pieces in front of the first that did not (off = -1)
+        if off[k + 1] < 0:
+            n = k
+            break
+    return [(int(kind[k]), rows[off[k]:off[k + 1]].copy()) for k in range(n)]
+
+
+def _rdiff_unit_rows(A3, b2, m):
+    """The constructor's row scaling as region_diff applies it to its table (polytope.py:1755-1760), elementwise on packed
+    rows; rows past m[p] become 0 -> (An, bn, ok[B]: every live row has a norm above 1e-10)."""
+    live = np.arange(A3.shape[1])[None, :] < m[:, None]
+    norms = np.sqrt(np.sum(A3 * A3, 2))
+    ok = np.all(~live | (norms > 1e-10), axis=1)
+    scale = np.zeros_like(norms)
+    use = live & (norms > 1e-10)
+    scale[use] = 1 / norms[use]
+    return np.where(live[:, :, None], A3, 0.0) * scale[:, :, None], np.where(live, b2, 0.0) * scale, ok
+
+
+def _rdiff_prepare(A, b, m, CA, Cb, mc, cell_off, cell_idx, intersect_tol, order):
+    """Steps 1-4 of region_diff_batch on numpy arrays: unit rows, the radius of every (minuend, listed cell) stack in one
+    cheby_ball_batch, the cells below intersect_tol dropped, each problem's cells ordered by np.argsort(-Rc) on its own
+    array (or by order[p]).  -> dict(A, b, m, CA, Cb, mc, cell_off, cell_idx (the ordered lists), Rc (per listed pair, in
+    the caller's order), ok[B])."""
+    A, b = _np(A), _np(b)
+    B, m_max, d = A.shape
+    CA, Cb = _np(CA), _np(Cb)
+    Nc, mc_max = CA.shape[:2]
+    m = np.full(B, m_max, np.int32) if m is None else _np(m, np.int32)
+    mc = np.full(Nc, mc_max, np.int32) if mc is None else _np(mc, np.int32)
+    cell_off, cell_idx = _np(cell_off, np.int64), _np(cell_idx, np.int64)
+    An, bn, ok = _rdiff_unit_rows(A, b.reshape(B, m_max), m)
+    CAn, Cbn, okc = _rdiff_unit_rows(CA, Cb.reshape(Nc, mc_max), mc)
+    L = int(cell_off[B])
+    owner = np.repeat(np.arange(B), np.diff(cell_off))
+    Rc = np.zeros(L)
+    if L:
+        # the stack [minuend; cell] of every listed pair, the cell's rows right behind the minuend's
+        cidx = cell_idx[:L]
+        ok &= np.bincount(owner, weights=~okc[cidx], minlength=B) == 0
+        R = m_max + mc_max
+        r = np.arange(R)[None, :]
+        mp, mcl = m[owner][:, None], mc[cidx][:, None]
+        from_p, from_c = r < mp, (r >= mp) & (r < mp + mcl)
+        rp, rc_ = np.minimum(r, max(m_max - 1, 0)), np.clip(r - mp, 0, max(mc_max - 1, 0))
+        A3, b3 = np.zeros((L, R, d)), np.zeros((L, R))
+        if m_max:
+            A3 = np.where(from_p[:, :, None], An[owner[:, None], rp], A3)
+            b3 = np.where(from_p, bn[owner[:, None], rp], b3)
+        if mc_max:
+            A3 = np.where(from_c[:, :, None], CAn[cidx[:, None], rc_], A3)
+            b3 = np.where(from_c, Cbn[cidx[:, None], rc_], b3)
+        out = cheby_ball_batch(A3, b3, m=(mp + mcl).ravel().astype(np.int32))
+        Rc = np.where((out["status"] == 0) & (out["r"] >= 0), out["r"], 0.0)
+    new_off, new_idx = [0], []
+    for p in range(B):
+        lo, hi = int(cell_off[p]), int(cell_off[p + 1])
+        Rp = Rc[lo:hi]
+        N = int(np.sum(Rp >= intersect_tol))
+        perm = np.argsort(-Rp) if order is None or order[p] is None else np.asarray(order[p], dtype=int)
+        new_idx.append(cell_idx[lo:hi][perm[:N]])
+        new_off.append(new_off[-1] + N)
+    return dict(A=An, b=bn, m=m, CA=CAn, Cb=Cbn, mc=mc, cell_off=np.asarray(new_off, np.int32),
+                cell_idx=np.concatenate(new_idx).astype(np.int32) if new_idx else np.zeros(0, np.int32), Rc=Rc, ok=ok)
+
+
+def _rdiff_gather(pre, res):
+    """The pieces of every problem as rows of the unit tables -> (status[B]: RD_UNSUPPORTED where a live row had no norm,
+    else the search's; leaves: per problem the list of (kind, A[rows, d], b[rows]) of an RD_OK problem, else [])."""
+    An, bn, mm = pre["A"], pre["b"], pre["m"]
+    B, m_max, d = An.shape
+    CAf, Cbf = pre["CA"].reshape(-1, d), pre["Cb"].ravel()
+    status = np.where(pre["ok"], _host(res["status"]), RD_UNSUPPORTED).astype(np.int32)
+    mi, src_all = _host(res["mi"]), _host(res["src"])
+    leaves = []
+    for p in range(B):
+        mine = []
+        if status[p] == RD_OK:
+            m, M = int(mm[p]), int(mi[p].sum())
+            # the problem's table: the minuend's rows, the new rows by `src`, their negations (the bits of numpy's -A)
+            src = src_all[p, :M].astype(np.int64)
+            TA = np.concatenate([An[p, :m], CAf[src], -CAf[src]])
+            Tb = np.concatenate([bn[p, :m], Cbf[src], -Cbf[src]])
+            mine = [(kind, TA[rows], Tb[rows]) for kind, rows in region_diff_leaves(res, p)]
+        leaves.append(mine)
+    return status, leaves
+
+
+_RD_REDUCE_TOL = 1e-7   # region_diff reduces its leaves with the module's ABS_TOL whatever its own abs_tol (polytope.py)
+
+
+def region_diff_batch(A, b, m, CA, Cb, mc, cell_off, cell_idx, abs_tol=1e-7, intersect_tol=1e-7, order=None):
+    """Everything region_diff (polytope.py) does around its search, for B problems on packed numpy arrays: problem p is the
+    minuend A[p] minus the union of the cells cell_idx[cell_off[p] : cell_off[p + 1]] of CA[Nc, mc_max, d], Cb, mc.
+    Rows are scaled to unit length; the radius Rc of every (minuend, listed cell) stack comes from ONE cheby_ball_batch;
+    cells with Rc < intersect_tol are dropped and the rest ordered by np.argsort(-Rc) on the problem's own array (`order`:
+    a list with a permutation of a problem's list, or None, per problem, instead); the searches run in one launch
+    (region_diff_search_batch); the pieces are gathered from the unit rows, and the pieces the reference reduce()s go
+    through ONE reduce_batch and come back as reduce() leaves them: the kept rows, their right-hand sides through the
+    reference's + 0.1 - 0.1 round trip where the reduce ran to the end, the rows scaled as the Polytope constructor scales
+    them; a piece that reduces to the empty set is dropped, as region_diff's union drops it.
+
+    -> dict(A[P, rows, d], b[P, rows], m[P]: the pieces of all problems; kind[P]: 0 = a piece as the search left it,
+            1 = reduced, 2 = still to be reduce()d by the caller (the fused reduce's Chebyshev LP gave no verdict: rows as
+            the search left them); piece_off[B + 1]: problem p owns pieces piece_off[p] : piece_off[p + 1]; status[B]
+            (RD_*), Rc (per listed pair, in the caller's order), nlp[B]).
+    A problem none of whose cells intersects returns its minuend (unit rows) as its one piece; one with a status other
+    than RD_OK returns no piece (RD_COVERED: the difference is empty; the others are for the caller to solve another way:
+    polytope.region_diff_batch sends them through region_diff)."""
+    pre = _rdiff_prepare(_host(A), _host(b), None if m is None else _host(m), _host(CA), _host(Cb),
+                         None if mc is None else _host(mc), _host(cell_off), _host(cell_idx), intersect_tol, order)
+    d = pre["A"].shape[2]
+    res = region_diff_search_batch(pre["A"], pre["b"], pre["m"], pre["CA"], pre["Cb"], pre["mc"], pre["cell_off"],
+                                   pre["cell_idx"], abs_tol)
+    status, leaves = _rdiff_gather(pre, res)
+    flat = [(p, kind, Ak, bk) for p, mine in enumerate(leaves) for kind, Ak, bk in mine]
+    red = [k for k, piece in enumerate(flat) if piece[1] == 1]
+    dropped = set()
+    kinds = [piece[1] for piece in flat]
+    if red:   # the leaves the reference reduces (ref :2276), all problems' in one launch
+        rm = np.array([flat[k][2].shape[0] for k in red], dtype=np.int32)
+        RA, Rb = np.zeros((len(red), int(rm.max()), d)), np.zeros((len(red), int(rm.max())))
+        for j, k in enumerate(red):
+            RA[j, :rm[j]], Rb[j, :rm[j]] = flat[k][2], flat[k][3]
+        out = reduce_batch(RA, Rb, m=rm, abs_tol=_RD_REDUCE_TOL)
+        masks = keep_to_bool(out["keep"], RA.shape[1])
+        for j, k in enumerate(red):
+            fl = int(out["flags"][j])
+            if fl & _lib.RF_LPFAIL:
+                raise RuntimeError("bounding_box: an LP of the box prefilter of `reduce` ended with status 1 or 4")
+            if fl & 32:   # PLP_RF_F1OPEN: reduce() re-examines these with verified LPs (polytope._reduce_many)
+                kinds[k] = 2
+                continue
+            if fl & _lib.RF_EMPTY:
+                dropped.add(k)
+                continue
+            keep = np.nonzero(masks[j, :rm[j]])[0]
+            Ak, bk = flat[k][2][keep], flat[k][3][keep]
+            if fl & _lib.RF_MINREP:
+                bk = (bk + 0.1) - 0.1   # the h[k] += 0.1; h[k] -= 0.1 round trip of ref :1149-1151
+            norms = np.sqrt(np.add.reduce(Ak * Ak, 1))   # the constructor's scaling (Polytope.__init__)
+            if Ak.size and np.minimum.reduce(norms) > 1e-10:
+                scale = 1 / norms
+                Ak, bk = Ak * scale[:, None], bk * scale
+            flat[k] = (flat[k][0], 1, Ak, bk)
+    keep_k = [k for k in range(len(flat)) if k not in dropped]
+    owner = np.array([flat[k][0] for k in keep_k], dtype=np.int64)
+    piece_off = np.concatenate([[0], np.cumsum(np.bincount(owner, minlength=len(leaves)))]).astype(np.int64) \
+        if len(leaves) else np.zeros(1, np.int64)
+    P = len(keep_k)
+    pm = np.array([flat[k][2].shape[0] for k in keep_k], dtype=np.int32)
+    rmax = int(pm.max()) if P else 0
+    Ao, bo = np.zeros((P, rmax, d)), np.zeros((P, rmax))
+    for q, k in enumerate(keep_k):
+        Ao[q, :pm[q]], bo[q, :pm[q]] = flat[k][2], flat[k][3]
+    return dict(A=Ao, b=bo, m=pm, kind=np.array([kinds[k] for k in keep_k], dtype=np.int32), piece_off=piece_off,
+                status=status, Rc=pre["Rc"], nlp=_host(res["nlp"]))
+
+
 _DGESV = None
 
 

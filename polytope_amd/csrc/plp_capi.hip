@@ -1562,4 +1562,92 @@ int plp_rdiff_result_free(plp_rdiff_result* r) {
     return PLP_OK;
 }
 
+// ------------------------------------------------------------------------------- region_diff, many searches in one launch
+static int rdiff_batch_check(plp_ctx* ctx, int64_t B, int m_max, int d, const double* A, const double* b, int64_t Nc, int mc_max,
+                             const double* CA, const double* Cb, const int32_t* cell_off, const int32_t* cell_idx, int max_lps,
+                             int p_max, int r_max, int n_max, int M_max, const void* kind, const void* off, const void* rows,
+                             const void* count, const void* nrows, const void* nlp, const void* status, const void* mi,
+                             const void* src) {
+    if (!ctx) return fail(PLP_EINVAL, "ctx is NULL");
+    if (B < 0 || m_max < 0 || d < 1 || Nc < 0 || mc_max < 0 || n_max < 0 || M_max < 0) return fail(PLP_EINVAL, "bad sizes");
+    if (B == 0) return PLP_OK;
+    if (d > 4) return fail(PLP_EUNSUPPORTED, "region_diff_batch: d=%d outside the kernel (d<=4)", d);
+    if (p_max < 1 || r_max < 1 || max_lps < 0)
+        return fail(PLP_EINVAL, "region_diff_batch: p_max=%d r_max=%d max_lps=%d", p_max, r_max, max_lps);
+    if (B > 2147483647ll || Nc > 2147483647ll || (long long)Nc * mc_max > 2147483647ll)
+        return fail(PLP_EUNSUPPORTED, "region_diff_batch: B or the cell table exceeds 2^31 - 1");
+    if (!cell_off || !kind || !off || !rows || !count || !nrows || !nlp || !status || (n_max > 0 && !mi) || (M_max > 0 && !src) ||
+        (m_max > 0 && (!A || !b)) || (Nc > 0 && mc_max > 0 && (!CA || !Cb)) || (Nc > 0 && !cell_idx))
+        return fail(PLP_EINVAL, "NULL pointer");
+    return PLP_OK;
+}
+
+int plp_region_diff_batch_dev(plp_ctx* ctx, void* stream, int64_t B, int m_max, int d, const double* A, const double* b,
+                              const int32_t* m, int64_t Nc, int mc_max, const double* CA, const double* Cb, const int32_t* mc,
+                              const int32_t* cell_off, const int32_t* cell_idx, double abs_tol, int max_lps, int p_max,
+                              int r_max, int n_max, int M_max, int32_t* kind, int32_t* off, int32_t* rows, int32_t* count,
+                              int32_t* nrows, int32_t* nlp, int32_t* status, int32_t* mi, int32_t* src) {
+    int rc = rdiff_batch_check(ctx, B, m_max, d, A, b, Nc, mc_max, CA, Cb, cell_off, cell_idx, max_lps, p_max, r_max, n_max, M_max,
+                               kind, off, rows, count, nrows, nlp, status, mi, src);
+    if (rc || B == 0) return rc;
+    if (plp::launch_rdiff_batch(B, m_max, d, A, b, m, Nc, mc_max, CA, Cb, mc, cell_off, cell_idx, abs_tol, max_lps, p_max, r_max,
+                                n_max, M_max, kind, off, rows, count, nrows, nlp, status, mi, src, (hipStream_t)stream))
+        return fail(PLP_EUNSUPPORTED, "region_diff_batch: unsupported size");
+    return check_launch("rdiff_batch_kernel");
+}
+
+int plp_region_diff_batch(plp_ctx* ctx, int64_t B, int m_max, int d, const double* A, const double* b, const int32_t* m,
+                          int64_t Nc, int mc_max, const double* CA, const double* Cb, const int32_t* mc, const int32_t* cell_off,
+                          const int32_t* cell_idx, double abs_tol, int max_lps, int p_max, int r_max, int n_max, int M_max,
+                          int32_t* kind, int32_t* off, int32_t* rows, int32_t* count, int32_t* nrows, int32_t* nlp,
+                          int32_t* status, int32_t* mi, int32_t* src) {
+    int rc = rdiff_batch_check(ctx, B, m_max, d, A, b, Nc, mc_max, CA, Cb, cell_off, cell_idx, max_lps, p_max, r_max, n_max, M_max,
+                               kind, off, rows, count, nrows, nlp, status, mi, src);
+    if (rc || B == 0) return rc;
+    if (cell_off[0] < 0) return fail(PLP_EINVAL, "region_diff_batch: cell_off[0] = %d", cell_off[0]);
+    for (int64_t p = 0; p < B; ++p)   // (the upload of cell_idx is sized by cell_off[B]: every list must lie inside it)
+        if (cell_off[p + 1] < cell_off[p])
+            return fail(PLP_EINVAL, "region_diff_batch: cell_off decreases at %lld", (long long)p);
+    double *dA, *db, *dCA, *dCb;
+    int32_t *dm, *dmc, *dcoff, *dcidx, *dkind, *doff, *drows, *dhead, *dmi, *dsrc;
+    // (count, nrows, nlp and status come back as one block: a call declares at most eight outputs)
+    std::vector<int32_t> head((size_t)B * 4);
+    HostCall hc(ctx);
+    hc.in(dA, A, (size_t)B * m_max * d);
+    hc.in(db, b, (size_t)B * m_max);
+    hc.in(dm, m, B);
+    hc.in(dCA, CA, (size_t)Nc * mc_max * d);
+    hc.in(dCb, Cb, (size_t)Nc * mc_max);
+    hc.in(dmc, mc, Nc);
+    hc.in(dcoff, cell_off, (size_t)B + 1);
+    hc.in(dcidx, cell_idx, (size_t)cell_off[B]);
+    hc.out(dkind, kind, (size_t)B * p_max);
+    hc.out(doff, off, (size_t)B * ((size_t)p_max + 1));
+    hc.out(drows, rows, (size_t)B * r_max);
+    hc.out(dhead, head.data(), (size_t)B * 4);
+    hc.out(dmi, mi, (size_t)B * n_max);
+    hc.out(dsrc, src, (size_t)B * M_max);
+    rc = hc.reserve();
+    if (rc) return rc;
+    rc = hc.upload();
+    if (rc) return rc;
+    // (a problem that ends early leaves its slots unwritten: the caller gets zeros there, not what the arena held)
+    HIP_TRY(hipMemsetAsync(dkind, 0, (size_t)B * p_max * 4, hc.st));
+    HIP_TRY(hipMemsetAsync(doff, 0, (size_t)B * ((size_t)p_max + 1) * 4, hc.st));
+    HIP_TRY(hipMemsetAsync(drows, 0, (size_t)B * r_max * 4, hc.st));
+    if (n_max > 0) HIP_TRY(hipMemsetAsync(dmi, 0, (size_t)B * n_max * 4, hc.st));
+    if (M_max > 0) HIP_TRY(hipMemsetAsync(dsrc, 0, (size_t)B * M_max * 4, hc.st));
+    rc = plp_region_diff_batch_dev(ctx, hc.st, B, m_max, d, dA, db, dm, Nc, mc_max, dCA, dCb, dmc, dcoff, dcidx, abs_tol, max_lps,
+                                   p_max, r_max, n_max, M_max, dkind, doff, drows, dhead, dhead + B, dhead + 2 * B, dhead + 3 * B,
+                                   dmi, dsrc);
+    if (rc) return rc;
+    rc = hc.download();
+    if (rc) return rc;
+    memcpy(count, head.data(), (size_t)B * 4);
+    memcpy(nrows, head.data() + B, (size_t)B * 4);
+    memcpy(nlp, head.data() + 2 * B, (size_t)B * 4);
+    memcpy(status, head.data() + 3 * B, (size_t)B * 4);
+    return PLP_OK;
+}
+
 }  // extern "C"

@@ -67,6 +67,13 @@ int launch_hull_enum(long long B, int n_max, int d, const double* X, const int* 
 int launch_volume_exact(long long B, int m_max, int d, const double* A, const double* b, const int* mrows,
                         const unsigned long long* keep, const double* xc, const double* scale, double* volume, double* area,
                         int* status, hipStream_t st);
+// B set differences, one whole region_diff search per wavefront (plp_rdiff_batch.hip; d <= 4, the caps of
+// plp_rdiff_batch.hpp): the pieces as row lists kind[B][p_max], off[B][p_max + 1], rows[B][r_max], count / nrows / nlp /
+// status[B], mi[B][n_max], src[B][M_max].  2: unsupported size
+int launch_rdiff_batch(long long B, int m_max, int d, const double* A, const double* b, const int* m, long long Nc, int mc_max,
+                       const double* CA, const double* Cb, const int* mc, const int* cell_off, const int* cell_idx,
+                       double abs_tol, int max_lps, int p_max, int r_max, int n_max, int M_max, int* kind, int* off, int* rows,
+                       int* count, int* nrows, int* nlp, int* status, int* mi, int* src, hipStream_t st);
 int launch_reduce_lds(long long B, int m_max, int d, const double* A, const double* b, const int* mrows, double abs_tol,
                       unsigned long long* keep, int* flags, double* r, double* xc, int* nlp, hipStream_t st);
 

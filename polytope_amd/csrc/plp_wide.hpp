@@ -277,6 +277,51 @@ __device__ __forceinline__ int wide_run(const int lane, const int m, typename Ro
     return status;
 }
 
+// The Chebyshev radius of the polytope whose m <= 64 rows a x <= bi the lanes hold, one each (`has`: this lane holds one),
+// as cheby_ball reads it (polytope.py:1289-1297): the radius when the LP is optimal with r >= 0, 0 when optimal with
+// r < 0, NaN when it ended without a verdict.  The body of server_slot_w (plp_rdiff.hip): the norm column, wide_run's
+// forced first pivot, the read-out.  Wave-uniform result; `sh`: this wavefront's LDS block.
+template <int D>
+__device__ __forceinline__ double cheby_radius_rows(const int lane, const int m, const bool has, const double (&a)[D],
+                                                    const double bi_in, WideShared<D + 1>& sh) {
+    constexpr int NC = D + 1;
+    typename RowVec<NC>::type Tv = (typename RowVec<NC>::type)(0.0);
+    double T16 = 0.0;
+    double nrm2 = 0.0;
+    bool finite = true;
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+        const double v = has ? a[k] : 0.0;
+        ROW_SET(k, v);
+        nrm2 = nrm2 + v * v;
+        finite = finite & isfinite(v);
+    }
+    const double bi = has ? bi_in : 0.0;
+    finite = finite & isfinite(bi);
+    const double nrm = sqrt(nrm2);
+    const bool zero = !(nrm > 0.0);
+    bool rowact = has & !zero;
+    ROW_SET(D, rowact ? nrm : 0.0);
+    double beta = rowact ? bi : 0.0;
+    int rowvar = NC + lane, rowneg = 0;
+    wave_sync();   // (the last LP's reads of the block are done)
+    if (lane <= NC) {
+        sh.cost[lane] = lane == D ? -1.0 : 0.0;
+        sh.cv[lane] = (lane + 1) << 1;
+    }
+    const bool infeasible0 = __ballot(has & zero & (bi < -TOL_FEAS)) != 0;
+    const bool bad = (__ballot(!finite) != 0) | (m > 64);
+    wave_sync();
+    int st, iters = 0;
+    if (bad) st = ST_NUM;
+    else if (infeasible0) st = ST_INFEAS;
+    else st = wide_run<NC>(lane, m, Tv, T16, beta, rowvar, rowneg, rowact, sh, NC, true, bi / nrm, iters);
+    const double mine = rowneg ? -beta : beta;
+    const uint64_t ob = __ballot(rowvar == D);
+    const double rv = ob ? uniform_lane(mine, __ffsll((long long)ob) - 1) : 0.0;
+    return st != ST_OPT ? __builtin_nan("") : (rv >= 0.0 ? rv : 0.0);
+}
+
 // One LP  min c.y  s.t.  A y <= beta  (y free, beta >= 0: the origin is feasible) of a polytope whose rows sit in LDS, one
 // per lane (dead rows zeroed there): the dense twin of lazy::solve() -- same arguments, same numbers (the dictionary
 // arithmetic is SimplexR's: bitwise the status and -zeta of reduce_r_kernel<D, 64, 1>), Bland's rule inside instead of a

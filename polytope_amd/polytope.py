@@ -1819,6 +1819,97 @@ def region_diff(poly, reg, abs_tol=ABS_TOL, intersect_tol=ABS_TOL, save=False, _
     return _union_all(pieces)
 
 
+def region_diff_batch(polys, regs, abs_tol=ABS_TOL, intersect_tol=ABS_TOL, _info=None):
+    """[region_diff(polys[k], regs[k], abs_tol, intersect_tol) for every k] with all searches in ONE launch.
+
+    `regs`: one Region (or Polytope) shared by all polytopes, or one per polytope.  On the 'hip' backend the Chebyshev radii
+    of all (polytope, cell) stacks come from one batch, the searches run one per wavefront (batch.region_diff_search_batch),
+    and the pieces the reference reduce()s go through one fused reduce; the early exits of region_diff (empty region,
+    empty polytope, nothing intersects, a cell that covers the polytope) are taken as there.  A problem beyond the kernel's
+    caps (d > 4, more than 64 rows or cells, a list of more than 64 rows, the LP budget), or one on which the reference's
+    index arithmetic raises IndexError, goes through region_diff itself.  On any other backend this is the loop.
+    `_info` (test hook): a dict that receives Rc (per problem, the radii region_diff would compute; None where the
+    problem never reached the batch), status and nlp."""
+    from .batch import _rdiff_prepare, _rdiff_gather, region_diff_search_batch, RD_OK, RD_COVERED, RD_MAX_CELLS
+    polys = list(polys)
+    n = len(polys)
+    regs = [regs] * n if isinstance(regs, (Polytope, Region)) else list(regs)
+    if len(regs) != n:
+        raise ValueError("region_diff_batch: one Region for all polytopes, or one per polytope")
+    out = [None] * n
+    info = dict(Rc=[None] * n, status=[None] * n, nlp=[None] * n)
+    groups = {}   # dimension -> the problems that go into its launch
+    for k in range(n):
+        poly, reg = polys[k], regs[k]
+        if isinstance(reg, Polytope):
+            reg = Region([reg])
+        batched = _use_hip() and _RDIFF_NATIVE and abs_tol > 0 and isinstance(poly, Polytope) and isinstance(reg, Region) \
+            and len(reg) > 0 and not is_empty(reg) and not is_empty(poly)
+        if batched:
+            d = poly.A.shape[1]
+            batched = _fits(poly.A.shape[0], d) and d <= 4 and len(reg) <= RD_MAX_CELLS and \
+                all(c.A.ndim == 2 and c.A.shape[1] == d and 0 < c.A.shape[0] <= _MAX_ROWS for c in reg.list_poly)
+        if not batched:
+            out[k] = region_diff(polys[k], regs[k], abs_tol, intersect_tol)
+            continue
+        groups.setdefault(d, []).append((k, poly.copy(), reg))
+    for d, members in groups.items():
+        # the cell table: every Region once, its cells in order
+        first, cells = {}, []
+        for _, _, reg in members:
+            if id(reg) not in first:
+                first[id(reg)] = len(cells)
+                cells.extend(reg.list_poly)
+        B, m_max, mc_max = len(members), max(p.A.shape[0] for _, p, _ in members), max(c.A.shape[0] for c in cells)
+        A, b, m = np.zeros((B, m_max, d)), np.zeros((B, m_max)), np.zeros(B, np.int32)
+        CA, Cb, mc = np.zeros((len(cells), mc_max, d)), np.zeros((len(cells), mc_max)), np.zeros(len(cells), np.int32)
+        for q, (_, p, _) in enumerate(members):
+            m[q] = p.A.shape[0]
+            A[q, :m[q]], b[q, :m[q]] = p.A, p.b
+        for q, c in enumerate(cells):
+            mc[q] = c.A.shape[0]
+            CA[q, :mc[q]], Cb[q, :mc[q]] = c.A, c.b
+        cell_off = np.concatenate([[0], np.cumsum([len(reg) for _, _, reg in members])]).astype(np.int64)
+        cell_idx = np.concatenate([first[id(reg)] + np.arange(len(reg)) for _, _, reg in members]).astype(np.int64)
+        pre = _rdiff_prepare(A, b, m, CA, Cb, mc, cell_off, cell_idx, intersect_tol, None)
+        res = region_diff_search_batch(pre["A"], pre["b"], pre["m"], pre["CA"], pre["Cb"], pre["mc"], pre["cell_off"],
+                                       pre["cell_idx"], abs_tol)
+        _cheby_fill([cells[c] for c in sorted(set(int(c) for c in pre["cell_idx"])) if cells[c].fulldim is None])
+        statuses, gathered = _rdiff_gather(pre, res)
+        leaves, todo = {}, []
+        for q, (k, p, reg) in enumerate(members):
+            Rc = np.array(pre["Rc"][cell_off[q]:cell_off[q + 1]], dtype=float)
+            status = int(statuses[q])
+            info["Rc"][k], info["status"][k], info["nlp"][k] = Rc, status, int(res["nlp"][q])
+            picked = pre["cell_idx"][pre["cell_off"][q]:pre["cell_off"][q + 1]]
+            if len(picked) == 0:
+                logger.debug("no Polytope in the Region intersects the given Polytope")
+                out[k] = p
+            elif status == RD_COVERED or not all(bool(is_fulldim(cells[c])) for c in picked):
+                out[k] = Polytope()   # some cell covers the polytope
+            elif status == RD_OK:
+                leaves[q] = []
+                for kind, Ak, bk in gathered[q]:
+                    piece = Polytope(Ak, bk, normalize=False)
+                    leaves[q].append((kind, piece))
+                    if kind == 1:   # leaves the reference reduces (:2276)
+                        todo.append(piece)
+            else:   # beyond the kernel (or IndexError in the reference): the single call, with the radii it would compute
+                out[k] = region_diff(polys[k], regs[k], abs_tol, intersect_tol, _Rc=Rc)
+        done = [None] * len(todo)
+        small = [t for t, p in enumerate(todo) if p.A.size > 0 and _fits_reduce(p.A.shape[0], p.A.shape[1])]
+        if small:   # one fused reduce launch for the leaves of all problems
+            for t, q_ in zip(small, _reduce_many([todo[t] for t in small], ABS_TOL)):
+                done[t] = q_
+        red = iter([r if r is not None else reduce(p) for p, r in zip(todo, done)])
+        for q, (k, _, _) in enumerate(members):   # (in the order the leaves were queued)
+            if q in leaves:
+                out[k] = _union_all([next(red) if kind == 1 else piece for kind, piece in leaves[q]])
+    if _info is not None:
+        _info.update(info)
+    return out
+
+
 class _DiffSearch:
     """The search of region_diff (ref :2201-2281) over row lists of one constraint table: m rows of the minuend, then
     M = sum(mi) new rows of the cells (cell j from beg[j]), then their M negations.

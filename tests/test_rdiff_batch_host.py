@@ -1,0 +1,321 @@
+"""CPU: the sequential rule of region_diff_batch (polytope_amd/csrc/plp_rdiff_batch.hpp built with g++ -ffp-contract=off,
+tests/rdiff_batch_host.py) -- the pieces against the library's search (plp_rdiff_search.hpp without speculation) and its
+Python twin polytope._DiffSearch on the random overlapping boxes of the GPU parity test, the table build against the arrays
+region_diff builds in numpy, single moves on hand-made states, every status once, and the stand-alone program under the
+sanitizers."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import host_build as hb  # noqa: E402
+import rdiff_batch_host as RB  # noqa: E402
+import rdiff_host as RH  # noqa: E402
+import test_rdiff_search_host as TS  # noqa: E402
+
+N_TRIALS = 24
+ABS_TOL = 1e-7
+# On these cases no radius comes closer than 4.9e-8 to abs_tol or abs_tol / 2 (a radius of 0 is 5e-8 from abs_tol / 2);
+# the LPs are exact to about 1e-12 (plp_rdiff_search.hpp, on Frame), so a radius this far from a threshold is on the same
+# side of it whichever of the searches reads it, and whatever rows a frame added before.
+MARGIN = 4e-8
+
+
+@pytest.fixture(scope="module")
+def LB(tmp_path_factory):
+    return RB.build(tmp_path_factory.mktemp("rdiff_batch_host"))
+
+
+@pytest.fixture(scope="module")
+def L(tmp_path_factory):
+    return RH.build(tmp_path_factory.mktemp("rdiff_host_for_batch"))
+
+
+def _free(fn, name):
+    return fn.__closure__[fn.__code__.co_freevars.index(name)].cell_contents
+
+
+@pytest.fixture(scope="module")
+def cases(L, LB, oracle):
+    """region_diff on the scipy backend over the 24 random cases, with polytope._DiffSearch replaced by a wrapper that
+    keeps the table region_diff built and runs, on the same table, tolerance and radii: the real twin, the library's
+    search without speculation, and the new rule (search alone, and table build + search from the packed inputs)."""
+    import polytope_amd.polytope as pcm
+    from polytope_amd import solvers
+    records = []
+    real = pcm._DiffSearch
+
+    class Spy(object):
+        def __init__(self, m, mi, beg, M, abs_tol, radii_rows, look_ahead):
+            poly_of = _free(radii_rows, "poly_of")
+            self.rec = dict(m=int(m), mi=[int(v) for v in mi], M=int(M), tol=abs_tol, A=_free(poly_of, "A").copy(),
+                            B=_free(poly_of, "B").copy(), radii=TS.SharedRadii(radii_rows, int(m) + 2 * int(M), oracle))
+            self.twin = real(m, mi, beg, M, abs_tol, self.rec["radii"], look_ahead)
+            # the dead cells of the twin's frames, as (frame rows, cell): read after its run
+            self.rec["twin_obj"] = self.twin
+
+        def run(self):
+            rec = self.rec
+            try:
+                rec["twin"] = [(kind, rec["radii"].key(rows)) for kind, rows in self.twin.run()]
+            except IndexError:
+                rec["twin"] = "IndexError"
+            records.append(rec)
+            if rec["twin"] == "IndexError":
+                raise IndexError("region_diff twin")
+            for kind, rows in rec["twin"]:
+                yield kind, list(rows)
+
+    saved_solver, solvers.default_solver = solvers.default_solver, "scipy"
+    pcm._DiffSearch = Spy
+    try:
+        for trial, (P, cells) in enumerate(RH.random_cases(N_TRIALS)):
+            P = P.copy()
+            cells = [c.copy() for c in cells]
+            Rc = np.array(pcm._radii_stacked(P, cells), dtype=float)
+            n0 = len(records)
+            try:
+                pcm.region_diff(P.copy(), pcm.Region([c.copy() for c in cells]), _Rc=Rc)
+            except IndexError:
+                pass
+            assert len(records) == n0 + 1, trial   # every case reaches its search, once
+            rec = records[-1]
+            order = np.argsort(-Rc)[:int(np.sum(Rc >= ABS_TOL))]
+            rec.update(trial=trial, P=P, cells=cells, order=order, d=P.A.shape[1])
+    finally:
+        pcm._DiffSearch = real
+        solvers.default_solver = saved_solver
+    for rec in records:
+        rec["lib"] = RH.search(L, rec["m"], rec["mi"], rec["tol"], rec["radii"], knobs=RH.NO_SPECULATION)
+        rec["new"] = RB.search(LB, rec["m"], rec["mi"], rec["tol"], rec["radii"])
+        CA, Cb, mc = RB.pack_cells([(c.A, c.b) for c in rec["cells"]])
+        rec["packed"] = (rec["P"].A, rec["P"].b, CA, Cb, mc, rec["order"].astype(np.int32))
+        rec["full"] = RB.problem(LB, *rec["packed"], rec["tol"], rec["radii"])
+    return records
+
+
+def test_inputs_fit_the_caps_and_keep_clear_of_the_thresholds(cases):
+    """What the comparison below rests on, asserted on this run's own tables and radii: the caps of the kernel hold, and no
+    radius any of the searches read lies within MARGIN of abs_tol or abs_tol / 2."""
+    assert sorted(rec["trial"] for rec in cases) == list(range(N_TRIALS))
+    longest = pieces = lps = 0
+    for rec in cases:
+        assert rec["tol"] == ABS_TOL
+        assert rec["m"] <= 64 and len(rec["mi"]) <= 64 and rec["m"] + 2 * rec["M"] <= RB.MAX_TABLE, rec["trial"]
+        asked = rec["new"].asked + rec["lib"].asked
+        longest = max([longest] + [len(w) for w in asked])
+        radii = np.array([rec["radii"].known[rec["radii"].key(w)] for w in asked], dtype=float)
+        radii = radii[~np.isnan(radii)]
+        gap = min(np.abs(radii - ABS_TOL).min(), np.abs(radii - 0.5 * ABS_TOL).min())
+        assert gap > MARGIN, (rec["trial"], gap)
+        pieces, lps = max(pieces, rec["new"].count), max(lps, rec["new"].nlp)
+    print("longest list %d rows, up to %d pieces and %d LPs per case" % (longest, pieces, lps))
+    assert longest <= RB.MAX_LIST
+
+
+def test_pieces_equal_the_library_search_and_the_twin(cases):
+    """Case 1: the same leaves (kind and row tuples, in order) as plp::rdiff::Search without speculation and as
+    polytope._DiffSearch, or RD_INDEX exactly where they end with an index out of range; at least as many LPs as the
+    library reads radii; and every list asked beyond the library's is a scan cell the library had solved under a subset of
+    the rows with a radius <= abs_tol / 2 -- the cell one of its frames marks dead."""
+    compared = extra_total = 0
+    for rec in cases:
+        lib, new, twin = rec["lib"], rec["new"], rec["twin"]
+        if twin == "IndexError":
+            assert lib.code == RH.BAD_INDEX and new.status == RB.RD_INDEX, rec["trial"]
+            continue
+        assert lib.code == RH.OK and new.status == RB.RD_OK, (rec["trial"], lib.code, new.status)
+        assert new.leaves == lib.leaves == twin, rec["trial"]
+        assert new.count == len(twin) and new.nrows == sum(len(r) for _, r in twin)
+        assert new.nlp == len(new.asked) >= lib.n_requests, rec["trial"]
+        m, mi = rec["m"], rec["mi"]
+        beg = m + np.concatenate([[0], np.cumsum(mi[:-1])]).astype(int)
+        blocks = [tuple(range(beg[j], beg[j] + mi[j])) for j in range(len(mi))]
+        lib_asked = set(lib.asked)
+        dead = {}   # cell -> the row sets under which the library solved it with a radius <= tol / 2
+        for w in lib.asked:
+            for j, blk in enumerate(blocks):
+                if w[-len(blk):] == blk and rec["radii"].known[w] <= 0.5 * rec["tol"]:
+                    dead.setdefault(j, []).append(frozenset(w[:-len(blk)]))
+        extra = [w for w in new.asked if w not in lib_asked]
+        for w in extra:
+            owners = [j for j, blk in enumerate(blocks) if w[-len(blk):] == blk]
+            assert any(base <= frozenset(w[:-len(blocks[j])]) for j in owners for base in dead.get(j, [])), (rec["trial"], w)
+        extra_total += len(extra)
+        compared += 1
+        print("trial %d: %d pieces, %d LPs (the library reads %d radii), %d beyond the library's lists" % (
+            rec["trial"], new.count, new.nlp, lib.n_requests, len(extra)))
+    assert compared >= 20
+    print("%d LPs beyond the library's lists in all" % extra_total)
+
+
+def test_build_and_search_from_packed_inputs(cases):
+    """Cases 1 and 2 together: from the packed minuend and cells the rule builds the table itself and finds the same leaves."""
+    for rec in cases:
+        assert rec["full"].status == rec["new"].status and rec["full"].leaves == rec["new"].leaves, rec["trial"]
+        assert rec["full"].asked == rec["new"].asked
+
+
+def _check_table(got, pA, pb, cells, order, mc_max, want=None):
+    A, B, mi = RB.numpy_table(pA, pb, [cells[k] for k in order], ABS_TOL)
+    if want is not None:   # the replica above IS what region_diff builds
+        assert hb.same_bits(A, want[0]) and hb.same_bits(B, want[1]) and list(mi) == list(want[2])
+    assert list(got.mi) == list(mi)
+    if np.any(mi == 0):
+        assert got.status == RB.RD_COVERED and got.count == 0 and got.leaves == []
+    assert got.M == int(mi.sum())
+    assert hb.same_bits(got.table[:, :-1], A) and hb.same_bits(got.table[:, -1], B)
+    # src: new row k is row src % mc_max of cell src // mc_max
+    m = pA.shape[0]
+    for k, s in enumerate(got.src):
+        cA, cb = cells[s // mc_max]
+        assert hb.same_bits(cA[s % mc_max], A[m + k]) and cb[s % mc_max] == B[m + k]
+    return mi
+
+
+def test_table_build_bit_for_bit(cases, LB):
+    """Case 2: mi, src and the table rows equal the arrays region_diff builds in numpy -- on the 24 cases (against the
+    arrays taken from region_diff itself), with a cell row equal to a minuend row, and with a second cell that repeats a
+    minuend face within abs_tol / 2: mi == 0, RD_COVERED."""
+    for rec in cases:
+        pA, pb, CA, Cb, mc, order = rec["packed"]
+        cells = [(c.A, c.b) for c in rec["cells"]]
+        _check_table(rec["full"], pA, pb, cells, order, CA.shape[1], want=(rec["A"], rec["B"], rec["mi"]))
+    never = lambda lists: [0.0 for _ in lists]   # noqa: E731
+    pA = np.array([[1.0, 0], [0, 1.0], [-1.0, 0], [0, -1.0]])
+    pb = np.array([1.0, 1.0, 0.0, 0.0])
+    # cell 0 shares the face x <= 1 with the minuend exactly; cell 1 cuts it with four new rows
+    cell0 = (pA.copy(), np.array([1.0, 0.5, -0.5, -0.25]))
+    cell1 = (pA.copy(), np.array([0.75, 0.75, -0.25, -0.25]))
+    CA, Cb, mc = RB.pack_cells([cell0, cell1])
+    got = RB.problem(LB, pA, pb, CA, Cb, mc, [0, 1], ABS_TOL, never)
+    assert list(_check_table(got, pA, pb, [cell0, cell1], [0, 1], 4)) == [3, 4] and got.status == RB.RD_OK
+    # the second cell repeats all four faces of the minuend within abs_tol / 2 (an L1 distance of 4e-8 per row)
+    cell2 = (pA.copy(), pb + np.array([4e-8, -4e-8, 4e-8, -4e-8]))
+    CA, Cb, mc = RB.pack_cells([cell1, cell2])
+    got = RB.problem(LB, pA, pb, CA, Cb, mc, [0, 1], ABS_TOL, never)
+    assert list(_check_table(got, pA, pb, [cell1, cell2], [0, 1], 4)) == [4, 0] and got.status == RB.RD_COVERED
+    assert got.asked == []
+
+
+def test_moves_equal_the_existing_state(L, LB):
+    """Case 3: on the hand-made states of test_rdiff_search_host.py (level -1 with open cells, counters above mi, indices
+    that wrap or leave the table) and its 3 000 random states, the fixed-array State equals plp::rdiff::State field for
+    field: level, ended, counters, INDICES, the sum of the counters, the resolved rows."""
+    rng = np.random.default_rng(5)
+    states = list(TS.MOVE_STATES)
+    for _ in range(3000):
+        N = int(rng.integers(1, 5))
+        m = int(rng.integers(1, 4))
+        mi = [int(v) for v in rng.integers(1, 4, N)]
+        nrows = m + 2 * sum(mi)
+        counter = [int(rng.integers(0, mi[j] + 3)) if rng.random() < 0.6 else 0 for j in range(N)]
+        idx = [int(v) for v in rng.integers(-nrows - 4 if rng.random() < 0.3 else 0, nrows + (4 if rng.random() < 0.2 else 0),
+                                            int(rng.integers(1, m + sum(counter) + 3)))]
+        states.append((m, mi, counter, idx, int(rng.integers(0, N)), int(rng.integers(0, 2))))
+    out_of_range = 0
+    for st in states:
+        want = RH.move(L, *st)
+        assert RB.move(LB, *st) == want, st
+        out_of_range += want[5] is None
+    assert out_of_range >= 5
+    for st in TS.MOVE_STATES[:2]:
+        assert RB.move(LB, *st)[:2] == (-1, True)
+
+
+def test_each_remaining_status_once(cases, LB):
+    """Case 4: RD_OVERFLOW with the right count / nrows and what fits written, RD_BUDGET, RD_LONG, RD_UNSUPPORTED."""
+    rec = next(r for r in cases if r["twin"] != "IndexError" and len(r["twin"]) > 4)
+    full = rec["new"]
+    got = RB.search(LB, rec["m"], rec["mi"], rec["tol"], rec["radii"], p_max=2)
+    assert got.status == RB.RD_OVERFLOW and (got.count, got.nrows, got.nlp) == (full.count, full.nrows, full.nlp)
+    assert got.leaves == full.leaves[:2]
+    few_rows = len(full.leaves[0][1]) + len(full.leaves[1][1]) + 1   # two pieces fit, the third does not
+    got = RB.search(LB, rec["m"], rec["mi"], rec["tol"], rec["radii"], r_max=few_rows)
+    assert got.status == RB.RD_OVERFLOW and (got.count, got.nrows) == (full.count, full.nrows)
+    assert got.leaves == full.leaves[:2]
+    got = RB.search(LB, rec["m"], rec["mi"], rec["tol"], rec["radii"], max_lps=5)
+    assert got.status == RB.RD_BUDGET and got.nlp == 5 and got.asked == full.asked[:5]
+    assert got.leaves == [lf for lf in full.leaves[:got.count]]
+    # a table whose SECOND list has 65 rows: 63 rows of the minuend, cell 0 (one new row) is empty, cell 1 has two
+    asked = RB.search(LB, 63, [1, 2], 1e-7, lambda lists: [0.0 for _ in lists])
+    assert asked.status == RB.RD_LONG and [len(w) for w in asked.asked] == [64] and asked.count == 0
+    got = RB.search(LB, 2, [1] * 65, 1e-7, lambda lists: [1.0 for _ in lists])
+    assert got.status == RB.RD_UNSUPPORTED and got.asked == [] and got.count == 0
+    assert RB.search(LB, 65, [1], 1e-7, lambda lists: [1.0 for _ in lists]).status == RB.RD_UNSUPPORTED
+    assert RB.search(LB, 2, [64, 64], 1e-7, lambda lists: [1.0 for _ in lists]).status == RB.RD_UNSUPPORTED   # m + 2M = 258
+
+
+def _write_problem(f, rec, out, max_lps, p_max, r_max):
+    pA, pb, CA, Cb, mc, order = rec["packed"]
+    hexs = lambda a: " ".join(float(v).hex() for v in np.ravel(a))   # noqa: E731
+    f.write("%d %d %d %d %d %s %d %d %d\n" % (pA.shape[1], pA.shape[0], CA.shape[0], CA.shape[1], len(order),
+                                              float(rec["tol"]).hex(), max_lps, p_max, r_max))
+    for a in (pA, pb, CA, Cb):
+        f.write(hexs(a) + "\n")
+    f.write(" ".join(str(int(v)) for v in mc) + "\n" + " ".join(str(int(v)) for v in order) + "\n")
+    lists = list(dict.fromkeys(out.asked))
+    f.write("%d\n" % len(lists))
+    for w in lists:
+        r = rec["radii"].known[w]
+        f.write("%d %s %s\n" % (len(w), " ".join(str(v) for v in w), "nan" if r != r else float(r).hex()))
+    f.write("%d %d %d\n" % (out.count, out.nrows, out.status))
+    n = len(out.leaves)
+    off = np.concatenate([[0], np.cumsum([len(r) for _, r in out.leaves])]).astype(int)
+    f.write(" ".join(str(k) for k, _ in out.leaves) + "\n" + " ".join(str(v) for v in off[:n + 1]) + "\n")
+    f.write(" ".join(str(v) for _, r in out.leaves for v in r) + "\n")
+
+
+def test_program_under_sanitizers(cases, LB, tmp_path):
+    """Case 5: the stand-alone program runs cases 0-5 again -- table build and search, the radii replayed from this run,
+    once with room for every piece and once with p_max = 2 -- under -fsanitize=address,undefined."""
+    path = os.path.join(str(tmp_path), "problems.txt")
+    recs = [r for r in cases if r["trial"] < 6]
+    assert len(recs) == 6
+    with open(path, "w") as f:
+        f.write("%d\n" % (2 * len(recs)))
+        for rec in recs:
+            full = rec["full"]
+            _write_problem(f, rec, full, 1 << 16, max(full.count, 1), max(full.nrows, 1))
+            small = RB.problem(LB, *rec["packed"], rec["tol"], rec["radii"], p_max=2, r_max=max(full.nrows, 1))
+            _write_problem(f, rec, small, 1 << 16, 2, max(full.nrows, 1))
+    prog = RB.build_program(tmp_path)
+    p = subprocess.run([prog, path], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
+    assert "12 problems" in p.stdout and "inconsistent: 0" in p.stdout, p.stdout
+
+
+def test_public_call_on_another_backend_is_the_loop():
+    """polytope.region_diff_batch on the scipy backend: [region_diff(p, r)] piece for piece, with one Region per
+    polytope and with one Region (or one Polytope) shared by all; a list of Regions of another length is refused."""
+    import polytope_amd
+    import polytope_amd.polytope as pcm
+    from polytope_amd import solvers
+
+    def pieces(D):
+        ps = list(D.list_poly) if isinstance(D, pcm.Region) else ([] if D.A.size == 0 else [D])
+        return [(q.A, q.b) for q in ps]
+
+    def same(got, want):
+        assert len(got) == len(want)
+        for g, w in zip(got, want):
+            assert len(pieces(g)) == len(pieces(w))
+            assert all(hb.same_bits(A0, A1) and hb.same_bits(b0, b1) for (A0, b0), (A1, b1) in zip(pieces(g), pieces(w)))
+    saved, solvers.default_solver = solvers.default_solver, "scipy"
+    try:
+        cases = [c for k, c in enumerate(RH.random_cases(7)) if k % 3 == 0]   # d = 2: trials 0, 3, 6
+        polys = [P for P, _ in cases]
+        regs = [pcm.Region([c.copy() for c in cells]) for _, cells in cases]
+        same(polytope_amd.region_diff_batch(polys, regs), [pcm.region_diff(p, r) for p, r in zip(polys, regs)])
+        same(polytope_amd.region_diff_batch(polys, regs[1]), [pcm.region_diff(p, regs[1]) for p in polys])
+        cell = regs[0].list_poly[0]
+        same(polytope_amd.region_diff_batch(polys[:2], cell), [pcm.region_diff(p, cell) for p in polys[:2]])
+        assert polytope_amd.region_diff_batch([], regs[0]) == []
+        with pytest.raises(ValueError):
+            polytope_amd.region_diff_batch(polys, regs[:2])
+    finally:
+        solvers.default_solver = saved
