@@ -606,6 +606,36 @@ int plp_region_diff_batch_dev(plp_ctx *ctx, void *stream, int64_t B, int m_max, 
                               int32_t *rows, int32_t *count, int32_t *nrows, int32_t *nlp, int32_t *status, int32_t *mi,
                               int32_t *src);
 
+/*
+ * The facet tests of envelope() (polytope.py envelope, ref :1414-1464) for B regions in one launch.  The members of all
+ * regions are one packed table A[C][mc_max][d], b[C][mc_max], mc[C] (NULL = mc_max) of unit rows; region p lists the
+ * members mem_idx[reg_off[p] .. reg_off[p + 1]) (mem_idx NULL: list entry w is member w), L = the length of mem_idx.  Two
+ * regions, or two entries of one region, may list the same member.  One wavefront takes one list entry w -- member
+ * i = mem_idx[w] of its region -- and tests every row ii of i against every OTHER entry j of the same list: row ii is
+ * crossed once the Chebyshev radius R of [rows of j; -a_ii x <= -b_ii] exceeds abs_tol, and outer otherwise.  Rows that are
+ * crossed already are not tested again (the verdict is an OR: the order changes the LP count only).
+ * A test with R NaN or abs_tol / 2 < R < 2 * abs_tol has no verdict: it neither crosses nor clears its row.
+ * Caps: d <= 8, every listed member 1 .. 63 rows; no cap on the members of a region.
+ * Out, per list entry: outer[L] (bit ii set = row ii of the member is outer), nlp[L] LPs run, status[L]:
+ *        PLP_ENV_OK;
+ *        PLP_ENV_OPEN         a row is not crossed and one of its tests had no verdict: outer holds it as outer;
+ *        PLP_ENV_UNSUPPORTED  a listed member with no row or more than 63, a listed index outside the table, or no pair
+ *                             reg_off[p] <= w < reg_off[p + 1] <= L around the entry (the region of w is found by bisection:
+ *                             reg_off starts above w, decreases in front of it, or ends beyond L): nothing is run, outer 0.
+ * Neither form reads mem_idx beyond L or the table beyond C members, whatever reg_off and mem_idx hold.
+ * B = 0 or L = 0: returns PLP_OK, nothing runs.  d > 8: PLP_EUNSUPPORTED.
+ * The _dev form enqueues on `stream` and uses no scratch of the context.
+ */
+#define PLP_ENV_OK 0
+#define PLP_ENV_OPEN 1
+#define PLP_ENV_UNSUPPORTED 2
+int plp_envelope_batch(plp_ctx *ctx, int64_t C, int mc_max, int d, const double *A, const double *b, const int32_t *mc,
+                       int64_t B, const int32_t *reg_off, int64_t L, const int32_t *mem_idx, double abs_tol, uint64_t *outer,
+                       int32_t *status, int32_t *nlp);
+int plp_envelope_batch_dev(plp_ctx *ctx, void *stream, int64_t C, int mc_max, int d, const double *A, const double *b,
+                           const int32_t *mc, int64_t B, const int32_t *reg_off, int64_t L, const int32_t *mem_idx,
+                           double abs_tol, uint64_t *outer, int32_t *status, int32_t *nlp);
+
 /* cross-lane primitive self-test (group size 8/16/32/64); host out_d[128], out_u[128] */
 int plp_selftest(plp_ctx *ctx, int group_size, double *out_d, uint32_t *out_u);
 

@@ -37,5 +37,6 @@ from .batch import (  # noqa: F401
     volume_exact_batch, locate_batch, locate_grid,
 )
 from .polytope import region_diff_batch  # noqa: F401,E402  (the Polytope-level call; the packed one is batch.region_diff_batch)
+from .polytope import envelope_batch, is_convex_batch  # noqa: F401,E402  (the raw launch is batch.envelope_outer_batch)
 
 __version__ = "0.1.0"

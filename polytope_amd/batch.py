@@ -1440,6 +1440,42 @@ def region_diff_batch(A, b, m, CA, Cb, mc, cell_off, cell_idx, abs_tol=1e-7, int
                 status=status, Rc=pre["Rc"], nlp=_host(res["nlp"]))
 
 
+# ------------------------------------------------------------------ envelope: the facet tests of many regions in one launch
+ENV_OK, ENV_OPEN, ENV_UNSUPPORTED = range(3)   # include/plp.h: PLP_ENV_*
+ENV_MAX_DIM, ENV_MAX_ROWS = 8, 63              # the kernel's caps on d and on the rows of a listed member
+
+
+def envelope_outer_batch(A, b, m, reg_off, mem_idx=None, abs_tol=1e-7):
+    """The facet tests of envelope() for B regions in one launch (include/plp.h: plp_envelope_batch), one list entry per
+    wavefront.  The members of all regions are the packed table A[C, mc_max, d], b[C, mc_max], m[C] (None: mc_max rows
+    each) of unit rows; region p lists the members mem_idx[reg_off[p] : reg_off[p + 1]] (mem_idx None: the members of region
+    p are reg_off[p] .. reg_off[p + 1] - 1 themselves).  Two regions may list the same member.
+
+    -> dict(outer uint64[L] (int64 with tensors: the same bits), status int32[L] (ENV_*), nlp int32[L]) per list entry w:
+    bit ii of outer[w] is set when no other entry of w's list reaches beyond row ii of member mem_idx[w] by more than
+    abs_tol.  ENV_OPEN: a row counted as outer has a test behind it whose radius was NaN or within (abs_tol / 2,
+    2 * abs_tol); ENV_UNSUPPORTED: a listed member has no row or more than 63, an index lies outside the table, or no pair
+    reg_off[p] <= w < reg_off[p + 1] <= L holds the entry -- nothing was run for it and outer is 0.  d > 8 raises.
+    numpy arrays or CUDA tensors in, the same kind out (numpy: blocks, as every host-pointer call)."""
+    be = _Backend(A)
+    A, b, m, (Cn, mc_max, d) = _packed(be, A, b, m)
+    reg_off = be.arr(reg_off, np.int32)
+    if len(reg_off.shape) != 1 or reg_off.shape[0] < 1:
+        raise ValueError("envelope_outer_batch: reg_off must be [B + 1]")
+    B = int(reg_off.shape[0]) - 1
+    mem_idx = be.arr(mem_idx, np.int32)
+    if mem_idx is not None:
+        L = int(mem_idx.shape[0])
+    else:   # (one scalar read back with tensors: the length of the identity list)
+        L = int(reg_off[B]) if B else 0
+        if L < 0 or L > Cn:
+            raise ValueError("envelope_outer_batch: without mem_idx, reg_off must end within the member table")
+    outer, status, nlp = be.out((L,), np.uint64, zero=True), be.out((L,), np.int32, zero=True), be.out((L,), np.int32, zero=True)
+    be.call("plp_envelope_batch", Cn, mc_max, d, A, b, m, B, reg_off, L, mem_idx, float(abs_tol), outer, status, nlp,
+            h2d=(A, b, m, reg_off, mem_idx))
+    return dict(outer=outer, status=status, nlp=nlp)
+
+
 _DGESV = None
 
 

@@ -1650,4 +1650,56 @@ int plp_region_diff_batch(plp_ctx* ctx, int64_t B, int m_max, int d, const doubl
     return PLP_OK;
 }
 
+// ------------------------------------------------------------------------------- envelope: the facet tests of many regions
+static int envelope_check(plp_ctx* ctx, int64_t C, int mc_max, int d, const double* A, const double* b, int64_t B,
+                          const int32_t* reg_off, int64_t L, const void* outer, const void* status, const void* nlp) {
+    if (!ctx) return fail(PLP_EINVAL, "ctx is NULL");
+    if (C < 0 || mc_max < 0 || d < 1 || B < 0 || L < 0) return fail(PLP_EINVAL, "bad sizes");
+    if (B == 0 || L == 0) return PLP_OK;
+    if (d > 8) return fail(PLP_EUNSUPPORTED, "envelope_batch: d=%d outside the kernel (d<=8)", d);
+    if (B > 2147483647ll || L > 2147483647ll || C > 2147483647ll || (long long)C * mc_max > 2147483647ll)
+        return fail(PLP_EUNSUPPORTED, "envelope_batch: B, L or the member table exceeds 2^31 - 1");
+    if (!reg_off || !outer || !status || !nlp || (C > 0 && mc_max > 0 && (!A || !b))) return fail(PLP_EINVAL, "NULL pointer");
+    return PLP_OK;
+}
+
+int plp_envelope_batch_dev(plp_ctx* ctx, void* stream, int64_t C, int mc_max, int d, const double* A, const double* b,
+                           const int32_t* mc, int64_t B, const int32_t* reg_off, int64_t L, const int32_t* mem_idx,
+                           double abs_tol, uint64_t* outer, int32_t* status, int32_t* nlp) {
+    int rc = envelope_check(ctx, C, mc_max, d, A, b, B, reg_off, L, outer, status, nlp);
+    if (rc || B == 0 || L == 0) return rc;
+    if (plp::launch_envelope_cross(C, mc_max, d, A, b, mc, B, reg_off, L, mem_idx, abs_tol, (unsigned long long*)outer, status,
+                                   nlp, (hipStream_t)stream))
+        return fail(PLP_EUNSUPPORTED, "envelope_batch: unsupported size");
+    return check_launch("envelope_cross_kernel");
+}
+
+int plp_envelope_batch(plp_ctx* ctx, int64_t C, int mc_max, int d, const double* A, const double* b, const int32_t* mc,
+                       int64_t B, const int32_t* reg_off, int64_t L, const int32_t* mem_idx, double abs_tol, uint64_t* outer,
+                       int32_t* status, int32_t* nlp) {
+    int rc = envelope_check(ctx, C, mc_max, d, A, b, B, reg_off, L, outer, status, nlp);
+    if (rc || B == 0 || L == 0) return rc;
+    // (reg_off and mem_idx go up as they are: the kernel refuses an entry whose offsets or indices do not hold, and reads
+    // neither mem_idx beyond L nor the table beyond C members)
+    double *dA, *db;
+    int32_t *dmc, *droff, *dmidx, *dstatus, *dnlp;
+    uint64_t* douter;
+    HostCall hc(ctx);
+    hc.in(dA, A, (size_t)C * mc_max * d);
+    hc.in(db, b, (size_t)C * mc_max);
+    hc.in(dmc, mc, C);
+    hc.in(droff, reg_off, (size_t)B + 1);
+    hc.in(dmidx, mem_idx, L);
+    hc.out(douter, outer, L);
+    hc.out(dstatus, status, L);
+    hc.out(dnlp, nlp, L);
+    rc = hc.reserve();
+    if (rc) return rc;
+    rc = hc.upload();
+    if (rc) return rc;
+    rc = plp_envelope_batch_dev(ctx, hc.st, C, mc_max, d, dA, db, dmc, B, droff, L, dmidx, abs_tol, douter, dstatus, dnlp);
+    if (rc) return rc;
+    return hc.download();
+}
+
 }  // extern "C"

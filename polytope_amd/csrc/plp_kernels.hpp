@@ -74,6 +74,11 @@ int launch_rdiff_batch(long long B, int m_max, int d, const double* A, const dou
                        const double* CA, const double* Cb, const int* mc, const int* cell_off, const int* cell_idx,
                        double abs_tol, int max_lps, int p_max, int r_max, int n_max, int M_max, int* kind, int* off, int* rows,
                        int* count, int* nrows, int* nlp, int* status, int* mi, int* src, hipStream_t st);
+// The facet tests of envelope() for B regions given as index lists into a packed member table, one list entry per
+// wavefront (plp_envelope.hip; d <= 8, members of 1 .. 63 rows): outer / status / nlp[L].  2: unsupported size
+int launch_envelope_cross(long long C, int mc_max, int d, const double* A, const double* b, const int* mc, long long B,
+                          const int* reg_off, long long L, const int* mem_idx, double abs_tol, unsigned long long* outer,
+                          int* status, int* nlp, hipStream_t st);
 int launch_reduce_lds(long long B, int m_max, int d, const double* A, const double* b, const int* mrows, double abs_tol,
                       unsigned long long* keep, int* flags, double* r, double* xc, int* nlp, hipStream_t st);
 

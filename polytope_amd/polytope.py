@@ -1436,6 +1436,147 @@ def envelope(reg, abs_tol=ABS_TOL):
     return ret if is_fulldim(ret) else Polytope()
 
 
+def _envelope_batch_dim(reg, abs_tol):
+    """The dimension of a region whose facet tests the batched kernel takes, else None: the region goes through the single
+    call (another backend, abs_tol <= 0, no members, an empty member or one known to be flat, mixed dimensions, d > 8, a
+    member of more than 63 rows)."""
+    from .batch import ENV_MAX_DIM, ENV_MAX_ROWS
+    if not (_use_hip() and abs_tol > 0 and isinstance(reg, Region) and reg.list_poly):
+        return None
+    d = None
+    for p in reg.list_poly:
+        if not isinstance(p, Polytope) or p.A.ndim != 2 or p.A.size == 0 or p.fulldim is False:
+            return None
+        m, dp = p.A.shape
+        if d is None:
+            d = dp
+        if dp != d or not 1 <= d <= ENV_MAX_DIM or m > ENV_MAX_ROWS:
+            return None
+    return d
+
+
+def _envelope_stacks(regs, ks, abs_tol, info):
+    """The outer rows of the regions regs[k], k in ks (all of one dimension, all taken by the kernel), gathered in member
+    order and row order -> {k: Polytope of the stacked rows}; a region with a list entry that is not ENV_OK, or a row that
+    is not unit length, is left out (the single call's)."""
+    from .batch import envelope_outer_batch, ENV_OK
+    table, pos, mem_idx, lens = [], {}, [], []
+    for k in ks:   # every member once, however many regions (or entries) list it
+        for p in regs[k].list_poly:
+            if id(p) not in pos:
+                pos[id(p)] = len(table)
+                table.append(p)
+            mem_idx.append(pos[id(p)])
+        lens.append(len(regs[k].list_poly))
+    A, b, ms = _pack(table)
+    m_max = A.shape[1]
+    live = np.arange(m_max)[None, :] < ms[:, None]
+    unit = np.all(~live | (np.abs(np.sqrt(np.sum(A * A, 2)) - 1.0) < 1e-9), axis=1)   # (normalize=False members)
+    mem_idx = np.asarray(mem_idx, dtype=np.int32)
+    reg_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+    res = envelope_outer_batch(A, b, ms, reg_off, mem_idx, abs_tol)
+    owner = np.repeat(np.arange(len(ks)), lens)
+    bad = np.bincount(owner, weights=(res["status"] != ENV_OK) | ~unit[mem_idx], minlength=len(ks)) > 0
+    bits = ((res["outer"][:, None] >> np.arange(m_max, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(bool)
+    bits &= ~bad[owner][:, None]
+    e, r = np.nonzero(bits)   # (row-major: entries in list order, rows in row order)
+    Af, bf = A[mem_idx[e], r], b[mem_idx[e], r]
+    cut = np.concatenate([[0], np.cumsum(np.bincount(owner[e], minlength=len(ks)))])
+    if info is not None:
+        info["nlp"] += int(res["nlp"].sum())
+        info["tests"] += int(sum((n - 1) * int(ms[mem_idx[lo:lo + n]].sum()) for lo, n in zip(reg_off[:-1], lens)))
+        info["routed"] += int(bad.sum())
+    return {k: Polytope(Af[cut[q]:cut[q + 1]], bf[cut[q]:cut[q + 1]]) for q, k in enumerate(ks) if not bad[q]}
+
+
+def envelope_batch(regs, abs_tol=ABS_TOL, _info=None):
+    """[envelope(r, abs_tol) for r in regs] with the facet tests of all regions in ONE launch
+    (batch.envelope_outer_batch: one (region, member) entry per wavefront), their stacks of outer rows through one fused
+    reduce and full dimension from one batch of Chebyshev balls.  A member listed by several regions is packed once.
+    Everything the kernel does not take goes through envelope() itself and returns or raises what it does: a region with
+    a list entry that is ENV_OPEN (a test at the threshold, or one without a verdict) or ENV_UNSUPPORTED, d > 8, a member of
+    more than 63 rows, mixed dimensions, an empty member or one known to be flat, abs_tol <= 0, a backend other than 'hip'.
+    `_info` (test hook): a dict that receives nlp (LPs the kernel ran), tests (LPs of the reference's loops for the same
+    regions) and routed (regions the kernel handed back)."""
+    regs = list(regs)
+    out = [None] * len(regs)
+    info = dict(nlp=0, tests=0, routed=0)
+    groups = {}
+    for k, reg in enumerate(regs):
+        d = _envelope_batch_dim(reg, abs_tol)
+        if d is not None:
+            groups.setdefault(d, []).append(k)
+    stacks = {}
+    for d, ks in groups.items():
+        stacks.update(_envelope_stacks(regs, ks, abs_tol, info))
+    for d in groups:   # one fused reduce per dimension (as reduce() routes a single stack)
+        todo = [k for k in groups[d] if k in stacks and stacks[k].A.size > 0 and np.all(np.isfinite(stacks[k].b))
+                and _fits_reduce(stacks[k].A.shape[0], d)]
+        for k, q in zip(todo, _reduce_many([stacks[k] for k in todo], abs_tol) if todo else []):
+            out[k] = q
+    for k, stack in stacks.items():
+        if out[k] is None:
+            out[k] = reduce(stack, abs_tol=abs_tol)
+    _cheby_fill([out[k] for k in stacks if out[k].A.size > 0 and out[k].fulldim is None])
+    for k in stacks:
+        if not is_fulldim(out[k]):
+            out[k] = Polytope()
+    for k, reg in enumerate(regs):
+        if k not in stacks:
+            out[k] = envelope(reg, abs_tol)
+    if _info is not None:
+        _info.update(info)
+    return out
+
+
+def is_convex_batch(regs, abs_tol=ABS_TOL):
+    """[is_convex(r, abs_tol) for r in regs]: (True, envelope) or (False, None) per region, (True, None) for one without
+    members.  The envelopes come from envelope_batch (at the module's ABS_TOL, as is_convex builds them), the bounding
+    boxes of all members and all envelopes from one batch, and for the regions the boxes leave undecided the differences
+    envelope minus region from one region_diff_batch and the balls of all their pieces from one batch.  Between the
+    stages only the survivors go on.  What envelope_batch hands to envelope() goes through is_convex() here."""
+    regs = list(regs)
+    out = [None] * len(regs)
+    live = []
+    for k, reg in enumerate(regs):
+        if len(reg) == 0:
+            out[k] = (True, None)
+        elif _envelope_batch_dim(reg, ABS_TOL) is None or not abs_tol > 0:
+            out[k] = is_convex(reg, abs_tol)
+        else:
+            live.append(k)
+    info = {}
+    env = dict(zip(live, envelope_batch([regs[k] for k in live], _info=info))) if live else {}
+    for k in live:
+        if is_empty(env[k]):
+            out[k] = (False, None)
+    live = [k for k in live if out[k] is None]
+    # ---- the boxes: every member and every envelope that has none yet, one batch per dimension
+    need = {}
+    for k in live:
+        for p in list(regs[k].list_poly) + [env[k]]:
+            if p.bbox is None:
+                need.setdefault(p.A.shape[1], {}).setdefault(id(p), p)
+    for d, todo in need.items():
+        todo = list(todo.values())
+        for p, box in zip(todo, _bbox_raw(todo)):
+            p.bbox = box
+    for k in live:
+        Pl, Pu = regs[k].bounding_box
+        Ol, Ou = env[k].bounding_box
+        if np.any(abs(Pl - Ol) > abs_tol) or np.any(abs(Pu - Ou) > abs_tol):
+            out[k] = (False, None)
+    live = [k for k in live if out[k] is None]
+    # ---- envelope minus region, all at once; full dimension of the pieces from one batch of balls
+    if live:
+        diffs = region_diff_batch([env[k] for k in live], [regs[k] for k in live])
+        pieces = [p for D in diffs for p in (D.list_poly if isinstance(D, Region) else [D]) if p.fulldim is None]
+        _cheby_fill(pieces)
+        for k, D in zip(live, diffs):
+            out[k] = (False, None) if is_fulldim(D) else (True, env[k])
+    return out
+
+
 # ====================================================================================== difference
 def mldivide(a, b, save=False):
     r"""Set difference a \ b as a Region (ref :1470-1505)."""
