@@ -636,6 +636,55 @@ int plp_envelope_batch_dev(plp_ctx *ctx, void *stream, int64_t C, int mc_max, in
                            const int32_t *mc, int64_t B, const int32_t *reg_off, int64_t L, const int32_t *mem_idx,
                            double abs_tol, uint64_t *outer, int32_t *status, int32_t *nlp);
 
+/*
+ * The projection of B polytopes {A x <= b} in R^d onto k of their coordinates by the iterative hull (polytope.py
+ * projection_iterhull, ref :1955-2100) in one launch: one polytope per wavefront, its rows read once, every LP and every
+ * hull rebuild inside the kernel (polytope_amd/csrc/plp_projhull.hpp holds the rule as host-compilable code).
+ * In: A[B][m_max][d], b[B][m_max], m[B] (NULL = m_max; only rows below m[p] are read); keep[k]: the kept coordinates,
+ * 0-based and increasing -- k integers in HOST memory in both forms; xc[B][d]: a strictly interior point of every polytope
+ * (the Chebyshev centre).  The rule, per polytope:
+ *   box     the 2k LPs max +x_j, max -x_j over the kept j, in that order; an unbounded one ends with PLP_PH_UNBOUNDED.
+ *           Their projected points start the point list V and fix the frame: the centre c and half-extent s of the box.
+ *           Every tolerance below is absolute on (p - c) / s.
+ *   points  a new point within 1e-9 (max-norm) of one held is dropped; a 65th point: PLP_PH_OVERFLOW_POINTS.
+ *   rank    while V has fewer than k + 1 points or is flat: the LPs +nu and -nu for a unit nu orthogonal to the span of V
+ *           (Gram-Schmidt, largest residual first), the further point joins V; none further than 1e-8: PLP_PH_FLAT.
+ *   rounds  the facets of V by the rule of plp_hull_batch.  A facet equal to one confirmed in an earlier round stays
+ *           confirmed; for every other, in list order, the LP max nu . x: a value within 1e-8 of the facet's offset
+ *           confirms it, otherwise the LP's point joins V.  A round that adds no point ends with the facet list as the
+ *           answer; otherwise the facets are enumerated again.
+ *   LPs     a point that violates a row by more than 1e-9 max(1, |b - A xc|_max), or an LP without a verdict:
+ *           PLP_PH_LPFAIL; at most max_lps LPs: PLP_PH_BUDGET.
+ * Out: Ao[B][f_max][k] (unit normals), bo[B][f_max], on[B][f_max] (bit i: point i of V lies on the facet), count[B] --
+ * the rows of the projection in the caller's coordinates, NaN / 0 beyond count, written for PLP_PH_OK only (count = 0
+ * otherwise); V[B][64][k], nv[B]: the points, NaN beyond nv; X[B][64][d] or NULL: a point of the polytope above every
+ * entry of V; vmask[B]: bit i set when point i lies on at least k of the rows -- advisory: a near-duplicate tilted row
+ * can set the bit of a point inside an edge; nlp[B]; status[B]:
+ *        PLP_PH_OK, PLP_PH_UNBOUNDED, PLP_PH_FLAT, PLP_PH_OVERFLOW_POINTS, PLP_PH_OVERFLOW_FACETS (more than f_max facets),
+ *        PLP_PH_BUDGET, PLP_PH_LPFAIL, PLP_PH_NOCENTRE (no row, an entry that is not finite, or b_i - a_i . xc <= 0 for a
+ *        row: nothing was run).
+ * Caps: 1 <= k <= 3, k <= d <= 16, m_max <= 64, 1 <= f_max <= 128 (the upper-bound theorem for 64 points in R^3 gives
+ * 124), keep increasing and below d, B < 2^31: PLP_EUNSUPPORTED beyond.  B = 0: returns PLP_OK, nothing runs.
+ * The _dev form enqueues on `stream` and uses no scratch of the context.
+ */
+#define PLP_PH_OK 0
+#define PLP_PH_UNBOUNDED 1
+#define PLP_PH_FLAT 2
+#define PLP_PH_OVERFLOW_POINTS 3
+#define PLP_PH_OVERFLOW_FACETS 4
+#define PLP_PH_BUDGET 5
+#define PLP_PH_LPFAIL 6
+#define PLP_PH_NOCENTRE 7
+#define PLP_PH_MAX_POINTS 64
+int plp_project_hull_batch(plp_ctx *ctx, int64_t B, int m_max, int d, int k, const double *A, const double *b,
+                           const int32_t *m, const int32_t *keep, const double *xc, int f_max, int max_lps, double *Ao,
+                           double *bo, uint64_t *on, int32_t *count, double *V, int32_t *nv, double *X, uint64_t *vmask,
+                           int32_t *nlp, int32_t *status);
+int plp_project_hull_batch_dev(plp_ctx *ctx, void *stream, int64_t B, int m_max, int d, int k, const double *A,
+                               const double *b, const int32_t *m, const int32_t *keep, const double *xc, int f_max,
+                               int max_lps, double *Ao, double *bo, uint64_t *on, int32_t *count, double *V, int32_t *nv,
+                               double *X, uint64_t *vmask, int32_t *nlp, int32_t *status);
+
 /* cross-lane primitive self-test (group size 8/16/32/64); host out_d[128], out_u[128] */
 int plp_selftest(plp_ctx *ctx, int group_size, double *out_d, uint32_t *out_u);
 

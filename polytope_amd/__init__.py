@@ -34,7 +34,7 @@ from . import polytope, prop2partition, quickhull  # noqa: F401,E402  (submodule
 from .batch import (  # noqa: F401
     lpsolve_batch, cheby_ball_batch, bbox_batch, reduce_batch, contains_batch, assign_batch, adjacent_pairs, keep_to_bool,
     verify_careful_lps, lp_histograms, projection_batch, volume_batch, support_batch, subset_batch, extreme_batch, hull_batch,
-    volume_exact_batch, locate_batch, locate_grid,
+    volume_exact_batch, locate_batch, locate_grid, projection_hull_batch,
 )
 from .polytope import region_diff_batch  # noqa: F401,E402  (the Polytope-level call; the packed one is batch.region_diff_batch)
 from .polytope import envelope_batch, is_convex_batch  # noqa: F401,E402  (the raw launch is batch.envelope_outer_batch)

@@ -104,6 +104,10 @@ SIGNATURES = {
                                      _vp, _vp, _vp]),
     "plp_envelope_batch_dev": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int64, _vp, C.c_int64, _vp,
                                          C.c_double, _vp, _vp, _vp]),
+    "plp_project_hull_batch": (C.c_int, [_vp, C.c_int64, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int]
+                               + [_vp] * 10),
+    "plp_project_hull_batch_dev": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int,
+                                             C.c_int] + [_vp] * 10),
     "plp_quickhull_run": (C.c_int, [_vp, C.c_int64, C.c_int, _vp, _vp, C.c_double, _vp, C.POINTER(_vp)]),
     "plp_qh_result_sizes": (C.c_int, [_vp, _vp, _vp, _vp]),
     "plp_qh_result_copy": (C.c_int, [_vp, _vp, _vp, _vp]),

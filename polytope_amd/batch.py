@@ -1739,8 +1739,170 @@ def _fm_flags(fl):
     return dead
 
 
-def projection_batch(A, b, dim, m=None, abs_tol=1e-7, minrep=False):
-    """projection(P_k, dim, solver="fm") (polytope/polytope.py:1698-1769, :1911-1952) of B packed polytopes whose rows are
+# ------------------------------------------------------------ projection by the iterative hull: many polytopes in one launch
+(PH_OK, PH_UNBOUNDED, PH_FLAT, PH_OVERFLOW_POINTS, PH_OVERFLOW_FACETS, PH_BUDGET, PH_LPFAIL,
+ PH_NOCENTRE) = range(8)   # include/plp.h: PLP_PH_*
+PH_MAX_POINTS, PH_MAX_KEEP, PH_MAX_FACETS = 64, 3, 128   # the kernel's caps: points held, kept coordinates, f_max
+
+
+def _ph_fmax(k):
+    """The upper-bound theorem for 64 points in R^k, k <= 3."""
+    return 2 if k == 1 else (PH_MAX_POINTS if k == 2 else 2 * PH_MAX_POINTS - 4)
+
+
+def projection_hull_batch(A, b, dim, m=None, xc=None, f_max=None, points=False, max_lps=4096):
+    """The projections of B packed polytopes onto the coordinates `dim` (1-based and increasing, at most 3) by the
+    iterative hull in one launch (include/plp.h: plp_project_hull_batch has the rule in words): one polytope per
+    wavefront, its rows read once, every facet LP and every hull rebuild inside the kernel.  A[B, m_max, d], b[B, m_max],
+    m[B]; d <= 16, m_max <= 64 (beyond: UnsupportedSize).  xc[B, d]: a strictly interior point per polytope; None: the
+    Chebyshev centres (cheby_ball_batch runs first; a polytope whose LP does not end optimal with r > 0 gets
+    PH_NOCENTRE and the kernel runs nothing for it).  f_max None: the upper-bound theorem for 64 points.
+
+    -> dict(A[B, f_max, k] unit rows, b[B, f_max], on uint64[B, f_max], m[B]: the rows of the projection (NaN / 0 beyond m;
+            written for PH_OK only), V[B, 64, k], nv[B]: the points the hull was built from, X[B, 64, d] (points=True): a
+            point of the polytope above each of them, vmask uint64[B]: bit i set when point i lies on at least k rows
+            (advisory: a near-duplicate tilted row can set the bit of a point inside an edge), nlp[B], status[B] (PH_*)).
+    numpy arrays or CUDA tensors in, the same kind out (tensors: on torch's current stream; uint64 as the same bits in
+    int64)."""
+    be = _Backend(A)
+    A, b, m, (B, m_max, d) = _packed(be, A, b, m)
+    keep = np.ascontiguousarray(np.asarray(dim, dtype=np.int64).ravel() - 1, dtype=np.int32)
+    k = int(keep.size)
+    if k < 1 or np.any(keep < 0) or np.any(keep >= d) or np.any(np.diff(keep) <= 0):
+        raise ValueError("projection_hull_batch: dim must be increasing coordinates within 1 .. d")
+    f_max = _ph_fmax(min(k, PH_MAX_KEEP)) if f_max is None else int(f_max)
+    if f_max < 1 or int(max_lps) < 0:
+        raise ValueError("projection_hull_batch: f_max must be at least 1 and max_lps at least 0")
+    if xc is None and B:
+        if be.torch is None and m is not None:
+            # (the host-pointer ball checks its whole input for inf / nan; what lies beyond m[p] is nobody's to read)
+            used = np.arange(m_max)[None, :] < m[:, None]
+            ball = cheby_ball_batch(np.where(used[:, :, None], A, 0.0), np.where(used, b, 0.0), m)
+        else:
+            ball = cheby_ball_batch(A, b, m)
+        if be.torch is not None:
+            usable = (ball["status"] == 0) & (ball["r"] > 0)
+            xc = be.torch.where(usable[:, None], ball["xc"], be.torch.full((), float("nan"), dtype=ball["xc"].dtype,
+                                                                          device=be.device))
+        else:
+            with np.errstate(invalid="ignore"):
+                usable = (ball["status"] == 0) & (ball["r"] > 0)
+            xc = np.where(usable[:, None], ball["xc"], np.nan)
+    xc = be.arr(xc, shape=(B, d)) if xc is not None else be.out((B, d), zero=True)
+    Ao, bo = be.out((B, f_max, k), zero=True), be.out((B, f_max), zero=True)
+    on, count = be.out((B, f_max), np.uint64, zero=True), be.out((B,), np.int32, zero=True)
+    V, nv = be.out((B, PH_MAX_POINTS, k), zero=True), be.out((B,), np.int32, zero=True)
+    X = be.out((B, PH_MAX_POINTS, d), zero=True) if points else None
+    vmask, nlp, status = be.out((B,), np.uint64, zero=True), be.out((B,), np.int32, zero=True), be.out((B,), np.int32, zero=True)
+    be.call("plp_project_hull_batch", B, m_max, d, k, A, b, m, _HostStruct((C.c_int32 * k)(*[int(v) for v in keep])), xc,
+            f_max, int(max_lps), Ao, bo, on, count, V, nv, X, vmask, nlp, status, h2d=(A, b, m, xc))
+    res = dict(A=Ao, b=bo, on=on, m=count, V=V, nv=nv, vmask=vmask, nlp=nlp, status=status)
+    if points:
+        res["X"] = X
+    return res
+
+
+def _projection_hull(torch, A2, b2, mt, go, live, new_dim, abs_tol, outs, routed):
+    """The iterative-hull solver of projection_batch for the polytopes live[go]: the centre, the kernel, the rows through
+    one reduce_batch (as the reference's qhull() reduces); whatever the kernel does not settle -- every PH_* but
+    PH_UNBOUNDED, a shape beyond its caps, a reduce without a verdict -- goes through projection(..., solver="iterhull")
+    into `outs`.  -> the settled polytopes as one block, or None."""
+    from . import polytope as _poly
+    gi = torch.as_tensor(go, device=A2.device)
+    Ag, bg, mg = A2.index_select(0, gi), b2.index_select(0, gi), mt.index_select(0, gi)
+    n, rows, d = Ag.shape
+    k = len(new_dim)
+    order = np.argsort(new_dim, kind="stable")
+    back = np.argsort(order, kind="stable")   # column j of the answer is sorted column back[j]
+    m_h = mg.cpu().numpy()
+    st = np.full(n, PH_LPFAIL, np.int32)
+    block = None   # (positions within go, A, b, m) of the polytopes settled here, as _fm_batch returns its last step
+    if 1 <= k <= PH_MAX_KEEP and d <= MAX_D and rows <= MAX_M and np.all(np.diff(new_dim[order]) > 0):
+        res = projection_hull_batch(Ag, bg, new_dim[order] + 1, m=mg)
+        st = res["status"].cpu().numpy()
+        cnt = res["m"].cpu().numpy()
+        ok = np.nonzero(st == PH_OK)[0]
+        if ok.size:
+            cmax = int(cnt[ok].max())
+            oi = torch.as_tensor(ok, device=A2.device)
+            RA = torch.nan_to_num(res["A"].index_select(0, oi)[:, :cmax]).contiguous()
+            Rb = torch.nan_to_num(res["b"].index_select(0, oi)[:, :cmax]).contiguous()
+            red = reduce_batch(RA, Rb, m=torch.as_tensor(cnt[ok], device=A2.device), abs_tol=_REDUCE_TOL)
+            masks = keep_to_bool(red["keep"].cpu().numpy(), cmax) & (np.arange(cmax)[None, :] < cnt[ok][:, None])
+            flags = red["flags"].cpu().numpy()
+            RA_h, Rb_h = RA.cpu().numpy(), Rb.cpu().numpy()
+            # (32: PLP_RF_F1OPEN) a reduce without a verdict: the single call
+            st[ok[(flags & (_lib.RF_LPFAIL | _lib.RF_EMPTY | 32)) != 0]] = PH_LPFAIL
+            # the kept rows of every polytope to the front, in their order; the answers of all settled polytopes as one block
+            front = np.argsort(~masks, axis=1, kind="stable")
+            RA_h = np.take_along_axis(RA_h, front[:, :, None], 1)[:, :, back]
+            Rb_h = np.take_along_axis(Rb_h, front, 1)
+            trip = (flags & _lib.RF_MINREP) != 0   # the h[k] += 0.1; h[k] -= 0.1 round trip of ref :1149-1151
+            Rb_h[trip] = (Rb_h[trip] + 0.1) - 0.1
+            mk = masks.sum(1).astype(np.int32)
+            pad = np.arange(cmax)[None, :] >= mk[:, None]
+            RA_h[pad], Rb_h[pad] = 0.0, 0.0
+            sel = st[ok] == PH_OK
+            w = max(int(mk[sel].max()) if sel.any() else 0, 1)
+            block = (ok[sel], RA_h[sel][:, :w], Rb_h[sel][:, :w], mk[sel])
+    Ag_h = bg_h = None
+    for t in np.nonzero(st != PH_OK)[0]:
+        kk = int(live[go[t]])
+        if st[t] == PH_UNBOUNDED:
+            outs[kk] = (PROJ_LPFAIL, None, None, False)
+            continue
+        if Ag_h is None:
+            Ag_h, bg_h = Ag.cpu().numpy(), bg.cpu().numpy()
+        routed[0] += 1
+        try:
+            q = _poly.projection(_poly.Polytope(Ag_h[t, :m_h[t]].copy(), bg_h[t, :m_h[t]].copy(), normalize=False),
+                                 new_dim + 1, solver="iterhull", abs_tol=abs_tol)
+        except Exception:   # (the reference's iterhull raises plain Exception for an LP it cannot use)
+            outs[kk] = (PROJ_LPFAIL, None, None, False)
+            continue
+        outs[kk] = (PROJ_OK, q.A, q.b, q.minrep) if q.A.size > 0 else (PROJ_EMPTY, None, None, False)
+    return block
+
+
+def _projection_exists(torch, At, bt, m_h, live, del_dim, abs_tol, dev, status, t_exists):
+    """The part of projection() in front of its solvers, for the polytopes `live` of a packed batch: the zero rows of a
+    polytope with fewer rows than dimensions and the existence LP.  Marks PROJ_EMPTY in `status` and -> A2, b2, mt (the
+    rows of the live polytopes as the solvers take them) and `go`: the positions within `live` that go on.  Shared by
+    both solvers of projection_batch."""
+    B, m_max, d = At.shape
+    # fewer rows than dimensions: zero rows up to d (ref :1748-1755)
+    rows = max(m_max, d)
+    li = torch.as_tensor(live, device=dev)
+    A2 = torch.zeros((live.size, rows, d), dtype=torch.float64, device=dev)
+    b2 = torch.zeros((live.size, rows), dtype=torch.float64, device=dev)
+    A2[:, :m_max] = At.index_select(0, li)
+    b2[:, :m_max] = bt.index_select(0, li)
+    m2 = np.maximum(m_h[live], d)
+    short = np.nonzero(m_h[live] < d)[0]
+    if short.size:
+        r = torch.arange(rows, device=dev)[None, :] >= torch.as_tensor(m_h[live][short], device=dev)[:, None]
+        st_ = torch.as_tensor(short, device=dev)
+        A2[st_] = torch.where(r[:, :, None], torch.zeros((), dtype=torch.float64, device=dev), A2[st_])
+        b2[st_] = torch.where(r, torch.zeros((), dtype=torch.float64, device=dev), b2[st_])
+    mt = torch.as_tensor(m2.astype(np.int32), device=dev)
+    # does the projection exist: the Chebyshev-style LP with the reference's norm (squared, and zeroed on the ROWS
+    # del_dim: ref :1757-1766)
+    norm = (A2 * A2).sum(2)
+    norm[:, torch.as_tensor(del_dim, device=dev)] = 0
+    c = torch.zeros((live.size, d + 1), dtype=torch.float64, device=dev)
+    c[:, d] = -1
+    sol = lpsolve_batch(c, torch.cat([A2, norm[:, :, None]], 2).contiguous(), b2, m=mt)
+    lp_st = sol["status"].cpu().numpy()
+    r_h = sol["x"][:, d].cpu().numpy()
+    fm_stats["steps"].append(dict(step="exists", launches=1, d2h=12 * live.size, t=t_exists))
+    empty = (lp_st != 0) | ~(r_h >= abs_tol)
+    status[live[empty]] = PROJ_EMPTY
+    go = np.nonzero(~empty)[0]
+    return A2, b2, mt, go
+
+
+def projection_batch(A, b, dim, m=None, abs_tol=1e-7, minrep=False, solver="fm"):
+    """projection(P_k, dim, solver=solver) (polytope/polytope.py:1698-1769, :1911-1952) of B packed polytopes whose rows are
     what Polytope(...).A / .b hold.  A[B, m_max, d], b[B, m_max], m[B] as numpy arrays or CUDA tensors; `dim`: the
     coordinates kept, 1-based, as the reference takes them; minrep: the inputs are minimal representations (no first
     reduce).
@@ -1753,9 +1915,19 @@ def projection_batch(A, b, dim, m=None, abs_tol=1e-7, minrep=False):
     the fused reduce takes and went on through the host's reduce(); `reexamined`: polytopes the fused reduce handed to
     the verified Chebyshev LP (RF_F1OPEN), which went on on the host likewise.  Numpy in, numpy out; tensors in, tensors
     out (on A's device).
+
+    solver: "fm" (the default: Fourier-Motzkin, everything above); "iterhull": the iterative hull in one launch
+    (projection_hull_batch) behind the same existence LP, its rows through one reduce_batch as the reference's qhull()
+    reduces them -- the same keys and status codes, 4 also where the projection is unbounded (the reference's iterhull
+    has no answer there); `routed` then counts the polytopes the kernel did not settle (more than 64 points, a flat
+    projection, an LP without a verdict, a shape beyond its caps), which went through projection(..., solver="iterhull");
+    None: the reference's choice for the whole call -- fm for at most two deleted coordinates, otherwise the hull.  Any
+    other name raises ValueError.
     """
     import torch
     from . import polytope as _poly
+    if solver not in ("fm", "iterhull", None):
+        raise ValueError('projection_batch: solver must be "fm", "iterhull" or None, not %r' % (solver,))
     numpy_in = not _is_torch(A)
     if numpy_in:
         dev = torch.device("cuda", torch.cuda.current_device())
@@ -1782,34 +1954,10 @@ def projection_batch(A, b, dim, m=None, abs_tol=1e-7, minrep=False):
     live = np.nonzero(m_h > 0)[0] if d >= len(dim) else np.zeros(0, np.int64)
     block = None
     if live.size:
-        # fewer rows than dimensions: zero rows up to d (ref :1748-1755)
-        rows = max(m_max, d)
-        li = torch.as_tensor(live, device=dev)
-        A2 = torch.zeros((live.size, rows, d), dtype=torch.float64, device=dev)
-        b2 = torch.zeros((live.size, rows), dtype=torch.float64, device=dev)
-        A2[:, :m_max] = At.index_select(0, li)
-        b2[:, :m_max] = bt.index_select(0, li)
-        m2 = np.maximum(m_h[live], d)
-        short = np.nonzero(m_h[live] < d)[0]
-        if short.size:
-            r = torch.arange(rows, device=dev)[None, :] >= torch.as_tensor(m_h[live][short], device=dev)[:, None]
-            st_ = torch.as_tensor(short, device=dev)
-            A2[st_] = torch.where(r[:, :, None], torch.zeros((), dtype=torch.float64, device=dev), A2[st_])
-            b2[st_] = torch.where(r, torch.zeros((), dtype=torch.float64, device=dev), b2[st_])
-        mt = torch.as_tensor(m2.astype(np.int32), device=dev)
-        # does the projection exist: the Chebyshev-style LP with the reference's norm (squared, and zeroed on the ROWS
-        # del_dim: ref :1757-1766)
-        norm = (A2 * A2).sum(2)
-        norm[:, torch.as_tensor(del_dim, device=dev)] = 0
-        c = torch.zeros((live.size, d + 1), dtype=torch.float64, device=dev)
-        c[:, d] = -1
-        sol = lpsolve_batch(c, torch.cat([A2, norm[:, :, None]], 2).contiguous(), b2, m=mt)
-        lp_st = sol["status"].cpu().numpy()
-        r_h = sol["x"][:, d].cpu().numpy()
-        fm_stats["steps"].append(dict(step="exists", launches=1, d2h=12 * live.size, t=t_exists))
-        empty = (lp_st != 0) | ~(r_h >= abs_tol)
-        status[live[empty]] = PROJ_EMPTY
-        go = np.nonzero(~empty)[0]
+        A2, b2, mt, go = _projection_exists(torch, At, bt, m_h, live, del_dim, abs_tol, dev, status, t_exists)
+        hull = solver == "iterhull" or (solver is None and len(del_dim) > 2)
+        if hull and go.size:
+            block = _projection_hull(torch, A2, b2, mt, go, live, new_dim, abs_tol, outs, routed)
         cols = [int(i) for i in -np.sort(-del_dim)]
 
         def on_host(k, poly, cols_left, first):
@@ -1827,7 +1975,7 @@ def projection_batch(A, b, dim, m=None, abs_tol=1e-7, minrep=False):
                 outs[kk] = (PROJ_LPFAIL, None, None, False)
                 return
             outs[kk] = (PROJ_OK, q.A, q.b, q.minrep) if q.A.size > 0 else (PROJ_EMPTY, None, None, False)
-        if go.size:
+        if go.size and not hull:
             gi = torch.as_tensor(go, device=dev)
             res = _fm_batch(A2.index_select(0, gi), b2.index_select(0, gi), mt.index_select(0, gi), cols, _REDUCE_TOL,
                             np.full(go.size, bool(minrep)), on_host, fm_stats["steps"])

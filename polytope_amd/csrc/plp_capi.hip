@@ -1702,4 +1702,73 @@ int plp_envelope_batch(plp_ctx* ctx, int64_t C, int mc_max, int d, const double*
     return hc.download();
 }
 
+// ------------------------------------------------------------------ projection by the iterative hull, one launch for B polytopes
+static int projhull_check(plp_ctx* ctx, int64_t B, int m_max, int d, int k, const double* A, const double* b,
+                          const int32_t* keep, const double* xc, int f_max, int max_lps, const void* Ao, const void* bo,
+                          const void* on, const void* count, const void* V, const void* nv, const void* vmask, const void* nlp,
+                          const void* status) {
+    if (!ctx) return fail(PLP_EINVAL, "ctx is NULL");
+    if (B < 0 || m_max < 0 || d < 1 || k < 1 || f_max < 1 || max_lps < 0) return fail(PLP_EINVAL, "bad sizes");
+    if (B == 0) return PLP_OK;
+    if (k > 3 || d < k || d > 16 || m_max > 64 || f_max > 128)
+        return fail(PLP_EUNSUPPORTED, "project_hull_batch: m_max=%d d=%d k=%d f_max=%d outside the kernel (m<=64, k<=d<=16, k<=3, f_max<=128)",
+                    m_max, d, k, f_max);
+    if (B > 2147483647ll) return fail(PLP_EUNSUPPORTED, "project_hull_batch: B exceeds 2^31 - 1");
+    if (!keep || !xc || !Ao || !bo || !on || !count || !V || !nv || !vmask || !nlp || !status || (m_max > 0 && (!A || !b)))
+        return fail(PLP_EINVAL, "NULL pointer");
+    for (int t = 0; t < k; ++t)
+        if (keep[t] < 0 || keep[t] >= d || (t && keep[t] <= keep[t - 1]))
+            return fail(PLP_EUNSUPPORTED, "project_hull_batch: keep must be increasing and inside 0 .. d - 1");
+    return PLP_OK;
+}
+
+int plp_project_hull_batch_dev(plp_ctx* ctx, void* stream, int64_t B, int m_max, int d, int k, const double* A, const double* b,
+                               const int32_t* m, const int32_t* keep, const double* xc, int f_max, int max_lps, double* Ao,
+                               double* bo, uint64_t* on, int32_t* count, double* V, int32_t* nv, double* X, uint64_t* vmask,
+                               int32_t* nlp, int32_t* status) {
+    int rc = projhull_check(ctx, B, m_max, d, k, A, b, keep, xc, f_max, max_lps, Ao, bo, on, count, V, nv, vmask, nlp, status);
+    if (rc || B == 0) return rc;
+    if (plp::launch_projhull(B, m_max, d, k, A, b, m, keep, xc, f_max, max_lps, Ao, bo, (unsigned long long*)on, count, V, nv, X,
+                             (unsigned long long*)vmask, nlp, status, (hipStream_t)stream))
+        return fail(PLP_EUNSUPPORTED, "project_hull_batch: unsupported size");
+    return check_launch("projhull_kernel");
+}
+
+int plp_project_hull_batch(plp_ctx* ctx, int64_t B, int m_max, int d, int k, const double* A, const double* b, const int32_t* m,
+                           const int32_t* keep, const double* xc, int f_max, int max_lps, double* Ao, double* bo, uint64_t* on,
+                           int32_t* count, double* V, int32_t* nv, double* X, uint64_t* vmask, int32_t* nlp, int32_t* status) {
+    int rc = projhull_check(ctx, B, m_max, d, k, A, b, keep, xc, f_max, max_lps, Ao, bo, on, count, V, nv, vmask, nlp, status);
+    if (rc || B == 0) return rc;
+    double *dA, *db, *dxc, *dAo, *dbo, *dV, *dX = nullptr;
+    int32_t *dm, *dhead;
+    uint64_t *don, *dvmask;
+    std::vector<int32_t> head((size_t)4 * B);   // count | nv | nlp | status: one copy back
+    HostCall hc(ctx);
+    hc.in(dA, A, (size_t)B * m_max * d);
+    hc.in(db, b, (size_t)B * m_max);
+    hc.in(dm, m, B);
+    hc.in(dxc, xc, (size_t)B * d);
+    hc.out(dAo, Ao, (size_t)B * f_max * k);
+    hc.out(dbo, bo, (size_t)B * f_max);
+    hc.out(don, on, (size_t)B * f_max);
+    hc.out(dV, V, (size_t)B * PLP_PH_MAX_POINTS * k);
+    if (X) hc.out(dX, X, (size_t)B * PLP_PH_MAX_POINTS * d);
+    hc.out(dvmask, vmask, B);
+    hc.out(dhead, head.data(), (size_t)4 * B);
+    rc = hc.reserve();
+    if (rc) return rc;
+    rc = hc.upload();
+    if (rc) return rc;
+    rc = plp_project_hull_batch_dev(ctx, hc.st, B, m_max, d, k, dA, db, dm, keep, dxc, f_max, max_lps, dAo, dbo, don, dhead, dV,
+                                    dhead + B, dX, dvmask, dhead + 2 * B, dhead + 3 * B);
+    if (rc) return rc;
+    rc = hc.download();
+    if (rc) return rc;
+    memcpy(count, head.data(), (size_t)B * 4);
+    memcpy(nv, head.data() + B, (size_t)B * 4);
+    memcpy(nlp, head.data() + 2 * B, (size_t)B * 4);
+    memcpy(status, head.data() + 3 * B, (size_t)B * 4);
+    return PLP_OK;
+}
+
 }  // extern "C"

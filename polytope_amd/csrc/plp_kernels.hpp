@@ -79,6 +79,12 @@ int launch_rdiff_batch(long long B, int m_max, int d, const double* A, const dou
 int launch_envelope_cross(long long C, int mc_max, int d, const double* A, const double* b, const int* mc, long long B,
                           const int* reg_off, long long L, const int* mem_idx, double abs_tol, unsigned long long* outer,
                           int* status, int* nlp, hipStream_t st);
+// The iterative-hull projection of B polytopes onto k of their coordinates, one polytope per wavefront (plp_projhull.hip;
+// k <= 3, d <= 16, m_max <= 64, f_max <= 128): keep[k] HOST integers; Ao[B][f_max][k], bo / on[B][f_max], count[B],
+// V[B][64][k], nv[B], X[B][64][d] (or nullptr), vmask / nlp / status[B].  2: unsupported size
+int launch_projhull(long long B, int m_max, int d, int k, const double* A, const double* b, const int* mrows, const int* keep,
+                    const double* xc, int f_max, int max_lps, double* Ao, double* bo, unsigned long long* on, int* count, double* V,
+                    int* nv, double* X, unsigned long long* vmask, int* nlp, int* status, hipStream_t st);
 int launch_reduce_lds(long long B, int m_max, int d, const double* A, const double* b, const int* mrows, double abs_tol,
                       unsigned long long* keep, int* flags, double* r, double* xc, int* nlp, hipStream_t st);
 

@@ -354,5 +354,36 @@ __device__ __forceinline__ int solve_dense(const int lane, const int nrows, cons
     return st;
 }
 
+// solve_dense with the optimal point as well: y[k] is read from the lane whose row holds structural k (rowvar == k, the
+// sign by rowneg, as cheby_radius_rows reads r); a structural that ended nonbasic is 0.  y is wave-uniform and means
+// something for ST_OPT only.  (A sibling, not a flag of solve_dense: its callers keep their code.)
+template <int D>
+__device__ __forceinline__ int solve_dense_point(const int lane, const int nrows, const double* __restrict__ rowsA, const double cj,
+                                                 const double beta0, const bool act, double& negz, WideShared<D>& sh,
+                                                 double (&y)[D]) {
+    typename RowVec<D>::type Tv = (typename RowVec<D>::type)(0.0);
+    double T16 = 0.0;
+#pragma unroll
+    for (int kk = 0; kk < D; ++kk) ROW_SET(kk, rowsA[lane * D + kk]);
+    double beta = beta0;
+    int rowvar = D + lane, rowneg = 0, iters = 0;
+    bool rowact = act;
+    wave_sync();  // (the last LP's reads of the block are done)
+    if (lane <= D) {
+        sh.cost[lane] = lane < D ? cj : 0.0;
+        sh.cv[lane] = (lane + 1) << 1;
+    }
+    wave_sync();
+    negz = 0.0;
+    const int st = wide_run<D>(lane, nrows, Tv, T16, beta, rowvar, rowneg, rowact, sh, D, false, 0.0, iters, &negz);
+    const double mine = rowneg ? -beta : beta;
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+        const uint64_t ob = __ballot(rowvar == k);
+        y[k] = ob ? uniform_lane(mine, __ffsll((long long)ob) - 1) : 0.0;
+    }
+    return st;
+}
+
 }  // namespace wide
 }  // namespace plp

@@ -48,6 +48,40 @@ def containment_workload(P, N, d=6, m=16, seed=0, stream=0):
     return np.ascontiguousarray(A), np.ascontiguousarray(b), np.ascontiguousarray(X)
 
 
+def horizon_polytopes(B, n, k, N, mt, seed=0, stream=0):
+    """B polytopes shaped like the pre-image step of a horizon-N reachability problem: the variables are a state x_0 in
+    R^n and N inputs u_0 .. u_{N-1} in R^k (d = n + k N), with x_{t+1} = F x_t + G u_t for a random F (entries N(0, 0.4))
+    and G (N(0, 1)) per polytope.  Rows: the state box |x_0| <= 1, the input boxes |u_t| <= 1, the intermediate state boxes
+    |x_t| <= 2 for t = 1 .. N - 1, and mt random unit target rows on x_N tangent to spheres of radius 0.5 .. 1.5: unit rows
+    A[B, m, d], b[B, m] with m = 2 n N + 2 k N + mt.  The origin is strictly inside; projecting onto the states is
+    dim = 1 .. n."""
+    rng = _rng(seed, stream)
+    d = n + k * N
+    A_all, b_all = [], []
+    for _ in range(B):
+        F, G = 0.4 * rng.standard_normal((n, n)), rng.standard_normal((n, k))
+        rows, rhs = [], []
+        M = np.hstack([np.eye(n), np.zeros((n, k * N))])   # x_t = M z
+        for t in range(N):
+            box = np.vstack([M, -M])
+            rows.append(box)
+            rhs.append(np.full(2 * n, 1.0 if t == 0 else 2.0))
+            U = np.zeros((k, d))
+            U[:, n + k * t:n + k * (t + 1)] = np.eye(k)
+            rows.append(np.vstack([U, -U]))
+            rhs.append(np.ones(2 * k))
+            M = F @ M + G @ U
+        T = rng.standard_normal((mt, n))
+        T /= np.sqrt(np.sum(T * T, axis=1, keepdims=True))
+        rows.append(T @ M)
+        rhs.append(rng.uniform(0.5, 1.5, mt))
+        A, b = np.vstack(rows), np.concatenate(rhs)
+        nrm = np.sqrt(np.sum(A * A, axis=1))
+        A_all.append(A / nrm[:, None])
+        b_all.append(b / nrm)
+    return np.ascontiguousarray(np.array(A_all)), np.ascontiguousarray(np.array(b_all))
+
+
 def quickhull_workload(N, d=8, F=9, seed=0, stream=0):
     """Config C5: N points U[0,1)^d (rows) and F facets.  The first d+1 facets are those of a
     random start simplex (centred at the origin, outward unit normals); further facets are
