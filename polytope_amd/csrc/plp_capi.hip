@@ -1500,7 +1500,7 @@ int plp_selftest(plp_ctx* ctx, int group_size, double* out_d, uint32_t* out_u) {
 // ------------------------------------------------------------------------------- region_diff search
 }  // extern "C"
 
-// The search is host code of its own (plp_rdiff_search.hpp: state, moves, radius memo, speculation); its batches of LPs
+// The search is host code of its own (plp_rdiff_search.hpp: the walk, radius memo, speculation); its batches of LPs
 // are solved by the device backend (plp_rdiff_host.hpp: resident LP server or a launch per batch).
 #include "plp_rdiff_host.hpp"
 

@@ -3,9 +3,9 @@
 // -ffp-contract=off, tests/cabi/rdiff_batch_host.cpp) and for the device, where ONE lane runs it on a State in LDS and the
 // wavefront solves the Chebyshev LP it asks for:
 //   the table build of region_diff (polytope.py:1726-1741, ref :2166-2183) on rows that are unit length already, and
-//   the search of plp_rdiff_search.hpp (State, next_sibling, reopen_after_piece, resolve, the run / scan / node loop)
-//   restated on fixed arrays, without memo or speculation: step() runs the walk up to the next radius it has to read,
-//   returns, and is called again with that radius.
+//   the walk of plp_rdiff_walk.hpp (the table's shape, the moves, the verdicts of a scan and a node: the same code the
+//   library search of plp_rdiff_search.hpp runs) on a State of fixed arrays, without memo or speculation: step() runs it
+//   up to the next radius it has to read, returns, and is called again with that radius.
 // It differs from the library search only in WHICH radii are read: a scan stops at its first hit, so a frame knows fewer
 // dead cells than the library's (which solves every cell of a scan) and some LPs the library skips are issued.  The
 // verdicts, and with them the pieces, are the same.
@@ -14,7 +14,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include "plp_enum.hpp"
+#include "plp_rdiff_walk.hpp"
 
 namespace plp {
 namespace rdb {
@@ -55,11 +55,12 @@ struct Out {
     int p_max, r_max;
 };
 
+// Table and state of the walk in one
 struct State {
     // ---- the table's shape: m rows of the minuend, M new rows (cell j from beg[j], mi[j] of them), their M negations
     int m, N, M, nrows;
     int mi[MAX_CELLS], beg[MAX_CELLS];
-    // ---- the walk (plp::rdiff::State): counter, the reference's INDICES, the open cells as a mask
+    // ---- the walk: counter, the reference's INDICES, the open cells as a mask
     int counter[MAX_CELLS];
     unsigned long long open;
     long long idx[IDX_CAP];
@@ -80,19 +81,12 @@ struct State {
     int count, nout, nlp, status, over;
 };
 
-PLP_ENUM_FN int at(const State& s, const long long level) { return (int)(level < 0 ? level + s.N : level); }
 PLP_ENUM_FN unsigned long long cells_from(const int from) { return from >= 64 ? 0ull : ~0ull << from; }
 
-// m, N, mi[] are set: beg, M, nrows and the start of the walk.  (The caller has checked the caps.)
+// m, N, mi[] are set: the table's shape and the start of the walk.  (The caller has checked the caps.)
 PLP_ENUM_FN void init(State& s) {
-    int M = 0;
-    for (int j = 0; j < s.N; ++j) {
-        s.beg[j] = s.m + M;
-        M += s.mi[j];
-        s.counter[j] = 0;
-    }
-    s.M = M;
-    s.nrows = s.m + 2 * M;
+    for (int j = 0; j < s.N; ++j) s.counter[j] = 0;
+    rdw::set_shape(s);
     s.open = 0ull;
     for (int i = 0; i < s.m; ++i) s.idx[i] = i;
     s.nidx = s.m;
@@ -111,68 +105,31 @@ PLP_ENUM_FN void init(State& s) {
     s.status = RD_OK;
 }
 
-PLP_ENUM_FN void set_counter(State& s, const int L, const int v) {
-    s.sumc += v - s.counter[L];
-    s.counter[L] = v;
-    if (v != 0) s.open |= 1ull << L;
-    else s.open &= ~(1ull << L);
+// ---- the moves are those of plp_rdiff_walk.hpp; what they reach the table and the storage through
+using rdw::set_counter, rdw::next_sibling, rdw::reopen_after_piece;
+PLP_ENUM_FN const State& table_of(const State& s) { return s; }
+PLP_ENUM_FN void last_minus(State& s, const long long M) {
+    if (s.nidx < 1) s.bad = 1;
+    else if (s.nidx <= IDX_CAP) s.idx[s.nidx - 1] -= M;
 }
 PLP_ENUM_FN void push(State& s, const long long v) {
     if (s.nidx < IDX_CAP) s.idx[s.nidx] = v;
     ++s.nidx;
 }
-PLP_ENUM_FN void last_minus_M(State& s) {
-    if (s.nidx < 1) s.bad = 1;
-    else if (s.nidx <= IDX_CAP) s.idx[s.nidx - 1] -= s.M;
+PLP_ENUM_FN void keep_first(State& s, const long long n) {
+    if ((long long)s.nidx > n) s.nidx = (int)n;
 }
-// close cell L and drop the rows beyond the m + sumc the reference keeps
-PLP_ENUM_FN void close_cell(State& s, const int L) {
-    set_counter(s, L, 0);
-    const long long keep_n = s.m + s.sumc;
-    if ((long long)s.nidx > keep_n) s.nidx = (int)(keep_n < 0 ? 0 : keep_n);
+PLP_ENUM_FN int deepest_open(const State& s) { return 63 - __builtin_clzll(s.open); }
+PLP_ENUM_FN int n_open(const State& s) { return __builtin_popcountll(s.open); }
+// (whatever the bit was: setting it again costs less than a branch, 1 % of the 1 000-problem shape of 4.17)
+PLP_ENUM_FN void mark_open(State& s, const int L, const bool, const bool on) {
+    s.open = on ? s.open | 1ull << L : s.open & ~(1ull << L);
 }
-// next sibling of the deepest open cell, closing exhausted cells on the way (ref :2246-2271); true: the search ends
-PLP_ENUM_FN bool next_sibling(State& s) {
-    while (s.open) {
-        const int L = 63 - __builtin_clzll(s.open);
-        s.level = L;
-        set_counter(s, L, s.counter[L] + 1);
-        if (s.counter[L] <= s.mi[L]) {
-            last_minus_M(s);
-            push(s, (long long)s.beg[L] + s.counter[L] + s.M - 1);
-            return false;
-        }
-        close_cell(s, L);
-        s.level = s.level - 1;
-        if (s.level == -1) return true;
-    }
-    return false;
-}
-// the move after a piece was emitted (ref :2230-2245); true: the search ends
-PLP_ENUM_FN bool reopen_after_piece(State& s) {
-    s.level = s.level - 1;
-    const int nz = __builtin_popcountll(s.open);
-    for (int k = 0; k < nz; ++k) {
-        const int L = at(s, s.level);
-        if (s.counter[L] <= s.mi[L]) {
-            last_minus_M(s);
-            push(s, (long long)s.beg[L] + s.counter[L] + s.M);
-            return false;
-        }
-        close_cell(s, L);
-        if (s.level == -1) return true;
-    }
-    return false;
-}
-// idx -> cur, with Python's wrap of an index below zero.  RD_OK, RD_LONG, or RD_INDEX: one is out of range
+// idx -> cur.  RD_OK, RD_LONG, or RD_INDEX: an index is out of range, or a move found the list empty
 PLP_ENUM_FN int resolve(State& s) {
     if (s.bad) return RD_INDEX;
     if (s.nidx > MAX_LIST) return RD_LONG;
-    for (int k = 0; k < s.nidx; ++k) {
-        const long long r = s.idx[k] < 0 ? s.idx[k] + s.nrows : s.idx[k];
-        if (r < 0 || r >= s.nrows) return RD_INDEX;
-        s.cur[k] = (int)r;
-    }
+    if (!rdw::rows_of(s, s.idx, s.nidx, s.cur)) return RD_INDEX;
     s.ncur = s.nidx;
     return RD_OK;
 }
@@ -226,7 +183,7 @@ PLP_ENUM_FN int step(State& s, const Out& o, const double tol, const int max_lps
                     emit(s, o, 0);
                     return finish(s, RD_OK);
                 }
-                if (s.counter[at(s, s.level)] != 0) {
+                if (s.counter[rdw::at(s, s.level)] != 0) {
                     if (next_sibling(s)) return finish(s, RD_OK);
                     s.phase = PH_NODE_REQUEST;
                     break;
@@ -269,15 +226,8 @@ PLP_ENUM_FN int step(State& s, const Out& o, const double tol, const int max_lps
             }
             case PH_SCAN_RESULT: {
                 const int j = s.scan_j;
-                // only a cell SOLVED with a radius <= tol / 2 is dead below this node (NaN compares false)
-                if (R <= 0.5 * tol) s.fr_alive &= ~(1ull << j);
-                const double Rj = R != R ? 0.0 : R;
-                if (Rj > tol) {
-                    s.hit = j;
-                    s.Rl = Rj;
-                } else if (j == s.N - 1) {
-                    s.Rl = Rj;
-                }
+                if (rdw::scan_dead(R, tol)) s.fr_alive &= ~(1ull << j);
+                rdw::scan_read(R, tol, j, s.N, s.hit, s.Rl);
                 s.scan_todo &= cells_from(j + 1);
                 if (s.hit < 0 && s.scan_todo) return ask_scan_cell(s, max_lps);
                 s.phase = PH_SCAN_FINISH;
@@ -293,7 +243,7 @@ PLP_ENUM_FN int step(State& s, const Out& o, const double tol, const int max_lps
                     set_counter(s, (int)s.hit, 1);
                     push(s, (long long)s.beg[s.hit] + s.M);
                 }
-                if (s.Rl < tol) {   // nothing left to subtract: the current rows are a piece (ref :2226-2245)
+                if (rdw::scan_emits(s.Rl, tol)) {
                     emit(s, o, 0);
                     if (reopen_after_piece(s)) return finish(s, RD_OK);
                 }
@@ -306,8 +256,7 @@ PLP_ENUM_FN int step(State& s, const Out& o, const double tol, const int max_lps
                 return ask(s, max_lps, 0, 0, PH_NODE_RESULT);
             }
             default: {   // PH_NODE_RESULT: a piece when the node is full-dimensional at the last cell, else one level down
-                const double rcv = R != R ? 0.0 : R;
-                if (rcv > tol) {
+                if (rdw::node_full(R, tol)) {
                     if (s.level == s.N - 1) emit(s, o, 1);
                     else s.level = s.level + 1;
                 }

@@ -1,7 +1,8 @@
 // plp_rdiff_search.hpp -- the search of region_diff (ref :2201-2281) over row lists of one constraint table, host only
-// (no HIP, no error string, no environment): the twin of polytope._DiffSearch -- a State and three moves (scan,
-// next_sibling, reopen_after_piece) -- plus a radius memo keyed by a hash of the row list, speculation on what the search
-// asks next, and a queue solved in batches by a Backend: cap_lp() / cap_rows() = the most lists / rows of a sub-batch;
+// (no HIP, no error string, no environment): the twin of polytope._DiffSearch.  The walk -- the table's shape, the moves
+// next_sibling / reopen_after_piece, the verdicts of a scan and a node -- is plp_rdiff_walk.hpp, run here on a State of
+// std::vectors; this header adds a radius memo keyed by a hash of the row list, speculation on what the search asks
+// next, and a queue solved in batches by a Backend: cap_lp() / cap_rows() = the most lists / rows of a sub-batch;
 // solve(off, rows, n, &radii, &stride): list k = rows[off[k] .. off[k + 1]) -> its radius at radii[k * stride]; 0 or a
 // code of its own.  plp_capi.hip runs it on plp_rdiff_host.hpp, tests/cabi/rdiff_search_host.cpp on a callback (CPU).
 #pragma once
@@ -9,7 +10,10 @@
 #include <stdint.h>
 #include <algorithm>
 #include <chrono>
+#include <numeric>
 #include <vector>
+
+#include "plp_rdiff_walk.hpp"
 
 namespace plp {
 namespace rdiff {
@@ -137,86 +141,52 @@ struct RadiusMemo {
     }
 };
 
-// the table's shape: m rows of the minuend, M = sum(mi) new rows of the N cells (cell j from beg[j]), their M negations
+// the table's shape (plp_rdiff_walk.hpp), cells without a cap
 struct Table {
     int m, N;
     const int32_t* mi;
     std::vector<long long> beg;
     long long M = 0, nrows = 0;
-    Table(int m_, int N_, const int32_t* mi_) : m(m_), N(N_), mi(mi_), beg(N_) {
-        for (int j = 0; j < N; ++j) { beg[j] = m + M; M += mi[j]; }
-        nrows = m + 2 * M;
-    }
-    // Python's negative indexing of counter / mi / beg (level == -1 reads the LAST cell, ref :2231)
-    int at(long long level) const { return (int)(level < 0 ? level + N : level); }
+    Table(int m_, int N_, const int32_t* mi_) : m(m_), N(N_), mi(mi_), beg(N_) { rdw::set_shape(*this); }
 };
 
-// The state of the search and its moves; a speculation runs them on a COPY to see which nodes follow, so the lists are
-// exactly the ones the search will form (odd turns of the INDICES arithmetic included).
+// The state of the walk; a speculation runs the moves on a COPY to see which nodes follow, so the lists are exactly the
+// ones the search will form (odd turns of the INDICES arithmetic included).
 struct State {
     const Table* t;
-    std::vector<int> counter;      // 0 = cell closed; c = its first c - 1 new rows kept, row c negated
-    std::vector<int> open_cells;   // cells with counter != 0, ascending; `sumc` = the sum of the counters
+    std::vector<int> counter;      // per cell; `sumc` = their sum
+    std::vector<int> open_cells;   // cells with counter != 0, ascending
     std::vector<long long> idx;    // the reference's INDICES (may hold wrapped / out-of-range values)
     long long level = 0, sumc = 0;
-    explicit State(const Table& tb) : t(&tb), counter(tb.N, 0), idx(tb.m) {
-        for (int i = 0; i < tb.m; ++i) idx[i] = i;
+    bool bad = false;              // a move read the last index of an empty list
+    explicit State(const Table& tb) : t(&tb), counter(tb.N, 0), idx(tb.m) { std::iota(idx.begin(), idx.end(), 0LL); }
+    // ---- the moves of plp_rdiff_walk.hpp on this state
+    void set_counter(int L, int v) { rdw::set_counter(*this, L, v); }
+    bool next_sibling() { return rdw::next_sibling(*this); }
+    bool reopen_after_piece() { return rdw::reopen_after_piece(*this); }
+    // ---- what they reach the table and the storage through
+    friend const Table& table_of(const State& s) { return *s.t; }
+    friend void last_minus(State& s, long long M) {
+        if (s.idx.empty()) s.bad = true;
+        else s.idx.back() -= M;
     }
-    void set_counter(int L, int v) {
-        const int old = counter[L];
-        sumc += v - old;
-        counter[L] = v;
-        if (old == 0 && v != 0) open_cells.insert(std::lower_bound(open_cells.begin(), open_cells.end(), L), L);
-        else if (old != 0 && v == 0) open_cells.erase(std::lower_bound(open_cells.begin(), open_cells.end(), L));
+    friend void push(State& s, long long v) { s.idx.push_back(v); }
+    friend void keep_first(State& s, long long n) {
+        if ((long long)s.idx.size() > n) s.idx.resize(n);
     }
-    // close cell L and drop the rows beyond the m + sumc the reference keeps
-    void close(int L) {
-        set_counter(L, 0);
-        const long long keep_n = t->m + sumc;
-        if ((long long)idx.size() > keep_n) idx.resize(keep_n < 0 ? 0 : keep_n);
+    friend int deepest_open(const State& s) { return s.open_cells.back(); }
+    friend int n_open(const State& s) { return (int)s.open_cells.size(); }
+    friend void mark_open(State& s, int L, bool was, bool on) {
+        if (was == on) return;
+        const auto it = std::lower_bound(s.open_cells.begin(), s.open_cells.end(), L);
+        if (on) s.open_cells.insert(it, L);
+        else s.open_cells.erase(it);
     }
-    // next sibling of the deepest open cell, closing exhausted cells on the way (ref :2246-2271); true: the search ends
-    bool next_sibling() {
-        while (!open_cells.empty()) {   // deepest open cell first (the reference walks nzcount backwards)
-            level = open_cells.back();
-            set_counter((int)level, counter[level] + 1);
-            if (counter[level] <= t->mi[level]) {
-                idx.back() -= t->M;
-                idx.push_back(t->beg[level] + counter[level] + t->M - 1);
-                return false;
-            }
-            close((int)level);
-            level = level - 1;
-            if (level == -1) return true;
-        }
-        return false;
-    }
-    // the move after a piece was emitted (ref :2230-2245: "level - 1", then re-open the cell there); true: the search ends
-    bool reopen_after_piece() {
-        level = level - 1;
-        const int nz = (int)open_cells.size();
-        for (int k = 0; k < nz; ++k) {
-            const int L = t->at(level);
-            if (counter[L] <= t->mi[L]) {
-                idx.back() -= t->M;
-                idx.push_back(t->beg[L] + counter[L] + t->M);
-                return false;
-            }
-            close(L);
-            if (level == -1) return true;
-        }
-        return false;
-    }
-    // idx as table rows, with Python's wrap of an index that went below zero after "- M" (ref :2233); false: one is out
-    // of range (the reference raises IndexError there) and `rows` is not to be used
+    // idx as table rows; false: an index is out of range or a move found the list empty (the reference raises IndexError
+    // there) and `rows` is not to be used
     bool resolve(std::vector<int32_t>& rows) const {
         rows.resize(idx.size());
-        for (size_t k = 0; k < idx.size(); ++k) {
-            const long long r = idx[k] < 0 ? idx[k] + t->nrows : idx[k];
-            if (r < 0 || r >= t->nrows) return false;
-            rows[k] = (int32_t)r;
-        }
-        return true;
+        return !bad && rdw::rows_of(*t, idx.data(), (int)idx.size(), rows.data());
     }
 };
 
@@ -254,7 +224,7 @@ public:
         while (s.level != -1) {
             bool ended = false;
             int rc = OK;
-            if (s.counter[t.at(s.level)] == 0) rc = scan(ended);
+            if (s.counter[rdw::at(t, s.level)] == 0) rc = scan(ended);
             else ended = s.next_sibling();
             if (rc || ended) return rc;
             rc = node();
@@ -354,7 +324,7 @@ private:
     // queue the nodes the search visits from state `c` on while every node turns out empty
     void queue_empty_chain(State& c, int steps) {
         for (int step = 0; step < steps; ++step) {
-            if (c.level == -1 || c.counter[t.at(c.level)] == 0) break;   // the next move would be a scan (or the end)
+            if (c.level == -1 || c.counter[rdw::at(t, c.level)] == 0) break;   // the next move would be a scan (or the end)
             if (c.next_sibling()) break;
             if (!want_state(c)) break;
         }
@@ -384,16 +354,11 @@ private:
         fr.rows = cur;
         for (int j : alive) {
             if (j < s.level) continue;
-            const double Rraw = *R.find(scan_key(kbase, j));
-            // NaN = the LP ended without a verdict (unbounded ball, iteration limit): the reference reads radius 0
-            // there (ref :1294-1297) and solves the cell again at every node below, so only a cell whose LP was
-            // SOLVED with a radius <= abs_tol / 2 is dropped from the scans below this node
-            if (!(Rraw <= 0.5 * tol)) fr.alive.push_back(j);
-            const double Rj = Rraw != Rraw ? 0.0 : Rraw;
-            if (hit < 0) {
+            const double Rj = *R.find(scan_key(kbase, j));
+            if (!rdw::scan_dead(Rj, tol)) fr.alive.push_back(j);
+            if (hit < 0) {   // (the reference stops reading at the hit; the frame takes every cell)
                 res.n_requests++;
-                if (Rj > tol) { hit = j; Rl = Rj; }
-                else if (j == t.N - 1) Rl = Rj;
+                rdw::scan_read(Rj, tol, j, t.N, hit, Rl);
             }
         }
         return OK;
@@ -409,9 +374,9 @@ private:
         if (hit >= 0) {
             s.level = hit;
             s.set_counter((int)hit, 1);
-            s.idx.push_back(t.beg[hit] + t.M);
+            push(s, t.beg[hit] + t.M);
         }
-        if (Rl < tol) {   // nothing left to subtract: the current rows are a piece (ref :2226-2245)
+        if (rdw::scan_emits(Rl, tol)) {
             emit(0);
             ended = s.reopen_after_piece();
         }
@@ -435,9 +400,8 @@ private:
         }
         const double* pnode = R.find(knode);
         if (!pnode) return RADIUS_MISSING;
-        const double rcv = *pnode != *pnode ? 0.0 : *pnode;
         res.n_requests++;
-        if (rcv > tol) {
+        if (rdw::node_full(*pnode, tol)) {
             if (s.level == t.N - 1) emit(1);
             else s.level = s.level + 1;
         }

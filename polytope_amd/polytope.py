@@ -1820,6 +1820,17 @@ def _radii(polys, nan_without_verdict=False):
     return out
 
 
+def _reduce_leaves(todo):
+    """reduce() of the leaves of region_diff searches that the reference reduces (ref :2276), in order: one fused reduce
+    launch for all that fit, reduce() itself for the rest."""
+    done = [None] * len(todo)
+    small = [k for k, p in enumerate(todo) if p.A.size > 0 and _fits_reduce(p.A.shape[0], p.A.shape[1])]
+    if small:
+        for k, q in zip(small, _reduce_many([todo[k] for k in small], ABS_TOL)):
+            done[k] = q
+    return [q if q is not None else reduce(p) for p, q in zip(todo, done)]
+
+
 def region_diff(poly, reg, abs_tol=ABS_TOL, intersect_tol=ABS_TOL, save=False, _order=None, _Rc=None):
     """poly minus the union of the polytopes of reg, as non-overlapping pieces.
 
@@ -1916,13 +1927,7 @@ def region_diff(poly, reg, abs_tol=ABS_TOL, intersect_tol=ABS_TOL, save=False, _
     else:
         leaves = None
     if leaves is not None:
-        todo = [poly_of(rows) for kind, rows in leaves if kind == 1]   # leaves the reference reduces (:2276)
-        done = [None] * len(todo)
-        small = [k for k, p in enumerate(todo) if p.A.size > 0 and _fits_reduce(p.A.shape[0], p.A.shape[1])]
-        if small:   # one fused reduce launch for all of them
-            for k, q in zip(small, _reduce_many([todo[k] for k in small], ABS_TOL)):
-                done[k] = q
-        red = iter([q if q is not None else reduce(p) for p, q in zip(todo, done)])
+        red = iter(_reduce_leaves([poly_of(rows) for kind, rows in leaves if kind == 1]))
         return _union_all([next(red) if kind == 1 else poly_of(rows) for kind, rows in leaves])
 
     def radii_rows(row_lists):
@@ -2037,12 +2042,7 @@ def region_diff_batch(polys, regs, abs_tol=ABS_TOL, intersect_tol=ABS_TOL, _info
                         todo.append(piece)
             else:   # beyond the kernel (or IndexError in the reference): the single call, with the radii it would compute
                 out[k] = region_diff(polys[k], regs[k], abs_tol, intersect_tol, _Rc=Rc)
-        done = [None] * len(todo)
-        small = [t for t, p in enumerate(todo) if p.A.size > 0 and _fits_reduce(p.A.shape[0], p.A.shape[1])]
-        if small:   # one fused reduce launch for the leaves of all problems
-            for t, q_ in zip(small, _reduce_many([todo[t] for t in small], ABS_TOL)):
-                done[t] = q_
-        red = iter([r if r is not None else reduce(p) for p, r in zip(todo, done)])
+        red = iter(_reduce_leaves(todo))   # (one launch for the leaves of all problems)
         for q, (k, _, _) in enumerate(members):   # (in the order the leaves were queued)
             if q in leaves:
                 out[k] = _union_all([next(red) if kind == 1 else piece for kind, piece in leaves[q]])

@@ -4,7 +4,7 @@
 //
 // -DRDIFF_HOST_MAIN adds a main(): a stand-alone program that searches axis-aligned tables it makes itself (a box minus
 // boxes, d = 2 and 3, the radius of a row list in closed form) with default knobs, without speculation and with a small
-// backend and memo, for a run under -fsanitize=address,undefined without anything loaded into an interpreter.
+// backend and memo, after single moves on hand-made states (an empty list of indices, indices that wrap), for a run under -fsanitize=address,undefined without anything loaded into an interpreter.
 #include <stdint.h>
 
 #include <vector>
@@ -152,10 +152,42 @@ Run search(BoxTable& T, int m, const std::vector<int32_t>& mi, const int32_t* kn
     return r;
 }
 
+// one move on a hand-made state (MOVE_STATES of tests/test_rdiff_search_host.py) and what rdiff_move_host must report
+struct MoveCase {
+    int m;
+    std::vector<int32_t> mi, counter;
+    std::vector<long long> idx;
+    long long level;
+    int move;
+    long long ended, resolved, n_idx, level_after;
+};
+const MoveCase MOVES[] = {
+    // an empty list of indices under an open cell within mi: "- M" has no last index, resolve fails
+    {0, {2}, {1}, {}, 0, 0, 0, 0, 1, 0},
+    {0, {2, 1}, {1, 0}, {}, 1, 1, 0, 0, 1, 0},
+    {2, {2}, {1}, {}, 0, 0, 0, 0, 1, 0},
+    {1, {1, 2}, {0, 1}, {}, 0, 1, 0, 0, 1, -1},
+    // ... under an exhausted cell: closed, nothing is read, the search ends
+    {0, {1}, {2}, {}, 0, 0, 1, 1, 0, -1},
+    // "- M" on a row of the minuend: the index wraps to the end of the table / leaves it
+    {2, {2, 1}, {1, 0}, {0, 1}, 1, 1, 0, 1, 3, 0},
+    {1, {3, 3}, {1, 1}, {-9}, 1, 1, 0, 0, 2, 0},
+    {1, {3, 3}, {2, 0}, {0, -12}, 0, 0, 0, 0, 3, 0},
+};
+bool move_as_expected(const MoveCase& c) {
+    std::vector<int32_t> counter = c.counter, rows(c.idx.size() + 2);
+    std::vector<long long> idx_out(c.idx.size() + 2);
+    long long level = c.level, out[4];
+    const int rc = rdiff_move_host(c.m, (int)c.mi.size(), c.mi.data(), counter.data(), (long long)c.idx.size(), c.idx.data(),
+                                   &level, c.move, (long long)idx_out.size(), idx_out.data(), rows.data(), out);
+    return rc == 0 && out[0] == c.ended && out[1] == c.resolved && out[2] == c.n_idx && level == c.level_after;
+}
+
 }  // namespace
 
 int main() {
     long long searches = 0, leaves = 0, bad = 0, ended[2] = {0, 0};
+    for (const MoveCase& c : MOVES) bad += !move_as_expected(c);
     const int32_t none[5] = {0, 0, 0, 0, 0}, deep[5] = {600, 6, 8, 1, 1};
     for (int trial = 0; trial < 40; ++trial) {
         const int d = 2 + trial % 2, N = 1 + (int)(unif() * (d == 2 ? 7 : 5)), m = 2 * d;

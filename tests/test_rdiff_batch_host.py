@@ -204,8 +204,9 @@ def test_table_build_bit_for_bit(cases, LB):
 
 def test_moves_equal_the_existing_state(L, LB):
     """Case 3: on the hand-made states of test_rdiff_search_host.py (level -1 with open cells, counters above mi, indices
-    that wrap or leave the table) and its 3 000 random states, the fixed-array State equals plp::rdiff::State field for
-    field: level, ended, counters, INDICES, the sum of the counters, the resolved rows."""
+    that wrap or leave the table, an empty list of indices) and its 3 000 random states, the two instantiations of the
+    moves of plp_rdiff_walk.hpp agree -- the fixed-array State equals plp::rdiff::State field for field: level, ended,
+    counters, INDICES, the sum of the counters, the resolved rows."""
     rng = np.random.default_rng(5)
     states = list(TS.MOVE_STATES)
     for _ in range(3000):
@@ -223,6 +224,8 @@ def test_moves_equal_the_existing_state(L, LB):
         assert RB.move(LB, *st) == want, st
         out_of_range += want[5] is None
     assert out_of_range >= 5
+    for st in TS.EMPTY_LIST_STATES:
+        assert RB.move(LB, *st)[5] is None
     for st in TS.MOVE_STATES[:2]:
         assert RB.move(LB, *st)[:2] == (-1, True)
 

@@ -262,7 +262,10 @@ def _twin_move(m, mi, counter, idx, level, which):
     nrows = m + 2 * M
     tw = pcm._DiffSearch(m, mi, [m + sum(mi[:j]) for j in range(len(mi))], M, 1e-7, None, False)
     counter, rows = list(counter), list(idx)
-    level, ended = (tw._next_sibling if which == 0 else tw._reopen_after_piece)(counter, rows, level)
+    try:
+        level, ended = (tw._next_sibling if which == 0 else tw._reopen_after_piece)(counter, rows, level)
+    except IndexError:
+        return "IndexError"
     ok = all(-nrows <= v < nrows for v in rows)   # what numpy's indexing of the table accepts
     return level, ended, counter, rows, sum(counter), [v + nrows if v < 0 else v for v in rows] if ok else None
 
@@ -287,6 +290,18 @@ MOVE_STATES = [
     (2, [1, 1], [1, 1], [0, 1, 4, 5], 1, 0),
     (2, [1, 2, 1], [0, 2, 1], [0, 1, 3, 8], 2, 0),
 ]
+# an EMPTY list of indices and an open cell whose counter is within mi: "- M" on the last index has nothing to act on.
+# The twin's `rows[-1] -= M` raises IndexError; both C++ states note it and their resolve fails (BAD_INDEX / RD_INDEX).
+# m = 0 and m >= 1, next_sibling and reopen_after_piece (the last one re-opens the LAST cell at level -1)
+EMPTY_LIST_STATES = [
+    (0, [2], [1], [], 0, 0),
+    (0, [2, 1], [1, 0], [], 1, 1),
+    (2, [2], [1], [], 0, 0),
+    (1, [1, 2], [0, 1], [], 0, 1),
+]
+MOVE_STATES += EMPTY_LIST_STATES
+# ... and an empty list that no move reads: the one open cell is exhausted, closed, and the search ends
+MOVE_STATES.append((0, [1], [2], [], 0, 0))
 
 
 def test_moves_on_hand_made_states(L):
@@ -296,8 +311,9 @@ def test_moves_on_hand_made_states(L):
     with nothing to re-open: the 24 random cases and the tables above never get there with an open cell, nor did a
     search over small tables with made-up radii find an index out of range.  The moves take an explicit state on both
     sides, so they are compared directly: hand-made states at level 0 with open cells and a counter above mi, indices
-    that wrap or leave the table, and 3 000 random states; plp::rdiff::State against the twin's _next_sibling /
-    _reopen_after_piece, field for field, and State::resolve against numpy's reading of the indices."""
+    that wrap or leave the table, an empty list of indices, and 3 000 random states; plp::rdiff::State under the moves
+    of plp_rdiff_walk.hpp against the twin's _next_sibling / _reopen_after_piece, field for field, and resolve against
+    numpy's reading of the indices (where the twin's own indexing raises IndexError, resolve must fail)."""
     rng = np.random.default_rng(5)
     states = list(MOVE_STATES)
     for _ in range(3000):
@@ -313,6 +329,9 @@ def test_moves_on_hand_made_states(L):
     for m, mi, counter, idx, level, which in states:
         want = _twin_move(m, mi, counter, idx, level, which)
         got = RH.move(L, m, mi, counter, idx, level, which)
+        if want == "IndexError":   # the twin's own indexing raised: the State's resolve must fail
+            assert got[5] is None, (m, mi, counter, idx, level, which)
+            continue
         assert got == want, (m, mi, counter, idx, level, which)
         lvl, ended, _, rows_after, _, table_rows = got
         if which == 1 and level == 0 and any(counter):
@@ -322,6 +341,9 @@ def test_moves_on_hand_made_states(L):
         seen["trimmed"] += len(rows_after) < len(idx)
     print(seen)
     assert all(v >= 5 for v in seen.values()), seen
+    for st in EMPTY_LIST_STATES:
+        assert _twin_move(*st) == "IndexError" and RH.move(L, *st)[5] is None
+    assert RH.move(L, *MOVE_STATES[-1]) == (-1, True, [0], [], 0, [])
     for st in MOVE_STATES[:2]:
         assert RH.move(L, *st)[:2] == (-1, True)
     assert [RH.move(L, *st)[5] is None for st in MOVE_STATES[5:10]] == [False, True, True, True, False]
