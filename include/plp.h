@@ -522,6 +522,52 @@ int plp_adjacent_pairs_range_dev(plp_ctx *ctx, void *stream, int n, int m_max, i
                                  int64_t pair_hi, uint8_t *out);
 
 /*
+ * The pair verdicts of a LIST of pairs: out[t] is the byte the calls above give the pair (pairs[t][0], pairs[t][1]) of the
+ * n cells -- 1 iff the stack of the two cells, every b raised by `inflate`, has a Chebyshev radius > thresh (adjacency:
+ * inflate = abs_tol, thresh = abs_tol / 10; overlap: inflate = 0, thresh = abs_tol).  The same engines (picked by K as the
+ * dense calls pick by their pair count) and the same careful pass, so the bytes are equal, pair for pair.  A pair may be
+ * listed more than once and in either order.  pairs[K][2] int32.  2 * m_max <= 64, d <= 16.
+ * A pair with an index outside [0, n) or with two equal indices: the host-pointer call returns PLP_EINVAL before anything
+ * runs; the device-pointer call, which cannot read the list, writes PLP_PAIR_BAD for that pair and reads nothing for it.
+ */
+#define PLP_PAIR_BAD 255
+int plp_pair_list(plp_ctx *ctx, int n, int m_max, int d, const double *A, const double *b, const int32_t *m,
+                  double inflate, double thresh, int64_t K, const int32_t *pairs, uint8_t *out);
+int plp_pair_list_dev(plp_ctx *ctx, void *stream, int n, int m_max, int d, const double *A, const double *b,
+                      const int32_t *m, double inflate, double thresh, int64_t K, const int32_t *pairs, uint8_t *out);
+
+/*
+ * The broad phase in front of plp_pair_list: the pairs of cells whose outer boxes meet.  Cell p has the box lb[p][d],
+ * ub[p][d], padded to L_p = lb_p - pad', U_p = ub_p + pad' with pad' = pad * max(1, the box's largest finite |bound|); NaN
+ * bounds and infinite sides span their axis (as plp_locate_grid_count).  (i, j) is a CANDIDATE iff
+ * max(L_i[k], L_j[k]) <= min(U_i[k], U_j[k]) on all d axes.  If every finite side bounds the cell {A x <= b + inflate}, a
+ * pair that is no candidate has verdict 0 in plp_pair_list: a ball of radius r > thresh >= 0 in both cells lies in both boxes.
+ * n1 == 0: the pairs (i, j) with j < i.  n1 > 0, the cross form: the table holds n1 cells and then n - n1, and the pairs are
+ *      (a, c) with a < n1 <= c.
+ * grid == NULL: every partner is box-tested.  grid != NULL (a HOST pointer in both forms) with cell_start / cell_items, the
+ *      lists plp_locate_grid_count / _fill build from the SAME lb, ub and pad: partners are met through the lists, each
+ *      pair in one canonical grid cell.  The set of candidates is the same, integer for integer.
+ * plp_box_pairs_count: per_cell[n + 1] (int64), the exclusive prefix sums of the cells' numbers of partners; per_cell[n] = K.
+ * plp_box_pairs_fill: with that per_cell, the pairs of the cells cell_lo <= i < cell_hi into
+ *      pairs[per_cell[cell_hi] - per_cell[cell_lo]][2] (int32): (i, j), cell i's partners ascending, so the list is sorted
+ *      by (i, j) and deterministic.  Count and fill evaluate one predicate.
+ * Errors: negative sizes, d < 1, n1 > n, pad < 0, a bad grid descriptor or cell range: PLP_EINVAL "bad sizes"; NULL
+ *      arrays: PLP_EINVAL "NULL pointer"; d > 16: PLP_EUNSUPPORTED.
+ */
+int plp_box_pairs_count(plp_ctx *ctx, int n, int d, const double *lb, const double *ub, double pad,
+                        const plp_locate_grid *grid, const int32_t *cell_start, const int32_t *cell_items, int n1,
+                        int64_t *per_cell);
+int plp_box_pairs_count_dev(plp_ctx *ctx, void *stream, int n, int d, const double *lb, const double *ub, double pad,
+                            const plp_locate_grid *grid, const int32_t *cell_start, const int32_t *cell_items, int n1,
+                            int64_t *per_cell);
+int plp_box_pairs_fill(plp_ctx *ctx, int n, int d, const double *lb, const double *ub, double pad,
+                       const plp_locate_grid *grid, const int32_t *cell_start, const int32_t *cell_items, int n1,
+                       const int64_t *per_cell, int cell_lo, int cell_hi, int32_t *pairs);
+int plp_box_pairs_fill_dev(plp_ctx *ctx, void *stream, int n, int d, const double *lb, const double *ub, double pad,
+                           const plp_locate_grid *grid, const int32_t *cell_start, const int32_t *cell_items, int n1,
+                           const int64_t *per_cell, int cell_lo, int cell_hi, int32_t *pairs);
+
+/*
  * Quickhull's main loop (polytope/quickhull.py:224-345) as native host code over a plp_hull session: facet graph,
  * visibility search, horizon, new facets and their links on the host, every pass over the points one plp_hull_reassign.
  * X0[N][d]: the points translated so that the start simplex' centroid is the origin (:188-192); simplex[d + 1]: the

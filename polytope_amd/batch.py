@@ -1163,6 +1163,227 @@ def adjacent_pairs_range(A, b, pair_lo, pair_hi, m=None, abs_tol=1e-7):
     return out
 
 
+# ------------------------------------------------------------------------------------- sparse pair screens
+# box_pairs(grid="auto"): every partner box-tested below this many cells, a grid built above.  NOT MEASURED:
+# at 1024 cells the brute walk of a cell is at most 16 steps of 64 partners, about what a walk over a 2 x 2 x 2 cell range
+# costs; which of the two runs changes the time only, never the set.
+_BOX_PAIRS_AUTO_N = 1024
+PAIR_BAD = 255    # include/plp.h: PLP_PAIR_BAD
+
+
+class _BoxPairs(object):
+    """The broad phase of one table of boxes: the grid (or none), per_cell int64[n + 1] and K = per_cell[n] after the count
+    pass; fill(cell_lo, cell_hi) then gives the candidate pairs of whole cells."""
+
+    def __init__(self, be, lb, ub, n1, pad, grid):
+        self.be = be
+        lb, ub = be.arr(lb), be.arr(ub)
+        if len(lb.shape) != 2 or tuple(ub.shape) != tuple(lb.shape):
+            raise ValueError("box_pairs: lb and ub must both be [n, d]")
+        self.n, self.d = int(lb.shape[0]), int(lb.shape[1])
+        self.n1 = 0 if n1 is None else int(n1)
+        if n1 is not None and not (0 < self.n1 <= self.n):
+            raise ValueError("box_pairs: n1 must lie in 1..n (the cells of the first list)")
+        if self.d < 1 or self.d > MAX_D:
+            raise _lib.UnsupportedSize("box_pairs: d=%d outside 1..%d" % (self.d, MAX_D))
+        if not (isinstance(grid, str) and grid in ("auto", "grid")) and grid is not None:
+            raise ValueError("grid must be 'auto', 'grid' or None")
+        self.pad = float(pad)
+        self.lb, self.ub = lb, ub
+        self.lists, self.desc, self.reason = (None, None, None), None, "not asked for"
+        if grid == "grid" or (grid == "auto" and self.n >= _BOX_PAIRS_AUTO_N):
+            self._build_grid()
+        self.per_cell = be.out((self.n + 1,), np.int64, zero=True)
+        be.call("plp_box_pairs_count", self.n, self.d, self.lb, self.ub, self.pad, *self.lists, self.n1, self.per_cell,
+                h2d=(self.lb, self.ub) + tuple(a for a in self.lists[1:] if a is not None))
+        self.K = int(self.per_cell[self.n])   # (resident: the one read-back of the count pass)
+        self._pc_host = None
+
+    def _build_grid(self):
+        """The cell lists of the point-location grid over these boxes (locate_grid's passes); declined -- self.lists stays
+        (None, None, None) and the kernels box-test every partner -- as locate_grid declines."""
+        be, n, d = self.be, self.n, self.d
+        xp = be.torch if be.torch is not None else np
+        if n == 0:
+            self.reason = "no cells"
+            return
+        never = xp.zeros_like(self.lb[:, 0]) != 0
+        self.lb, self.ub, st = _locate_boxes(be, self.lb, self.ub, never, never)
+        desc, axes = _locate_desc(n, d, st)
+        if desc is None:
+            self.reason = "no axis along which the boxes are narrower than their common extent"
+            return
+        G = int(np.prod([a[3] for a in axes]))
+        hs = _HostStruct(desc)
+        cell_start = be.out((G + 1,), np.int32, zero=True)
+        max_len = be.out((1,), np.int32, zero=True)
+        be.call("plp_locate_grid_count", n, d, self.lb, self.ub, self.pad, hs, cell_start, max_len, h2d=(self.lb, self.ub))
+        if be.torch is not None:
+            n_items, longest = (int(v) for v in be.torch.stack([cell_start[G], max_len[0]]).cpu())
+        else:
+            n_items, longest = int(cell_start[G]), int(max_len[0])
+        if n_items > _LOCATE_MAX_ITEMS or longest > _LOCATE_MAX_LIST:
+            self.reason = "%d list entries (budget %d), longest list %d (cap %d)" % (n_items, _LOCATE_MAX_ITEMS, longest,
+                                                                                    _LOCATE_MAX_LIST)
+            return
+        cell_items = be.out((max(n_items, 1),), np.int32, zero=True)
+        cursor = be.out((G,), np.int32, zero=True)
+        be.call("plp_locate_grid_fill", n, d, self.lb, self.ub, self.pad, hs, cell_start, cursor, cell_items,
+                h2d=(self.lb, self.ub, cell_start))
+        self.lists, self.reason, self.desc = (hs, cell_start, cell_items), "", desc
+
+    def fill(self, cell_lo=0, cell_hi=None):
+        """int32[K', 2]: the candidate pairs of the cells cell_lo <= i < cell_hi, sorted by (i, j)."""
+        cell_hi = self.n if cell_hi is None else int(cell_hi)
+        if cell_lo == 0 and cell_hi == self.n:
+            k = self.K
+        else:
+            k = int(self.per_cell[cell_hi]) - int(self.per_cell[cell_lo]) if self._pc_host is None else \
+                int(self._pc_host[cell_hi] - self._pc_host[cell_lo])
+        pairs = self.be.out((k, 2), np.int32, zero=True)
+        if k:
+            self.be.call("plp_box_pairs_fill", self.n, self.d, self.lb, self.ub, self.pad, *self.lists, self.n1, self.per_cell,
+                         int(cell_lo), cell_hi, pairs, h2d=(self.lb, self.ub, self.per_cell))
+        return pairs
+
+    def chunks(self, max_candidates):
+        """[(cell_lo, cell_hi)]: whole cells, at most max_candidates pairs each (a single cell with more is a chunk of its
+        own); one chunk, and no read-back of per_cell, when everything fits."""
+        if self.K <= max_candidates:
+            return [(0, self.n)] if self.K else []
+        pc = self.per_cell.cpu().numpy() if self.be.torch is not None else self.per_cell
+        self._pc_host = pc
+        out, lo = [], 0
+        while lo < self.n and pc[lo] < pc[self.n]:
+            hi = int(np.searchsorted(pc, pc[lo] + max_candidates, side="right")) - 1
+            hi = min(max(hi, lo + 1), self.n)
+            if pc[hi] > pc[lo]:
+                out.append((lo, hi))
+            lo = hi
+        return out
+
+
+def box_pairs(lb, ub, n1=None, pad=_LOCATE_PAD, grid="auto"):
+    """The pairs of n boxes lb[n, d], ub[n, d] that meet -- the broad phase of the sparse pair calls.
+
+    Box p is padded to [lb_p - pad', ub_p + pad'], pad' = pad * max(1, its largest finite |bound|); NaN bounds and infinite
+    sides span their axis.  (i, j), j < i, is a candidate iff the padded boxes meet on all d axes; with n1 the table holds
+    two lists, n1 boxes and then n - n1, and the candidates are the (a, c) with a < n1 <= c.
+    -> dict(pairs int32[K, 2] sorted by (i, j), per_cell int64[n + 1] (cell i's partners are pairs[per_cell[i] :
+    per_cell[i + 1]]), ncand = K, grid = the LocateGridDesc used or None).
+    grid: None -- every partner is box-tested; "grid" -- partners are met through the cell lists of the point-location grid
+    (locate_grid's passes over these boxes), each pair in one canonical cell; "auto" -- the grid from 1024 boxes on.  The
+    set is the same, integer for integer; a declined grid (no separating axis, lists over budget) runs the first form.
+    numpy in: numpy out; CUDA tensors in: resident tensors on torch's current stream (read-backs: K, and the grid's sizes)."""
+    bp = _BoxPairs(_Backend(lb), lb, ub, n1, pad, grid)
+    return dict(pairs=bp.fill(), per_cell=bp.per_cell, ncand=bp.K, grid=bp.desc)
+
+
+def pair_verdicts(A, b, pairs, m=None, inflate=0.0, thresh=1e-7):
+    """uint8[K]: for each listed pair (pairs[t, 0], pairs[t, 1]) of the n cells A[n, m_max, d], b[n, m_max] the verdict of
+    the dense pair calls -- 1 iff the stack of the two cells, every b raised by `inflate`, has a Chebyshev radius > thresh
+    (adjacent_pairs: inflate = abs_tol, thresh = abs_tol / 10; overlap_pairs / overlap_cross: inflate = 0, thresh =
+    abs_tol), through the same engines and careful pass.  pairs int32[K, 2]; a pair may appear more than once, in either
+    order.  2 * m_max <= 64, d <= 16.  numpy: an index outside [0, n) or a pair (i, i) raises PlpError; CUDA tensors
+    (nothing synchronises, so the list is not read by the host): such a pair gets 255 and nothing is read for it."""
+    be, A, b, m, n, m_max, d = _cells("pair_verdicts", A, b, m)
+    pairs = be.arr(pairs, np.int32)
+    if len(pairs.shape) != 2 or pairs.shape[1] != 2:
+        raise ValueError("pairs must be [K, 2]")
+    K = int(pairs.shape[0])
+    out = be.out((K,), np.uint8, zero=True)
+    be.call("plp_pair_list", n, m_max, d, A, b, m, float(inflate), float(thresh), K, pairs, out, h2d=(A, b, m, pairs))
+    return out
+
+
+def _outer_boxes(be, A, b, m, inflate):
+    """Outer boxes of the cells {A x <= b + inflate}: bbox_batch's, and every side infinite for a cell whose box is not to
+    be had -- status != 0, a zero row, a non-finite entry, no rows.  (Never "nowhere": only outer boxes are safe.)"""
+    tor = be.torch
+    xp = tor if tor is not None else np
+    kw = {} if tor is None else {"device": be.device}
+    n, m_max = int(A.shape[0]), int(A.shape[1])
+    inf = float("inf")
+    with np.errstate(all="ignore"):
+        br = b + inflate
+        box = bbox_batch(A, br, m)
+        rows = (xp.arange(m_max, **kw)[None, :] < m[:, None]) if m is not None else \
+            xp.ones((n, m_max), dtype=(bool if tor is None else tor.bool), **kw)
+        zero = rows & (A == 0).all(-1)
+        bad = rows & ~(xp.isfinite(A).all(-1) & xp.isfinite(br))
+        every = (box["status"] != 0) | zero.any(-1) | bad.any(-1) | ~rows.any(-1)
+        lb = xp.where(every[:, None], xp.full_like(box["lb"], -inf), box["lb"])
+        ub = xp.where(every[:, None], xp.full_like(box["ub"], inf), box["ub"])
+    return lb, ub
+
+
+def _pairs_sparse(what, A, b, m, inflate, thresh, n1, boxes, max_candidates, grid="auto"):
+    """Broad phase, then per chunk of whole cells: fill -> listed pair LPs -> the positives -> dict(pairs, ncand)."""
+    be, A, b, m, n, m_max, d = _cells(what, A, b, m)
+    if m_max < 1 or 2 * m_max > MAX_M or d < 1 or d > MAX_D:
+        raise _lib.UnsupportedSize("%s: m_max=%d d=%d outside envelope (2*m_max<=64, d<=16)" % (what, m_max, d))
+    max_candidates = int(max_candidates)
+    if max_candidates < 1:
+        raise ValueError("%s: max_candidates must be at least 1" % what)
+    if boxes is None:
+        lb, ub = _outer_boxes(be, A, b, m, float(inflate)) if n else (be.out((0, d)), be.out((0, d)))
+    else:
+        lb, ub = boxes
+        if tuple(lb.shape) != (n, d) or tuple(ub.shape) != (n, d):
+            raise ValueError("%s: boxes must be (lb[n, d], ub[n, d])" % what)
+    bp = _BoxPairs(be, lb, ub, n1, _LOCATE_PAD, grid)
+    found = []
+    for lo, hi in bp.chunks(max_candidates):
+        cand = bp.fill(lo, hi)
+        K = int(cand.shape[0])
+        v = be.out((K,), np.uint8, zero=True)
+        be.call("plp_pair_list", n, m_max, d, A, b, m, float(inflate), float(thresh), K, cand, v, h2d=(A, b, m, cand))
+        found.append(cand[v != 0])
+    if not found:
+        pairs = be.out((0, 2), np.int32, zero=True)
+    elif len(found) == 1:
+        pairs = found[0]
+    else:
+        pairs = be.torch.cat(found) if be.torch is not None else np.concatenate(found)
+    return dict(pairs=pairs, ncand=bp.K)
+
+
+def adjacent_pairs_sparse(A, b, m=None, abs_tol=1e-7, boxes=None, max_candidates=1 << 24):
+    """The adjacent pairs of n single-polytope cells as a list: dict(pairs int32[K, 2], ncand) with pairs EXACTLY the
+    nonzeros of tril(adjacent_pairs(A, b, m, abs_tol), -1) -- (i, j), i > j, sorted by (i, j) -- and ncand the number of
+    pair LPs solved.  A[n, m_max, d], b[n, m_max]; 2 * m_max <= 64, d <= 16; no n x n matrix is formed.
+
+    Only pairs whose outer boxes meet are solved (box_pairs): a pair counts iff the stack of the two abs_tol-inflated cells
+    holds a ball of radius > abs_tol / 10, and that ball lies in both boxes.  boxes: None -- bbox_batch(A, b + abs_tol, m),
+    every side infinite for a cell without a usable box (box status != 0, a zero row, a non-finite entry, no rows); or
+    (lb[n, d], ub[n, d]), which MUST be outer boxes of the inflated cells {A_p x <= b_p + abs_tol} -- a side that cuts
+    into a cell loses pairs silently.  The candidates go through the pair LPs in chunks of whole cells of at most
+    max_candidates pairs (8 bytes of indices and one of verdict each; a cell with more partners is a chunk of its own).
+    numpy in: numpy out; CUDA tensors in: resident tensors on torch's current stream."""
+    abs_tol = float(abs_tol)
+    return _pairs_sparse("adjacent_pairs_sparse", A, b, m, abs_tol, abs_tol / 10, None, boxes, max_candidates)
+
+
+def overlap_pairs_sparse(A, b, m=None, abs_tol=1e-7, boxes=None, max_candidates=1 << 24):
+    """As adjacent_pairs_sparse for overlap: pairs = the nonzeros of tril(overlap_pairs(A, b, m, abs_tol), -1); nothing is
+    inflated (boxes passed in are outer boxes of the cells themselves) and a pair counts iff the stack holds a ball of
+    radius > abs_tol."""
+    return _pairs_sparse("overlap_pairs_sparse", A, b, m, 0.0, float(abs_tol), None, boxes, max_candidates)
+
+
+def overlap_cross_sparse(A, b, n1, m=None, thresh=1e-7, boxes=None, max_candidates=1 << 24):
+    """As overlap_pairs_sparse for two lists in one table (overlap_cross): pairs = the nonzeros (a, c) of
+    overlap_cross(A, b, n1, m, thresh), a < n1 a cell of the first list and c < n - n1 one of the second, sorted by (a, c)."""
+    n1 = int(n1)
+    if n1 == 0:   # (an empty first list, as overlap_cross; the library reads n1 = 0 as "all pairs")
+        be = _Backend(A)
+        return dict(pairs=be.out((0, 2), np.int32, zero=True), ncand=0)
+    res = _pairs_sparse("overlap_cross_sparse", A, b, m, 0.0, float(thresh), n1, boxes, max_candidates)
+    if int(res["pairs"].shape[0]):
+        res["pairs"][:, 1] -= n1
+    return res
+
+
 def selftest(group_size):
     """Cross-lane primitive self-test -> (out_d[128], out_u[128]) (see plp_points.hip)."""
     lib = _lib.load()

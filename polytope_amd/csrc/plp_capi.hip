@@ -1482,6 +1482,150 @@ int plp_adjacent_pairs_range(plp_ctx* ctx, int n, int m_max, int d, const double
                       });
 }
 
+// ------------------------------------------------------------------------------- listed pairs, box pairs
+static int check_pair_list(plp_ctx* ctx, int n, int m_max, int d, const double* A, const double* b, int64_t K,
+                           const int32_t* pairs, const uint8_t* out) {
+    int rc = check_pairs(ctx, n < 0 || K < 0, K == 0, m_max, d, A, b, out);
+    if (rc == PLP_OK && K > 0 && !pairs) return fail(PLP_EINVAL, "NULL pointer");
+    return rc;
+}
+
+int plp_pair_list_dev(plp_ctx* ctx, void* stream, int n, int m_max, int d, const double* A, const double* b, const int32_t* m,
+                      double inflate, double thresh, int64_t K, const int32_t* pairs, uint8_t* out) {
+    int rc = check_pair_list(ctx, n, m_max, d, A, b, K, pairs, out);
+    if (rc || K == 0) return rc;
+    void* sc;
+    if ((rc = pair_scratch(ctx, stream, &sc))) return rc;
+    if (plp::launch_pair_list(n, m_max, d, A, b, m, inflate, thresh, K, pairs, out, (hipStream_t)stream, sc))
+        return fail(PLP_EUNSUPPORTED, "adjacent kernel: unsupported size");
+    return check_launch("adjacent_r_list_kernel");
+}
+
+int plp_pair_list(plp_ctx* ctx, int n, int m_max, int d, const double* A, const double* b, const int32_t* m, double inflate,
+                  double thresh, int64_t K, const int32_t* pairs, uint8_t* out) {
+    int rc = check_pair_list(ctx, n, m_max, d, A, b, K, pairs, out);
+    if (rc || K == 0) return rc;
+    for (int64_t t = 0; t < K; ++t) {
+        const int32_t i = pairs[2 * t], j = pairs[2 * t + 1];
+        if (i < 0 || i >= n || j < 0 || j >= n || i == j)
+            return fail(PLP_EINVAL, "pair %lld = (%d, %d): indices must be two different cells of [0, %d)", (long long)t, i, j, n);
+    }
+    double *dA, *db;
+    int32_t *dm, *dpairs;
+    uint8_t* dout;
+    HostCall hc(ctx);
+    hc.in(dA, A, (size_t)n * m_max * d);
+    hc.in(db, b, (size_t)n * m_max);
+    hc.in(dm, m, n);
+    hc.in(dpairs, pairs, (size_t)K * 2);
+    hc.out(dout, out, (size_t)K);
+    hc.direct_out = true;
+    rc = hc.reserve();
+    if (rc) return rc;
+    rc = hc.upload();
+    if (rc) return rc;
+    rc = plp_pair_list_dev(ctx, hc.st, n, m_max, d, dA, db, dm, inflate, thresh, K, dpairs, dout);
+    if (rc) return rc;
+    return hc.download();
+}
+
+static int check_box_pairs(plp_ctx* ctx, int n, int d, const double* lb, const double* ub, double pad,
+                           const plp_locate_grid* grid, const int32_t* cell_start, int n1, const void* out) {
+    if (!ctx) return fail(PLP_EINVAL, "ctx is NULL");
+    if (n < 0 || d < 1 || n1 < 0 || n1 > n || !(pad >= 0.0)) return fail(PLP_EINVAL, "bad sizes");
+    if (!out || (n > 0 && (!lb || !ub)) || (grid && n > 0 && !cell_start)) return fail(PLP_EINVAL, "NULL pointer");
+    if (d > plp::MAX_D) return fail(PLP_EUNSUPPORTED, "d=%d > 16", d);
+    if (grid && plp::loc::grid_bad(*grid, d)) return fail(PLP_EINVAL, "bad sizes (box pairs: grid descriptor)");
+    return PLP_OK;
+}
+
+int plp_box_pairs_count_dev(plp_ctx* ctx, void* stream, int n, int d, const double* lb, const double* ub, double pad,
+                            const plp_locate_grid* grid, const int32_t* cell_start, const int32_t* cell_items, int n1,
+                            int64_t* per_cell) {
+    int rc = check_box_pairs(ctx, n, d, lb, ub, pad, grid, cell_start, n1, per_cell);
+    if (rc) return rc;
+    const int lr = plp::launch_box_pairs_count(n, d, lb, ub, pad, grid, cell_start, cell_items, n1, (long long*)per_cell,
+                                               (hipStream_t)stream);
+    if (lr == 3) return fail(PLP_EHIP, "box pairs: hipMemsetAsync failed");
+    if (lr) return fail(PLP_EINVAL, "bad sizes (box pairs)");
+    return check_launch("box_pairs_kernel");
+}
+
+int plp_box_pairs_fill_dev(plp_ctx* ctx, void* stream, int n, int d, const double* lb, const double* ub, double pad,
+                           const plp_locate_grid* grid, const int32_t* cell_start, const int32_t* cell_items, int n1,
+                           const int64_t* per_cell, int cell_lo, int cell_hi, int32_t* pairs) {
+    int rc = check_box_pairs(ctx, n, d, lb, ub, pad, grid, cell_start, n1, per_cell);
+    if (rc) return rc;
+    if (cell_lo < 0 || cell_hi > n || cell_lo > cell_hi) return fail(PLP_EINVAL, "bad sizes (box pairs: cell range)");
+    if (cell_lo == cell_hi) return PLP_OK;
+    if (!pairs) return fail(PLP_EINVAL, "NULL pointer");
+    if (plp::launch_box_pairs_fill(n, d, lb, ub, pad, grid, cell_start, cell_items, n1, (const long long*)per_cell, cell_lo,
+                                   cell_hi, pairs, (hipStream_t)stream))
+        return fail(PLP_EINVAL, "bad sizes (box pairs)");
+    return check_launch("box_pairs_kernel");
+}
+
+// (host-pointer forms: the lists are read up to cell_start[G], as plp_locate reads them)
+int plp_box_pairs_count(plp_ctx* ctx, int n, int d, const double* lb, const double* ub, double pad, const plp_locate_grid* grid,
+                        const int32_t* cell_start, const int32_t* cell_items, int n1, int64_t* per_cell) {
+    int rc = check_box_pairs(ctx, n, d, lb, ub, pad, grid, cell_start, n1, per_cell);
+    if (rc) return rc;
+    const bool lists = grid && n > 0;
+    const size_t G = lists ? (size_t)grid_cells(grid) : 0;
+    const size_t items = lists ? (size_t)(cell_start[G] < 0 ? 0 : cell_start[G]) : 0;
+    if (items && !cell_items) return fail(PLP_EINVAL, "NULL pointer");
+    double *dlb, *dub;
+    int32_t *dcs, *dci;
+    int64_t* dpc;
+    HostCall hc(ctx);
+    hc.in(dlb, lb, (size_t)n * d);
+    hc.in(dub, ub, (size_t)n * d);
+    hc.in(dcs, lists ? cell_start : nullptr, G + 1);
+    hc.in(dci, items ? cell_items : nullptr, items);
+    hc.out(dpc, per_cell, (size_t)n + 1);
+    rc = hc.reserve();
+    if (rc) return rc;
+    rc = hc.upload();
+    if (rc) return rc;
+    rc = plp_box_pairs_count_dev(ctx, hc.st, n, d, dlb, dub, pad, grid, dcs, dci, n1, dpc);
+    if (rc) return rc;
+    return hc.download();
+}
+
+int plp_box_pairs_fill(plp_ctx* ctx, int n, int d, const double* lb, const double* ub, double pad, const plp_locate_grid* grid,
+                       const int32_t* cell_start, const int32_t* cell_items, int n1, const int64_t* per_cell, int cell_lo,
+                       int cell_hi, int32_t* pairs) {
+    int rc = check_box_pairs(ctx, n, d, lb, ub, pad, grid, cell_start, n1, per_cell);
+    if (rc) return rc;
+    if (cell_lo < 0 || cell_hi > n || cell_lo > cell_hi) return fail(PLP_EINVAL, "bad sizes (box pairs: cell range)");
+    const int64_t K = per_cell[cell_hi] - per_cell[cell_lo];
+    if (K < 0) return fail(PLP_EINVAL, "bad sizes (box pairs: per_cell decreases)");
+    if (K == 0) return PLP_OK;
+    if (!pairs) return fail(PLP_EINVAL, "NULL pointer");
+    const bool lists = grid != nullptr;
+    const size_t G = lists ? (size_t)grid_cells(grid) : 0;
+    const size_t items = lists ? (size_t)(cell_start[G] < 0 ? 0 : cell_start[G]) : 0;
+    if (items && !cell_items) return fail(PLP_EINVAL, "NULL pointer");
+    double *dlb, *dub;
+    int32_t *dcs, *dci, *dpairs;
+    int64_t* dpc;
+    HostCall hc(ctx);
+    hc.in(dlb, lb, (size_t)n * d);
+    hc.in(dub, ub, (size_t)n * d);
+    hc.in(dcs, lists ? cell_start : nullptr, G + 1);
+    hc.in(dci, items ? cell_items : nullptr, items);
+    hc.in(dpc, per_cell, (size_t)n + 1);
+    hc.out(dpairs, pairs, (size_t)K * 2);
+    hc.direct_out = true;
+    rc = hc.reserve();
+    if (rc) return rc;
+    rc = hc.upload();
+    if (rc) return rc;
+    rc = plp_box_pairs_fill_dev(ctx, hc.st, n, d, dlb, dub, pad, grid, dcs, dci, n1, dpc, cell_lo, cell_hi, dpairs);
+    if (rc) return rc;
+    return hc.download();
+}
+
 int plp_selftest(plp_ctx* ctx, int group_size, double* out_d, uint32_t* out_u) {
     if (!ctx || !out_d || !out_u) return fail(PLP_EINVAL, "NULL pointer");
     double* dd;

@@ -26,4 +26,15 @@ int launch_adjacent_r(int d, const LpLaunch& L, int force_retry, const PairArgs&
     });
 }
 
+// the listed form (a.list, a.p_hi pairs into a.compact)
+int launch_adjacent_r_list(int d, const LpLaunch& L, int force_retry, const PairArgs& a, hipStream_t st) {
+    return for_dim<1, 8>(d, [&](auto K) {
+        constexpr int D = decltype(K)::value;
+        return for_gs<RowsPerLane<D>::value>(L.gs, [&](auto G) {
+            hipLaunchKernelGGL((adjacent_r_list_kernel<D, decltype(G)::value>), dim3((unsigned)L.grid), dim3(L.block), L.lds, st,
+                               a.n, a.m_max, a.A, a.b, a.mrows, a.inflate, a.thresh, a.p_hi, a.list, a.compact, force_retry, a.mark);
+        });
+    });
+}
+
 }  // namespace plp

@@ -7,6 +7,7 @@
 //   cheby_r_kernel<D,GS>    : a batch of polytopes (cheby_ball / is_fulldim, :1241-1300, :962-985)
 //   adjacent_r_kernel<D,GS> : all pairs of n cells (is_adjacent(overlap=True), :1843-1866, under the pair
 //                             loop of find_adjacent_regions, prop2partition.py:57-61)
+//   adjacent_r_list_kernel<D,GS> : the same LP for a caller's list of pairs (plp_pair_list)
 //
 // A polytope (or a stacked pair) of up to 16 / 32 / 64 rows takes a group of GS = 4 / 8 / 16 lanes, lane l
 // holding rows 4l..4l+3 in VGPRs, so a wavefront carries 16 / 8 / 4 LPs (plp_simplex_r.hpp).  The LP runs
@@ -15,6 +16,7 @@
 // solves it with the general engine, behind a wave-uniform branch that is almost never taken.
 #pragma once
 #include "plp_lp_launch.hpp"
+#include "plp_pair_index.hpp"
 #include "plp_simplex_r.hpp"
 
 namespace plp {
@@ -313,29 +315,22 @@ __global__ __launch_bounds__(RBLK, (D <= 4 ? 3 : 1)) void bbox_split_kernel(long
 // nothing is staged by the host.  adj is n x n, symmetric, ones on the diagonal; with `compact` set the
 // kernel instead solves the pairs p_lo <= p < p_hi (p = i (i - 1) / 2 + j) and writes compact[p - p_lo]
 // (the shard of one rank when the pair space is split across GPUs).
-template <int D, int GS>
-__global__ __launch_bounds__(RBLK, (D <= 4 ? 3 : 1)) void adjacent_r_kernel(
+// `list` (LISTED, plp_pair_list): pair t of the launch is (list[2 t], list[2 t + 1]), verdicts go to compact[t]; the p -> (i, j)
+// map of both forms is plp_pair_index.hpp's.
+template <int D, int GS, bool LISTED>
+__device__ __forceinline__ void adjacent_r_body(
     int n, int m_max, const double* __restrict__ A, const double* __restrict__ b, const int* __restrict__ mrows,
     double inflate, double thresh, unsigned char* __restrict__ adj, long long p_lo, long long p_hi,
-    unsigned char* __restrict__ compact, int force_retry, int cross_n1, int mark) {
+    unsigned char* __restrict__ compact, int force_retry, int cross_n1, int mark, const int* __restrict__ list) {
     const Grp g(GS);
     constexpr int gpb = RBLK / GS;
     const int gib = threadIdx.x / GS;
     constexpr int R = RowsPerLane<D>::value;
     const int row0 = g.gl * R;
     const long long p = p_lo + (long long)blockIdx.x * gpb + gib;
-    const bool valid = p < p_hi;
-    // p -> (i, j) with j < i, p = i (i - 1) / 2 + j;  cross pairs (cross_n1 > 0, compact only): the table holds two lists,
-    // n1 cells then n - n1 cells, and p = a (n - n1) + c pairs cell a of the first with cell c of the second
-    long long i = valid ? (long long)((1.0 + sqrt(1.0 + 8.0 * (double)p)) * 0.5) : 1;
-    while (i * (i - 1) / 2 > p) --i;
-    while ((i + 1) * i / 2 <= p) ++i;
-    long long j = valid ? p - i * (i - 1) / 2 : 0;
-    if (cross_n1 > 0) {
-        const long long n2 = n - cross_n1;
-        i = valid ? p / n2 : 0;
-        j = valid ? cross_n1 + (p - i * n2) : 0;
-    }
+    const bool inrange = p < p_hi;
+    long long i, j;
+    const bool valid = pair_cells<LISTED>(p, inrange, n, cross_n1, list, i, j);
     const int mi = valid ? (mrows ? mrows[i] : m_max) : 0;
     const int mj = valid ? (mrows ? mrows[j] : m_max) : 0;
     double x[D + 1];
@@ -347,6 +342,10 @@ __global__ __launch_bounds__(RBLK, (D <= 4 ? 3 : 1)) void adjacent_r_kernel(
     const bool yes = (st == ST_OPT) & (x[D] > thresh);
     // (mark: "unbounded" / the iteration limit is not a verdict -- the careful pass that follows decides, plp_kernels.hpp)
     const unsigned char verdict = yes ? 1 : ((mark != 0) & ((st == ST_UNBND) | (st == ST_ITER)) ? PAIR_OPEN : 0);
+    if constexpr (LISTED) {
+        if (inrange & (g.gl == 0)) compact[p - p_lo] = valid ? verdict : PAIR_BAD;
+        return;
+    }
     if (compact) {
         if (valid & (g.gl == 0)) compact[p - p_lo] = verdict;
         return;
@@ -358,6 +357,24 @@ __global__ __launch_bounds__(RBLK, (D <= 4 ? 3 : 1)) void adjacent_r_kernel(
     // diagonal
     const long long t = (long long)blockIdx.x * RBLK + threadIdx.x;
     if (t < n) adj[t * n + t] = 1;
+}
+
+template <int D, int GS>
+__global__ __launch_bounds__(RBLK, (D <= 4 ? 3 : 1)) void adjacent_r_kernel(
+    int n, int m_max, const double* __restrict__ A, const double* __restrict__ b, const int* __restrict__ mrows,
+    double inflate, double thresh, unsigned char* __restrict__ adj, long long p_lo, long long p_hi,
+    unsigned char* __restrict__ compact, int force_retry, int cross_n1, int mark) {
+    adjacent_r_body<D, GS, false>(n, m_max, A, b, mrows, inflate, thresh, adj, p_lo, p_hi, compact, force_retry, cross_n1, mark,
+                                  nullptr);
+}
+
+// the listed pairs list[K][2] into out[K] (plp_pair_list): the same lane groups, LP and verdict bytes
+template <int D, int GS>
+__global__ __launch_bounds__(RBLK, (D <= 4 ? 3 : 1)) void adjacent_r_list_kernel(
+    int n, int m_max, const double* __restrict__ A, const double* __restrict__ b, const int* __restrict__ mrows,
+    double inflate, double thresh, long long K, const int* __restrict__ list, unsigned char* __restrict__ out,
+    int force_retry, int mark) {
+    adjacent_r_body<D, GS, true>(n, m_max, A, b, mrows, inflate, thresh, nullptr, 0, K, out, force_retry, 0, mark, list);
 }
 
 // the LPs that need phase 1 stay on the fast path for n = 3..PLP_P1_FAST_MAXN (plp_lp_plan.hpp)

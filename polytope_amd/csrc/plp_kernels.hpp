@@ -119,7 +119,12 @@ size_t pair_careful_scratch_bytes();
 // what launch_adjacent wrote with the pairs marked PAIR_OPEN: those pairs decided by the careful engine, one pair per thread
 void launch_careful_pairs(int n, int m_max, int d, const double* A, const double* b, const int* mrows, double inflate,
                           double thresh, unsigned char* adj, long long p_lo, long long p_hi, unsigned char* compact,
-                          int cross_n1, void* scratch, hipStream_t st);
+                          int cross_n1, void* scratch, hipStream_t st, const int* list = nullptr);
+// the listed form (plp_pair_list): out[t] = the verdict the calls above give pair (list[2 t], list[2 t + 1]), through the same
+// engines (plan_pair_list picks among them by K) and the same careful pass; PAIR_BAD for a pair with an index outside
+// [0, n) or two equal ones, for which nothing is read
+int launch_pair_list(int n, int m_max, int d, const double* A, const double* b, const int* mrows, double inflate, double thresh,
+                     long long K, const int* list, unsigned char* out, hipStream_t st, void* careful_scratch = nullptr);
 
 // Fused reduce() of up to 64 rows (plp_reduce.hip).  The batch, the outputs, and what the fast kernels report besides:
 struct ReduceArgs {
@@ -163,6 +168,15 @@ int launch_locate_grid_count(int P, int d, const double* lb, const double* ub, d
 // cell_items[cell_start[G]], every list ascending; cursor[G]: scratch
 int launch_locate_grid_fill(int P, int d, const double* lb, const double* ub, double pad, const plp_locate_grid* grid,
                             const int* cell_start, int* cursor, int* cell_items, hipStream_t st);
+
+// the broad phase of the sparse pair calls (plp_box_pairs.hip): per_cell[n + 1], the exclusive prefix sums of the cells'
+// numbers of partners whose padded box meets theirs; the pairs of cells [cell_lo, cell_hi) at per_cell[i] - per_cell[cell_lo].
+// grid == nullptr: every partner box-tested.  Return 0, 2 for bad sizes, 3 when hipMemsetAsync failed.
+int launch_box_pairs_count(int n, int d, const double* lb, const double* ub, double pad, const plp_locate_grid* grid,
+                           const int* cell_start, const int* cell_items, int n1, long long* per_cell, hipStream_t st);
+int launch_box_pairs_fill(int n, int d, const double* lb, const double* ub, double pad, const plp_locate_grid* grid,
+                          const int* cell_start, const int* cell_items, int n1, const long long* per_cell, int cell_lo,
+                          int cell_hi, int* pairs, hipStream_t st);
 
 int launch_assign(long long N, int d, const double* X, int F, const double* normals, const double* offsets,
                   double abs_tol, int* facet_of_point, double* dist, long long* argmax, double* maxd,

@@ -273,4 +273,21 @@ int launch_adjacent(int n, int m_max, int d, const double* A, const double* b, c
     return rc;
 }
 
+// the listed pairs list[K][2] into out[K]
+int launch_pair_list(int n, int m_max, int d, const double* A, const double* b, const int* mrows, double inflate, double thresh,
+                     long long K, const int* list, unsigned char* out, hipStream_t st, void* careful_scratch) {
+    const PairPlan p = plan_pair_list(n, m_max, d, K, lp_env());
+    const PairArgs a{n, m_max, A, b, mrows, inflate, thresh, nullptr, 0, K, out, 0, careful_scratch ? 1 : 0, list};
+    int rc;
+    switch (p.first.engine) {
+        case LE_EMPTY: return 0;
+        case LE_WIDE: rc = launch_adjacent_w_list(d, p.first, a, st); break;
+        case LE_GROUP: rc = launch_adjacent_r_list(d, p.first, p.force_retry, a, st); break;
+        default: return 2;
+    }
+    if (rc == 0 && careful_scratch)
+        launch_careful_pairs(n, m_max, d, A, b, mrows, inflate, thresh, nullptr, 0, K, out, 0, careful_scratch, st, list);
+    return rc;
+}
+
 }  // namespace plp

@@ -25,6 +25,7 @@ struct PairArgs {
     unsigned char* compact;
     int cross_n1;
     int mark;   // an LP that ends "unbounded" or at the iteration limit is written as PAIR_OPEN (the careful pass follows), not 0
+    const int* list = nullptr;   // the listed form (plp_pair_list): p_hi pairs (list[2 t], list[2 t + 1]) into compact[t]
 };
 
 // f(std::integral_constant<int, K>()) for K == d in LO .. HI -> what f returns (0 when nothing); 2 when d is outside (the
@@ -77,5 +78,8 @@ int launch_bbox_r(int d, const LpLaunch& L, int force_retry, const BoxArgs& a, h
 // pairs: adjacent_r_kernel (plp_cheby_r.hip), adjacent_w_kernel (plp_wide.hip)
 int launch_adjacent_r(int d, const LpLaunch& L, int force_retry, const PairArgs& a, hipStream_t st);
 int launch_adjacent_w(int d, const LpLaunch& L, const PairArgs& a, hipStream_t st);
+// ... and their listed instantiations, adjacent_r_list_kernel / adjacent_w_list_kernel
+int launch_adjacent_r_list(int d, const LpLaunch& L, int force_retry, const PairArgs& a, hipStream_t st);
+int launch_adjacent_w_list(int d, const LpLaunch& L, const PairArgs& a, hipStream_t st);
 
 }  // namespace plp

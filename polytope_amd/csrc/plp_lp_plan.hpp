@@ -1,8 +1,9 @@
 // plp_lp_plan.hpp -- which kernels the stand-alone LP, Chebyshev-ball, bounding-box and pair batches run, decided in one place.
 //
-// plan_lp / plan_cheby / plan_bbox / plan_pairs are pure host functions (no HIP): each names the engine, its tile shape,
-// grid, workgroup and LDS bytes, and what follows the first launch.  The launchers (plp_lp.hip and the translation units of
-// the kernels, plp_lp_launch.hpp) only carry the plan out.  tests/test_lp_plan.py pins it on the CPU.
+// plan_lp / plan_cheby / plan_bbox / plan_pairs / plan_pair_list are pure host functions (no HIP): each names the engine,
+// its tile shape, grid, workgroup and LDS bytes, and what follows the first launch.  The launchers (plp_lp.hip and the
+// translation units of the kernels, plp_lp_launch.hpp) only carry the plan out.  tests/test_lp_plan.py pins it on the CPU
+// (plan_pair_list: tests/test_box_pairs_host.py).
 //
 // The engines, by shape (defaults; rows = m_max, for pairs the stacked 2 m_max):
 //   generic LPs   rows > 64      LDS: dictionary in LDS, one LP per wavefront (lp_lds_kernel), complete; NONE when the
@@ -272,6 +273,21 @@ inline LpLaunch plan_general(long long B, int m_max) {
     return launch(LE_GENERAL, gs, 1, at_least1(blocks), LP_GENERAL_BLOCK, 0);
 }
 
+// the engine of `count` pair LPs over n cells of up to m_max rows each (L stays LE_NONE when none applies):
+// d >= 9 (no lane-group kernel), and d = 5..8 when the stacked pair has more than 32 rows or the pairs are few: one
+// pair per wavefront (plp_wide.hip), the rule of the Chebyshev batches.  PLP_ADJ_WIDE=0 / 1: A/B, tests
+inline void plan_pair_engine(long long count, int n, int m_max, int d, bool compact, const LpEnv& env, LpLaunch& L) {
+    const bool wide = d > 8 || (d >= 5 && (env.adj_wide ? env.adj_wide[0] == '1'
+                                                        : (2 * m_max > ADJ_WIDE_MIN_ROWS || count <= ADJ_WIDE_SMALL_PAIRS)));
+    const long long wdiag = compact ? 0 : cdiv(n, 64);
+    const long long wblocks = at_least1(count > wdiag ? count : wdiag);
+    if (wide && wblocks <= LP_MAX_GRID) {
+        L = launch(LE_WIDE, 64, 1, wblocks, 64, 0);
+        return;
+    }
+    if (d <= 8) plan_lane_group(count, 2 * m_max, 4, compact ? 0 : cdiv(n, RBLK), L);
+}
+
 }  // namespace plan_detail
 
 // ---- generic LPs  min c'x  s.t.  G x <= h  (plp_lp_solve_batch)
@@ -391,17 +407,23 @@ inline PairPlan plan_pairs(int n, int m_max, int d, long long p_lo, long long p_
         p.first.engine = LE_EMPTY;
         return p;
     }
-    // d >= 9 (no lane-group kernel), and d = 5..8 when the stacked pair has more than 32 rows or the pairs are few: one
-    // pair per wavefront (plp_wide.hip), the rule of the Chebyshev batches.  PLP_ADJ_WIDE=0 / 1: A/B, tests
-    const bool wide = d > 8 || (d >= 5 && (env.adj_wide ? env.adj_wide[0] == '1'
-                                                        : (2 * m_max > ADJ_WIDE_MIN_ROWS || p_hi - p_lo <= ADJ_WIDE_SMALL_PAIRS)));
-    const long long wdiag = compact ? 0 : cdiv(n, 64);
-    const long long wblocks = at_least1(p_hi - p_lo > wdiag ? p_hi - p_lo : wdiag);
-    if (wide && wblocks <= LP_MAX_GRID) {
-        p.first = launch(LE_WIDE, 64, 1, wblocks, 64, 0);
+    plan_pair_engine(p_hi - p_lo, n, m_max, d, compact, env, p.first);
+    return p;
+}
+
+// ---- the listed form (plp_pair_list): K pairs of the n cells, each named by its two indices; the engines and the rule that
+// picks among them are plan_pairs', sized by K (a list may name a pair more than once: K has no bound but the grid's)
+inline PairPlan plan_pair_list(int n, int m_max, int d, long long K, const LpEnv& env) {
+    using namespace plan_detail;
+    PairPlan p;
+    p.force_retry = lp_force_retry(env);
+    if (n < 0 || m_max < 1 || 2 * m_max > LP_MAX_M || d < 1 || d > LP_MAX_D || K < 0) return p;
+    p.p_hi = K;
+    if (K == 0) {
+        p.first.engine = LE_EMPTY;
         return p;
     }
-    if (d <= 8) plan_lane_group(p_hi - p_lo, 2 * m_max, 4, compact ? 0 : cdiv(n, RBLK), p.first);
+    plan_pair_engine(K, n, m_max, d, true, env, p.first);
     return p;
 }
 

@@ -18,6 +18,7 @@
 #include <stdlib.h>
 
 #include "plp_kernels.hpp"
+#include "plp_pair_index.hpp"
 #include "plp_verify.hpp"
 
 namespace plp {
@@ -382,29 +383,28 @@ __global__ __launch_bounds__(VBLK) void careful_kernel(int m_max, int n, const d
 constexpr long long PAIR_SLOTS = 1024;
 constexpr size_t PAIR_STAGE = (size_t)MAX_M * (MAX_D + 1);   // doubles per thread: 64 rows of up to 16 entries, then 64 right-hand sides
 
-__global__ __launch_bounds__(VBLK) void careful_pairs_kernel(int n, int m_max, int d, const double* __restrict__ A,
-                                                             const double* __restrict__ b, const int* __restrict__ mrows,
-                                                             double inflate, double thresh, unsigned char* __restrict__ adj,
-                                                             long long p_lo, long long p_hi, unsigned char* __restrict__ compact,
-                                                             int cross_n1, double* hi, double* lo, int* rowinfo, double* stage) {
+// `list` (LISTED, plp_pair_list): pair t is (list[2 t], list[2 t + 1]) and its byte compact[t].
+template <bool LISTED>
+__device__ __forceinline__ void careful_pairs_body(int n, int m_max, int d, const double* __restrict__ A,
+                                                   const double* __restrict__ b, const int* __restrict__ mrows,
+                                                   double inflate, double thresh, unsigned char* __restrict__ adj,
+                                                   long long p_lo, long long p_hi, unsigned char* __restrict__ compact,
+                                                   int cross_n1, double* hi, double* lo, int* rowinfo, double* stage,
+                                                   const int* __restrict__ list) {
     const long long slot = (long long)blockIdx.x * VBLK + threadIdx.x;
     if (slot >= PAIR_SLOTS) return;
     CarefulMem M{hi + slot, lo + slot, rowinfo + slot, PAIR_SLOTS};
     double* G = stage + (size_t)slot * PAIR_STAGE;
     double* h = G + (size_t)MAX_M * MAX_D;
     for (long long p = p_lo + slot; p < p_hi; p += PAIR_SLOTS) {
-        // p -> (i, j) as the engines' kernels map it (adjacent_r_kernel, plp_cheby_r_impl.hpp)
-        long long i = (long long)((1.0 + sqrt(1.0 + 8.0 * (double)p)) * 0.5);
-        while (i * (i - 1) / 2 > p) --i;
-        while ((i + 1) * i / 2 <= p) ++i;
-        long long j = p - i * (i - 1) / 2;
-        if (cross_n1 > 0) {
-            const long long n2 = n - cross_n1;
-            i = p / n2;
-            j = cross_n1 + (p - i * n2);
-        }
+        // p -> (i, j) as the engines' kernels map it (plp_pair_index.hpp)
+        long long i, j;
+        const bool known = pair_cells<LISTED>(p, true, n, cross_n1, list, i, j);
         unsigned char* out = compact ? compact + (p - p_lo) : adj + i * n + j;
         if (*out != PAIR_OPEN) continue;
+        if constexpr (LISTED) {
+            if (!known) continue;  // (the engines wrote PAIR_BAD for it: never open)
+        }
         const int mi = mrows ? mrows[i] : m_max, mj = mrows ? mrows[j] : m_max;
         const int m = mi + mj;
         bool yes = false;
@@ -434,6 +434,33 @@ __global__ __launch_bounds__(VBLK) void careful_pairs_kernel(int n, int m_max, i
     }
 }
 
+__global__ __launch_bounds__(VBLK) void careful_pairs_kernel(int n, int m_max, int d, const double* __restrict__ A,
+                                                             const double* __restrict__ b, const int* __restrict__ mrows,
+                                                             double inflate, double thresh, unsigned char* __restrict__ adj,
+                                                             long long p_lo, long long p_hi, unsigned char* __restrict__ compact,
+                                                             int cross_n1, double* hi, double* lo, int* rowinfo, double* stage) {
+    careful_pairs_body<false>(n, m_max, d, A, b, mrows, inflate, thresh, adj, p_lo, p_hi, compact, cross_n1, hi, lo, rowinfo, stage,
+                              nullptr);
+}
+
+// (the listed instantiation stays a function of its own, called by its kernel: inlined into a second kernel of this unit it
+// ends hipcc 7.2's inliner with a segmentation fault)
+__device__ __noinline__ void careful_pair_list_body(int n, int m_max, int d, const double* __restrict__ A,
+                                                    const double* __restrict__ b, const int* __restrict__ mrows, double inflate,
+                                                    double thresh, long long K, const int* __restrict__ list,
+                                                    unsigned char* __restrict__ out, double* hi, double* lo, int* rowinfo,
+                                                    double* stage) {
+    careful_pairs_body<true>(n, m_max, d, A, b, mrows, inflate, thresh, nullptr, 0, K, out, 0, hi, lo, rowinfo, stage, list);
+}
+
+__global__ __launch_bounds__(VBLK) void careful_pair_list_kernel(int n, int m_max, int d, const double* __restrict__ A,
+                                                                 const double* __restrict__ b, const int* __restrict__ mrows,
+                                                                 double inflate, double thresh, long long K,
+                                                                 const int* __restrict__ list, unsigned char* __restrict__ out,
+                                                                 double* hi, double* lo, int* rowinfo, double* stage) {
+    careful_pair_list_body(n, m_max, d, A, b, mrows, inflate, thresh, K, list, out, hi, lo, rowinfo, stage);
+}
+
 bool verify_off() {
     static const int off = [] {
         const char* e = getenv("PLP_VERIFY");
@@ -460,7 +487,7 @@ size_t pair_careful_scratch_bytes() {
 
 void launch_careful_pairs(int n, int m_max, int d, const double* A, const double* b, const int* mrows, double inflate,
                           double thresh, unsigned char* adj, long long p_lo, long long p_hi, unsigned char* compact,
-                          int cross_n1, void* scratch, hipStream_t st) {
+                          int cross_n1, void* scratch, hipStream_t st, const int* list) {
     if (p_hi <= p_lo) return;
     const size_t nd = careful_doubles_per_lp(MAX_M) * PAIR_SLOTS;
     char* p = static_cast<char*>(scratch) + 256;
@@ -473,8 +500,12 @@ void launch_careful_pairs(int n, int m_max, int d, const double* A, const double
     double* stage = reinterpret_cast<double*>(p);
     long long blocks = (p_hi - p_lo + VBLK - 1) / VBLK;
     if (blocks > PAIR_SLOTS / VBLK) blocks = PAIR_SLOTS / VBLK;
-    hipLaunchKernelGGL(careful_pairs_kernel, dim3((unsigned)blocks), dim3(VBLK), 0, st, n, m_max, d, A, b, mrows, inflate, thresh,
-                       adj, p_lo, p_hi, compact, cross_n1, hi, lo, rowinfo, stage);
+    if (list)
+        hipLaunchKernelGGL(careful_pair_list_kernel, dim3((unsigned)blocks), dim3(VBLK), 0, st, n, m_max, d, A, b, mrows, inflate,
+                           thresh, p_hi, list, compact, hi, lo, rowinfo, stage);
+    else
+        hipLaunchKernelGGL(careful_pairs_kernel, dim3((unsigned)blocks), dim3(VBLK), 0, st, n, m_max, d, A, b, mrows, inflate,
+                           thresh, adj, p_lo, p_hi, compact, cross_n1, hi, lo, rowinfo, stage);
 }
 
 // ---- the same for LPs of N <= 5 columns (d <= 4: most of what the library is asked): ONE LP PER LANE, the column count a

@@ -19,6 +19,7 @@
 #include <stdlib.h>
 
 #include "plp_lp_launch.hpp"
+#include "plp_pair_index.hpp"
 #include "plp_wave.hpp"
 #include "plp_wide.hpp"
 
@@ -162,12 +163,13 @@ int launch_cheby_gather_w(int d, long long nlp, const int* off, const int* rows,
 // prop2partition.py:57-61), one pair per wavefront: the rows of cell i and of cell j stacked (at most 64), every b
 // inflated, adjacent iff the Chebyshev radius exceeds `thresh` -- the contract of adjacent_r_kernel (plp_cheby_r_impl.hpp),
 // for d = 5..16 (the lane-group kernel stops at d = 8 and holds one or two such LPs per wavefront from 33 rows on).
-template <int D>
-__global__ __launch_bounds__(64) void adjacent_w_kernel(int n, int m_max, const double* __restrict__ A,
-                                                        const double* __restrict__ b, const int* __restrict__ mrows,
-                                                        double inflate, double thresh, unsigned char* __restrict__ adj,
-                                                        long long p_lo, long long p_hi, unsigned char* __restrict__ compact,
-                                                        int cross_n1, int mark) {
+// `list` (LISTED, plp_pair_list): pair t of the launch is (list[2 t], list[2 t + 1]), verdicts go to compact[t].
+template <int D, bool LISTED>
+__device__ __forceinline__ void adjacent_w_body(int n, int m_max, const double* __restrict__ A,
+                                                const double* __restrict__ b, const int* __restrict__ mrows,
+                                                double inflate, double thresh, unsigned char* __restrict__ adj,
+                                                long long p_lo, long long p_hi, unsigned char* __restrict__ compact,
+                                                int cross_n1, int mark, const int* __restrict__ list) {
     constexpr int NC = D + 1;
     __shared__ WideShared<NC> sh;
     const int lane = threadIdx.x;
@@ -177,15 +179,14 @@ __global__ __launch_bounds__(64) void adjacent_w_kernel(int n, int m_max, const 
     }
     const long long p = p_lo + (long long)blockIdx.x;
     if (p >= p_hi) return;
-    // p -> (i, j) with j < i, p = i (i - 1) / 2 + j
-    long long i = (long long)((1.0 + sqrt(1.0 + 8.0 * (double)p)) * 0.5);
-    while (i * (i - 1) / 2 > p) --i;
-    while ((i + 1) * i / 2 <= p) ++i;
-    long long j = p - i * (i - 1) / 2;
-    if (cross_n1 > 0) {   // two lists in one table (see adjacent_r_kernel): cell i of the first with cell j of the second
-        const long long n2 = n - cross_n1;
-        i = p / n2;
-        j = cross_n1 + (p - i * n2);
+    // p -> (i, j): plp_pair_index.hpp (two lists in one table, cross_n1 > 0: cell i of the first with cell j of the second)
+    long long i, j;
+    const bool known = pair_cells<LISTED>(p, true, n, cross_n1, list, i, j);
+    if constexpr (LISTED) {
+        if (!known) {  // (the whole wavefront: one pair per workgroup)
+            if (lane == 0) compact[p - p_lo] = PAIR_BAD;
+            return;
+        }
     }
     const int mi = mrows ? mrows[i] : m_max;
     const int mj = mrows ? mrows[j] : m_max;
@@ -238,11 +239,38 @@ __global__ __launch_bounds__(64) void adjacent_w_kernel(int n, int m_max, const 
     }
 }
 
+template <int D>
+__global__ __launch_bounds__(64) void adjacent_w_kernel(int n, int m_max, const double* __restrict__ A,
+                                                        const double* __restrict__ b, const int* __restrict__ mrows,
+                                                        double inflate, double thresh, unsigned char* __restrict__ adj,
+                                                        long long p_lo, long long p_hi, unsigned char* __restrict__ compact,
+                                                        int cross_n1, int mark) {
+    adjacent_w_body<D, false>(n, m_max, A, b, mrows, inflate, thresh, adj, p_lo, p_hi, compact, cross_n1, mark, nullptr);
+}
+
+// the listed pairs list[K][2] into out[K] (plp_pair_list): the same wavefront LP and verdict bytes
+template <int D>
+__global__ __launch_bounds__(64) void adjacent_w_list_kernel(int n, int m_max, const double* __restrict__ A,
+                                                             const double* __restrict__ b, const int* __restrict__ mrows,
+                                                             double inflate, double thresh, long long K,
+                                                             const int* __restrict__ list, unsigned char* __restrict__ out,
+                                                             int mark) {
+    adjacent_w_body<D, true>(n, m_max, A, b, mrows, inflate, thresh, nullptr, 0, K, out, 0, mark, list);
+}
+
 // one pair per wavefront, d = 5..16: L.grid covers the pairs and, in the matrix form, the diagonal
 int launch_adjacent_w(int d, const LpLaunch& L, const PairArgs& a, hipStream_t st) {
     return for_dim<5, MAX_D>(d, [&](auto K) {
         hipLaunchKernelGGL((adjacent_w_kernel<decltype(K)::value>), dim3((unsigned)L.grid), dim3(L.block), L.lds, st, a.n, a.m_max,
                            a.A, a.b, a.mrows, a.inflate, a.thresh, a.adj, a.p_lo, a.p_hi, a.compact, a.cross_n1, a.mark);
+    });
+}
+
+// the listed form (a.list, a.p_hi pairs into a.compact)
+int launch_adjacent_w_list(int d, const LpLaunch& L, const PairArgs& a, hipStream_t st) {
+    return for_dim<5, MAX_D>(d, [&](auto K) {
+        hipLaunchKernelGGL((adjacent_w_list_kernel<decltype(K)::value>), dim3((unsigned)L.grid), dim3(L.block), L.lds, st, a.n,
+                           a.m_max, a.A, a.b, a.mrows, a.inflate, a.thresh, a.p_hi, a.list, a.compact, a.mark);
     });
 }
 

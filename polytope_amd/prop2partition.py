@@ -278,6 +278,46 @@ def find_adjacent_regions(partition):
     return _adjacency_lil(_regions_of(partition), np.int8, owner=partition if hasattr(partition, "__dict__") else None)
 
 
+def _pairs_csr(partition, kind, abs_tol):
+    """The region pairs for which some member pair is set, from the sparse pair screens (batch.adjacent_pairs_sparse /
+    overlap_pairs_sparse: only member pairs whose boxes meet are solved, no n x n matrix) -> csr_matrix, int8, symmetric,
+    ones on the diagonal."""
+    from . import batch
+    from ._lib import UnsupportedSize
+    regions = _regions_of(partition)
+    n = len(regions)
+    owner = partition if hasattr(partition, "__dict__") else None
+    members, first, ok = _flat_members(regions, owner)
+    r = c = np.zeros(0, dtype=np.int64)
+    if len(members) >= 2:
+        if not ok:
+            raise UnsupportedSize("%s_sparse: the member polytopes must share one dimension d <= 16 and have 1..32 rows each"
+                                  % ("adjacency" if kind == "adjacent" else "overlap"))
+        At, bt, mt = pc._table_of(members, owner=owner if len(members) == len(regions) else None).dev()
+        fn = batch.adjacent_pairs_sparse if kind == "adjacent" else batch.overlap_pairs_sparse
+        pairs = fn(At, bt, m=mt, abs_tol=abs_tol)["pairs"]
+        pairs = pairs if isinstance(pairs, np.ndarray) else pairs.cpu().numpy()
+        # fold the member pairs to the elements (any member pair), as _pair_list_device does
+        of = np.repeat(np.arange(n), np.diff(first))
+        r, c = of[pairs[:, 0]], of[pairs[:, 1]]
+    code = np.unique(np.concatenate([r * n + c, c * n + r, np.arange(n) * (n + 1)]))
+    return sp.csr_matrix((np.ones(code.size, dtype=np.int8), (code // n, code % n)), shape=(n, n))
+
+
+def adjacency_sparse(partition, abs_tol=pc.ABS_TOL):
+    """The adjacency of a partition's regions as a scipy.sparse.csr_matrix (n x n, int8, ones on the diagonal), equal to
+    find_adjacent_regions(partition).tocsr() -- through the box-culled pair screen: only the member pairs whose bounding
+    boxes meet are solved, and nothing of size n^2 is formed.  Raises UnsupportedSize for member polytopes the pair kernels
+    do not take (more than 32 rows, d > 16, mixed dimensions)."""
+    return _pairs_csr(partition, "adjacent", abs_tol)
+
+
+def overlap_sparse(partition, abs_tol=pc.ABS_TOL):
+    """is_fulldim(regions[i].intersect(regions[j])) for the pairs of a partition's regions, as a csr_matrix (n x n, int8,
+    ones on the diagonal) equal to the nonzero pattern of overlap_matrix_dense -- through the box-culled pair screen."""
+    return _pairs_csr(partition, "overlap", abs_tol)
+
+
 ################################
 
 
