@@ -568,6 +568,45 @@ int plp_box_pairs_fill_dev(plp_ctx *ctx, void *stream, int n, int d, const doubl
                            const int64_t *per_cell, int cell_lo, int cell_hi, int32_t *pairs);
 
 /*
+ * The STACKS of a list of cell pairs: for pair t = (pairs[t][0], pairs[t][1]) = (i, j) of the n cells, what
+ * Polytope(np.vstack([A_i, A_j]), np.hstack([b_i, b_j])) holds (polytope.py:272-275, constructor :130-138): the m_i rows
+ * of cell i, then the m_j rows of cell j, each scaled by the reciprocal of its norm (sqrt of numpy's add.reduce of the
+ * squares), rows of norm <= 1e-10 dropped and the rows behind them moved up.  W = 2 * m_max row slots per stack:
+ * A_s[K][W][d], b_s[K][W], m_s[K] = rows that stay; rows from m_s[t] on are zero.  A packed table like any other: it goes
+ * into plp_cheby_batch, plp_reduce_batch, plp_volume_hits, ... as it is.  2 * m_max <= 64, d <= 16 (else
+ * PLP_EUNSUPPORTED).  A pair may be listed more than once and in either order (the order decides the row order).
+ * A pair with an index outside [0, n) or with two equal indices: the host-pointer call returns PLP_EINVAL before anything
+ * runs; the device-pointer call reads nothing of the table for it and writes m_s = 0 and zero rows.
+ */
+int plp_pair_stacks(plp_ctx *ctx, int n, int m_max, int d, const double *A, const double *b, const int32_t *m, int64_t K,
+                    const int32_t *pairs, double *A_s, double *b_s, int32_t *m_s);
+int plp_pair_stacks_dev(plp_ctx *ctx, void *stream, int n, int m_max, int d, const double *A, const double *b,
+                        const int32_t *m, int64_t K, const int32_t *pairs, double *A_s, double *b_s, int32_t *m_s);
+
+/*
+ * The INTERSECTIONS of a list of cell pairs: per pair exactly what plp_reduce_batch returns for the stack above --
+ * keep[K] (bit s = stack row s; where ms[t] == m_i + m_j the first m_i bits are cell i's rows), flags[K], r[K], xc[K][d],
+ * nlp[K] -- and ms[K], the rows of the stack.  With A_out != NULL also the result's rows as plp_fm_emit(col = -1) forms
+ * them from the reduce's keep and flags: A_out[K][mo_max][d], b_out[K][mo_max], m_out[K] (-1: more than mo_max rows; 0 under
+ * PLP_RF_EMPTY / PLP_RF_LPFAIL / PLP_RF_F1OPEN), a packed table again.
+ * The list is worked off in chunks of at most `chunk` pairs (chunk <= 0: the library's default, 32 MiB of stacks): stack ->
+ * fused reduce -> emission, the stacks of one chunk in per-stream scratch; the stacks of the whole list are never resident.
+ * Bad pairs as above; the device-pointer call writes keep = 0, flags = PLP_RF_EMPTY | PLP_RF_BADPAIR, r = 0, xc = NaN,
+ * nlp = 0, ms = 0, m_out = 0 for such a pair and the other pairs of the list are not affected.
+ */
+#define PLP_RF_BADPAIR 64
+/* the chunk plp_intersect_pairs uses for chunk <= 0 at this table shape (pairs; needs no context) */
+int64_t plp_pair_chunk_default(int m_max, int d);
+int plp_intersect_pairs(plp_ctx *ctx, int n, int m_max, int d, const double *A, const double *b, const int32_t *m,
+                        double abs_tol, int64_t K, const int32_t *pairs, int64_t chunk, uint64_t *keep, int32_t *flags,
+                        double *r, double *xc, int32_t *nlp, int32_t *ms, int mo_max, double *A_out, double *b_out,
+                        int32_t *m_out);
+int plp_intersect_pairs_dev(plp_ctx *ctx, void *stream, int n, int m_max, int d, const double *A, const double *b,
+                            const int32_t *m, double abs_tol, int64_t K, const int32_t *pairs, int64_t chunk,
+                            uint64_t *keep, int32_t *flags, double *r, double *xc, int32_t *nlp, int32_t *ms, int mo_max,
+                            double *A_out, double *b_out, int32_t *m_out);
+
+/*
  * Quickhull's main loop (polytope/quickhull.py:224-345) as native host code over a plp_hull session: facet graph,
  * visibility search, horizon, new facets and their links on the host, every pass over the points one plp_hull_reassign.
  * X0[N][d]: the points translated so that the start simplex' centroid is the origin (:188-192); simplex[d + 1]: the

@@ -26,16 +26,17 @@ from .polytope import (  # noqa: F401
     is_empty, is_fulldim, is_convex, is_adjacent, is_subset,
     reduce, separate, box2poly,
     cheby_ball, bounding_box, envelope, extreme, qhull,
-    is_inside, union, mldivide, intersect, volume, volume_exact,
+    is_inside, union, mldivide, intersect, intersect_pairs, volume, volume_exact,
 )
 from .prop2partition import (  # noqa: F401
-    Partition, MetricPartition, find_adjacent_regions, adjacency_sparse, overlap_sparse)
+    Partition, MetricPartition, find_adjacent_regions, adjacency_sparse, overlap_sparse, overlay)
 from . import polytope, prop2partition, quickhull  # noqa: F401,E402  (submodules, as `polytope.polytope` etc.)
 from .batch import (  # noqa: F401
     lpsolve_batch, cheby_ball_batch, bbox_batch, reduce_batch, contains_batch, assign_batch, adjacent_pairs, keep_to_bool,
     verify_careful_lps, lp_histograms, projection_batch, volume_batch, support_batch, subset_batch, extreme_batch, hull_batch,
     volume_exact_batch, locate_batch, locate_grid, projection_hull_batch,
     adjacent_pairs_sparse, overlap_pairs_sparse, overlap_cross_sparse, box_pairs, pair_verdicts,
+    pair_stacks, intersect_cross_sparse,   # (the packed intersect_pairs is batch.intersect_pairs: the root name is the Polytope-level call)
 )
 from .polytope import region_diff_batch  # noqa: F401,E402  (the Polytope-level call; the packed one is batch.region_diff_batch)
 from .polytope import envelope_batch, is_convex_batch  # noqa: F401,E402  (the raw launch is batch.envelope_outer_batch)

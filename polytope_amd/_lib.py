@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("PLP_LIB") or os.path.join(_HERE, "libplp_hip.so")
 
 PLP_OK, PLP_EINVAL, PLP_EUNSUPPORTED, PLP_EHIP, PLP_ENODEVICE, PLP_ENONFINITE = 0, 1, 2, 3, 4, 5
 RF_EMPTY, RF_EARLY, RF_MINREP, RF_LPFAIL = 1, 2, 4, 8
+RF_F1OPEN, RF_BADPAIR = 32, 64
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
@@ -100,6 +101,13 @@ SIGNATURES = {
                                      C.c_int, _vp]),
     "plp_box_pairs_fill_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_double, _vp, _vp, _vp, C.c_int, _vp,
                                          C.c_int, C.c_int, _vp]),
+    "plp_pair_stacks": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp]),
+    "plp_pair_stacks_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp]),
+    "plp_intersect_pairs": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_double, C.c_int64, _vp, C.c_int64,
+                                      _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
+    "plp_intersect_pairs_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_double, C.c_int64, _vp,
+                                          C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
+    "plp_pair_chunk_default": (C.c_int64, [C.c_int, C.c_int]),
     "plp_region_diff_search": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_double, C.POINTER(_vp)]),
     "plp_rdiff_result_sizes": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "plp_rdiff_result_copy": (C.c_int, [_vp, _vp, _vp, _vp]),

@@ -1384,6 +1384,180 @@ def overlap_cross_sparse(A, b, n1, m=None, thresh=1e-7, boxes=None, max_candidat
     return res
 
 
+# ------------------------------------------------------------------------------------- intersections of listed pairs
+RF_EMPTY, RF_LPFAIL, RF_F1OPEN, RF_BADPAIR = _lib.RF_EMPTY, _lib.RF_LPFAIL, _lib.RF_F1OPEN, _lib.RF_BADPAIR
+_RF_NO_ROWS = RF_EMPTY | RF_LPFAIL | RF_F1OPEN   # plp_fm_emit writes no rows under these
+
+
+def _pair_chunk(m_max, d, chunk):
+    """Pairs per chunk: the caller's, or the library's default for this table shape (plp_pair_chunk_default: the one
+    statement of that rule, csrc/plp_capi.hip)."""
+    if chunk is not None and int(chunk) > 0:
+        return int(chunk)
+    return int(_lib.load().plp_pair_chunk_default(int(m_max), int(d)))
+
+
+def _pair_table(what, A, b, m, pairs):
+    """The table and the list of a listed-pair call -> (backend, A, b, m, n, m_max, d, pairs int32[K, 2], K)."""
+    be, A, b, m, n, m_max, d = _cells(what, A, b, m)
+    if m_max < 1 or 2 * m_max > MAX_M or d < 1 or d > MAX_D:
+        raise _lib.UnsupportedSize("%s: m_max=%d d=%d outside envelope (2*m_max<=64, d<=16)" % (what, m_max, d))
+    pairs = be.arr(pairs, np.int32)
+    if len(pairs.shape) != 2 or pairs.shape[1] != 2:
+        raise ValueError("pairs must be [K, 2]")
+    return be, A, b, m, n, m_max, d, pairs, int(pairs.shape[0])
+
+
+def _popcount64(words):
+    """Bits set per 64-bit word (numpy uint64 / int64 or torch int64 -- the same bits) -> int64 of the same shape."""
+    x = words.view(np.int64) if isinstance(words, np.ndarray) else words
+    x = x - ((x >> 1) & 0x5555555555555555)
+    x = (x & 0x3333333333333333) + ((x >> 2) & 0x3333333333333333)
+    x = (x + (x >> 4)) & 0x0F0F0F0F0F0F0F0F
+    return ((x * 0x0101010101010101) >> 56) & 0xFF
+
+
+def pair_stacks(A, b, pairs, m=None):
+    """The stacks of listed cell pairs: for pair t = (pairs[t, 0], pairs[t, 1]) = (i, j) of the n cells A[n, m_max, d],
+    b[n, m_max] what Polytope(np.vstack([A_i, A_j]), np.hstack([b_i, b_j])) holds (polytope.py:272-275) -- cell i's rows,
+    then cell j's, each scaled by the reciprocal of its norm, rows of norm <= 1e-10 dropped -- formed on the device.
+    -> dict(A[K, 2 m_max, d], b[K, 2 m_max], m int32[K]), a packed table every batch call takes; rows from m[t] on are zero.
+    pairs int32[K, 2]; 2 * m_max <= 64, d <= 16.  numpy: an index outside [0, n) or a pair (i, i) raises ValueError; CUDA
+    tensors (nothing synchronises): such a pair gets m = 0 and nothing of the table is read for it."""
+    be, A, b, m, n, m_max, d, pairs, K = _pair_table("pair_stacks", A, b, m, pairs)
+    W = 2 * m_max
+    As, bs, ms = be.out((K, W, d), zero=True), be.out((K, W), zero=True), be.out((K,), np.int32, zero=True)
+    be.call("plp_pair_stacks", n, m_max, d, A, b, m, K, pairs, As, bs, ms, h2d=(A, b, m, pairs))
+    return dict(A=As, b=bs, m=ms)
+
+
+def _emit_pair_rows(be, A, b, m, n, m_max, d, pairs, keep, flags, abs_tol, chunk, mo_max):
+    """The rows of the results of listed pairs from the keep words and flags their reduce gave: per chunk the stacks are
+    formed again (a copy kernel) and go through plp_fm_emit(col = -1) -> A[K, mo_max, d], b[K, mo_max], m[K]."""
+    K, W = int(pairs.shape[0]), 2 * m_max
+    Ao, bo, mo = be.out((K, mo_max, d), zero=True), be.out((K, mo_max), zero=True), be.out((K,), np.int32, zero=True)
+    if K == 0:
+        return Ao, bo, mo
+    c = min(K, _pair_chunk(m_max, d, chunk))
+    sA, sb, sm = be.out((c, W, d)), be.out((c, W)), be.out((c,), np.int32)   # one table for all chunks (every slot is written)
+    for lo in range(0, K, c):
+        hi = min(K, lo + c)
+        k = hi - lo
+        As, bs, ms = sA[:k], sb[:k], sm[:k]
+        be.call("plp_pair_stacks", n, m_max, d, A, b, m, k, pairs[lo:hi], As, bs, ms, h2d=(A, b, m))
+        be.call("plp_fm_emit", k, W, d, As, bs, ms, keep[lo:hi], 1, flags[lo:hi], -1, 0, float(abs_tol), int(mo_max),
+                Ao[lo:hi], bo[lo:hi], mo[lo:hi])
+    return Ao, bo, mo
+
+
+def _pair_mo_max(be, keep, flags):
+    """The largest number of rows a result has (one read-back), at least 1."""
+    if int(keep.shape[0]) == 0:
+        return 1
+    cnt = _popcount64(keep)
+    if be.torch is not None:
+        cnt = be.torch.where((flags & _RF_NO_ROWS) != 0, be.torch.zeros_like(cnt), cnt)
+    else:
+        cnt = np.where((flags & _RF_NO_ROWS) != 0, 0, cnt)
+    return max(1, int(cnt.max()))
+
+
+def intersect_pairs(A, b, pairs, m=None, abs_tol=1e-7, rows=True, chunk=None, mo_max=None):
+    """The intersections of listed cell pairs of a table, formed on the device: for pair t = (i, j) of the n cells
+    A[n, m_max, d], b[n, m_max] exactly what reduce_batch returns for the stack pair_stacks forms -- what
+    cells[i].intersect(cells[j]) reduces (polytope.py:255-275) -- in list order:
+    -> dict(keep uint64[K] (bit s = stack row s; where ms[t] == m_i + m_j the first m_i bits are cell i's rows), flags, r,
+            xc[K, d], nlp, ms int32[K] (rows of the stack)[, A[K, mo_max, d], b[K, mo_max], m int32[K]]).
+    rows=True: the results' rows as a packed table (fm_emit(col=-1) of the stacks under keep / flags: the (b + 0.1) - 0.1 round
+    trip of a minimal representation, one constructor pass; m = 0 under RF_EMPTY / RF_LPFAIL / RF_F1OPEN).  mo_max: None --
+    the largest popcount(keep) of the list, ONE read-back; the stacks are then formed a second time, chunk by chunk, for the
+    emission (a copy kernel; the LPs run once).  An int -- no read-back, one pass, and m = -1 for a result of more rows.
+    The list is worked off in chunks of `chunk` pairs (None: 32 MiB of stacks): the stacks of the whole list are
+    never resident.  pairs int32[K, 2], 2 * m_max <= 64, d <= 16.  numpy in: numpy out, an index outside [0, n) or a pair
+    (i, i) raises ValueError; CUDA tensors in: resident tensors on torch's current stream, and such a pair gets flags =
+    RF_EMPTY | RF_BADPAIR, keep = r = nlp = ms = m = 0, xc = NaN."""
+    be, A, b, m, n, m_max, d, pairs, K = _pair_table("intersect_pairs", A, b, m, pairs)
+    c = 0 if chunk is None else int(chunk)
+    res = dict(keep=be.out((K,), np.uint64, zero=True), flags=be.out((K,), np.int32, zero=True), r=be.out((K,), zero=True),
+               xc=be.out((K, d), zero=True), nlp=be.out((K,), np.int32, zero=True), ms=be.out((K,), np.int32, zero=True))
+    outs = (None, None, None)
+    if rows and mo_max is not None:
+        mo_max = int(mo_max)
+        if mo_max < 0:
+            raise ValueError("intersect_pairs: mo_max must not be negative")
+        outs = (be.out((K, mo_max, d), zero=True), be.out((K, mo_max), zero=True), be.out((K,), np.int32, zero=True))
+    ptrs = outs
+    if rows and mo_max == 0 and K:
+        # (no row slots: the empty A / b have no address, and a NULL A_out would turn the emission off -- the library gets
+        # a word it never writes to, and m says which results have rows: -1)
+        dummy = be.out((1,), zero=True)
+        ptrs = (dummy, dummy, outs[2])
+    be.call("plp_intersect_pairs", n, m_max, d, A, b, m, float(abs_tol), K, pairs, c, res["keep"], res["flags"], res["r"],
+            res["xc"], res["nlp"], res["ms"], 0 if mo_max is None else mo_max, *ptrs, h2d=(A, b, m, pairs))
+    if rows and mo_max is None:
+        outs = _emit_pair_rows(be, A, b, m, n, m_max, d, pairs, res["keep"], res["flags"], abs_tol, chunk,
+                               _pair_mo_max(be, res["keep"], res["flags"]))
+    if rows:
+        res["A"], res["b"], res["m"] = outs
+    return res
+
+
+def intersect_cross_sparse(A, b, n1, m=None, abs_tol=1e-7, boxes=None, max_candidates=1 << 24, chunk=None):
+    """The overlay of two lists of cells in one table (n1 cells, then n - n1): the full-dimensional intersections a ∩ c of a
+    cell a < n1 of the first list with a cell c of the second, without any n1 x n2 object.
+    -> dict(pairs int32[K', 2]: (a, c), c counted from 0 as overlap_cross_sparse, sorted by (a, c); A[K', mo_max, d],
+            b[K', mo_max], m[K']: the K' cells as a packed table; r[K'], xc[K', d]: their Chebyshev balls; open: the positions
+            in 0..K' whose flags carry RF_F1OPEN -- no verdict from the fused reduce, no rows (m = 0), for the caller to
+            resolve (polytope.py: _reduce_many does, through the verified stand-alone ball); flags[K']; ncand).
+    Broad phase as overlap_cross_sparse (box_pairs in the cross form, nothing inflated; `boxes`: outer boxes of the cells,
+    see adjacent_pairs_sparse), then per chunk of whole cells of at most max_candidates candidates intersect_pairs: a pair is
+    kept iff its stack is not RF_EMPTY -- the reduce's own Chebyshev LP is the narrow phase, no pair LP is solved twice.  The
+    cull is exact: a ball of radius > abs_tol in both cells lies in both boxes.  Rows are emitted for the kept pairs only.
+    chunk: as in intersect_pairs.
+    numpy in: numpy out; CUDA tensors in: resident tensors on torch's current stream."""
+    n1 = int(n1)
+    what = "intersect_cross_sparse"
+    be, A, b, m, n, m_max, d = _cells(what, A, b, m)
+    if m_max < 1 or 2 * m_max > MAX_M or d < 1 or d > MAX_D:
+        raise _lib.UnsupportedSize("%s: m_max=%d d=%d outside envelope (2*m_max<=64, d<=16)" % (what, m_max, d))
+    if n1 < 0 or n1 > n:
+        raise ValueError("%s: n1 must lie in 0..n" % what)
+    max_candidates = int(max_candidates)
+    if max_candidates < 1:
+        raise ValueError("%s: max_candidates must be at least 1" % what)
+    xp = be.torch if be.torch is not None else np
+    found = []
+    ncand = 0
+    if n1 > 0 and n1 < n:
+        if boxes is None:
+            lb, ub = _outer_boxes(be, A, b, m, 0.0)
+        else:
+            lb, ub = boxes
+            if tuple(lb.shape) != (n, d) or tuple(ub.shape) != (n, d):
+                raise ValueError("%s: boxes must be (lb[n, d], ub[n, d])" % what)
+        bp = _BoxPairs(be, lb, ub, n1, _LOCATE_PAD, "auto")
+        ncand = bp.K
+        for lo, hi in bp.chunks(max_candidates):
+            cand = bp.fill(lo, hi)
+            res = intersect_pairs(A, b, cand, m, abs_tol, rows=False, chunk=chunk)
+            fl = res["flags"]
+            live = ((fl & RF_EMPTY) == 0) | ((fl & RF_F1OPEN) != 0)
+            found.append((cand[live], res["keep"][live], fl[live], res["r"][live], res["xc"][live]))
+    if not found:
+        found = [(be.out((0, 2), np.int32, zero=True), be.out((0,), np.uint64, zero=True), be.out((0,), np.int32, zero=True),
+                  be.out((0,), zero=True), be.out((0, d), zero=True))]
+    cat = (lambda v: v[0]) if len(found) == 1 else (be.torch.cat if be.torch is not None else np.concatenate)
+    pairs, keep, flags, r, xc = (cat([f[k] for f in found]) for k in range(5))
+    pairs, keep, flags = be.arr(pairs, np.int32), be.arr(keep, np.uint64), be.arr(flags, np.int32)
+    Ao, bo, mo = _emit_pair_rows(be, A, b, m, n, m_max, d, pairs, keep, flags, abs_tol, chunk, _pair_mo_max(be, keep, flags))
+    opened = xp.nonzero((flags & RF_F1OPEN) != 0)
+    opened = opened[0] if isinstance(opened, tuple) else opened[:, 0]
+    out_pairs = pairs.clone() if be.torch is not None else pairs.copy()
+    if int(out_pairs.shape[0]):
+        out_pairs[:, 1] -= n1
+    return {"pairs": out_pairs, "A": Ao, "b": bo, "m": mo, "r": r, "xc": xc, "open": opened, "flags": flags, "ncand": ncand}
+
+
 def selftest(group_size):
     """Cross-lane primitive self-test -> (out_d[128], out_u[128]) (see plp_points.hip)."""
     lib = _lib.load()

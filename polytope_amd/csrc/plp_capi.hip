@@ -4,6 +4,7 @@
 #include "plp_hostcall.hpp"
 #include "plp_locate.hpp"
 #include "plp_lp_plan.hpp"
+#include "plp_pair_stack.hpp"
 
 namespace {
 
@@ -85,6 +86,7 @@ int plp_ctx_destroy(plp_ctx* ctx) {
     for (auto& kv : ctx->as_scratch) if (kv.second.p) (void)hipFree(kv.second.p);
     for (auto& kv : ctx->vf_scratch) if (kv.second.p) (void)hipFree(kv.second.p);
     for (auto& kv : ctx->vf_basis) if (kv.second.p) (void)hipFree(kv.second.p);
+    for (auto& kv : ctx->ps_scratch) if (kv.second.p) (void)hipFree(kv.second.p);
     if (ctx->mf_ev) (void)hipEventDestroy(ctx->mf_ev);
     if (ctx->hull_spare.full) {
         (void)hipFree(ctx->hull_spare.X); (void)hipFree(ctx->hull_spare.owner); (void)hipFree(ctx->hull_spare.dist);
@@ -1624,6 +1626,155 @@ int plp_box_pairs_fill(plp_ctx* ctx, int n, int d, const double* lb, const doubl
     rc = plp_box_pairs_fill_dev(ctx, hc.st, n, d, dlb, dub, pad, grid, dcs, dci, n1, dpc, cell_lo, cell_hi, dpairs);
     if (rc) return rc;
     return hc.download();
+}
+
+// ------------------------------------------------------------------------------- stacks and intersections of listed pairs
+static int check_pair_stacks(plp_ctx* ctx, int n, int m_max, int d, const double* A, const double* b, int64_t K,
+                             const int32_t* pairs, bool outs_ok) {
+    if (!ctx) return fail(PLP_EINVAL, "ctx is NULL");
+    if (n < 0 || K < 0 || m_max < 1 || d < 1) return fail(PLP_EINVAL, "bad sizes");
+    if (2 * m_max > plp::MAX_M || d > plp::MAX_D)   // (also for an empty list: the sizes are wrong whatever K is)
+        return fail(PLP_EUNSUPPORTED, "m_max=%d d=%d outside envelope (2*m_max<=64, d<=16)", m_max, d);
+    if (K == 0) return PLP_OK;
+    if (!pairs || !outs_ok || (n > 0 && (!A || !b))) return fail(PLP_EINVAL, "NULL pointer");
+    return PLP_OK;
+}
+
+static int check_listed(int n, int64_t K, const int32_t* pairs) {
+    const long long t = plp::ps::host_first_bad(n, K, pairs);
+    if (t >= 0)
+        return fail(PLP_EINVAL, "pair %lld = (%d, %d): indices must be two different cells of [0, %d)", t, pairs[2 * t],
+                    pairs[2 * t + 1], n);
+    return PLP_OK;
+}
+
+int plp_pair_stacks_dev(plp_ctx* ctx, void* stream, int n, int m_max, int d, const double* A, const double* b, const int32_t* m,
+                        int64_t K, const int32_t* pairs, double* A_s, double* b_s, int32_t* m_s) {
+    int rc = check_pair_stacks(ctx, n, m_max, d, A, b, K, pairs, A_s && b_s && m_s);
+    if (rc || K == 0) return rc;
+    if (plp::launch_pair_stacks(n, m_max, d, A, b, m, K, pairs, A_s, b_s, m_s, (hipStream_t)stream))
+        return fail(PLP_EUNSUPPORTED, "pair stacks: unsupported size");
+    return check_launch("pair_stack_kernel");
+}
+
+int plp_pair_stacks(plp_ctx* ctx, int n, int m_max, int d, const double* A, const double* b, const int32_t* m, int64_t K,
+                    const int32_t* pairs, double* A_s, double* b_s, int32_t* m_s) {
+    int rc = check_pair_stacks(ctx, n, m_max, d, A, b, K, pairs, A_s && b_s && m_s);
+    if (rc || K == 0) return rc;
+    if ((rc = check_listed(n, K, pairs))) return rc;
+    const size_t W = 2 * (size_t)m_max;
+    double *dA, *db, *dAs, *dbs;
+    int32_t *dm, *dpairs, *dms;
+    HostCall hc(ctx);
+    hc.in(dA, A, (size_t)n * m_max * d);
+    hc.in(db, b, (size_t)n * m_max);
+    hc.in(dm, m, n);
+    hc.in(dpairs, pairs, (size_t)K * 2);
+    hc.out(dAs, A_s, (size_t)K * W * d);
+    hc.out(dbs, b_s, (size_t)K * W);
+    hc.out(dms, m_s, (size_t)K);
+    hc.direct_out = true;
+    rc = hc.reserve();
+    if (rc) return rc;
+    rc = hc.upload();
+    if (rc) return rc;
+    rc = plp_pair_stacks_dev(ctx, hc.st, n, m_max, d, dA, db, dm, K, dpairs, dAs, dbs, dms);
+    if (rc) return rc;
+    return hc.download();
+}
+
+// Pairs per chunk of plp_intersect_pairs_dev when the caller names none (the one statement of the rule; exported, so that
+// the Python layer chunks its emission pass the same way): what keeps the chunk's stacks at 32 MiB (REASONED,
+// NOT MEASURED -- DESIGN 4.21: some 50 000 stacks of two 8-row cells in d = 4, 3 800 of two 32-row cells in d = 16; the
+// scratch stays in the tens of megabytes per stream).
+int64_t plp_pair_chunk_default(int m_max, int d) {
+    if (m_max < 1 || d < 1) return 1024;
+    const size_t per = 2 * (size_t)m_max * ((size_t)d + 1) * 8;
+    const size_t c = ((size_t)32 << 20) / per;
+    return (int64_t)(c < 1024 ? 1024 : c);
+}
+
+int plp_intersect_pairs_dev(plp_ctx* ctx, void* stream, int n, int m_max, int d, const double* A, const double* b,
+                            const int32_t* m, double abs_tol, int64_t K, const int32_t* pairs, int64_t chunk, uint64_t* keep,
+                            int32_t* flags, double* r, double* xc, int32_t* nlp, int32_t* ms, int mo_max, double* A_out,
+                            double* b_out, int32_t* m_out) {
+    int rc = check_pair_stacks(ctx, n, m_max, d, A, b, K, pairs, keep && flags && r && xc && nlp && ms);
+    if (rc) return rc;
+    if (mo_max < 0) return fail(PLP_EINVAL, "bad sizes");
+    if (K == 0) return PLP_OK;
+    if (A_out && (!b_out || !m_out)) return fail(PLP_EINVAL, "NULL pointer");
+    const int W = 2 * m_max;
+    int64_t c = chunk > 0 ? chunk : plp_pair_chunk_default(m_max, d);
+    c = c < K ? c : K;
+    const size_t a_bytes = pad((size_t)c * W * d * 8), b_bytes = pad((size_t)c * W * 8);
+    char* sc = static_cast<char*>(stream_buf(ctx->ps_scratch, stream, a_bytes + b_bytes));
+    if (!sc) return fail(PLP_EHIP, "intersect_pairs: no device memory for the stacks of a chunk (%zu bytes)", a_bytes + b_bytes);
+    double* As = reinterpret_cast<double*>(sc);
+    double* bs = reinterpret_cast<double*>(sc + a_bytes);
+    hipStream_t st = (hipStream_t)stream;
+    for (int64_t lo = 0; lo < K; lo += c) {
+        const int64_t k = K - lo < c ? K - lo : c;
+        const int32_t* pl = pairs + 2 * lo;
+        // the rows that stay per stack are an output of the call and the row counts the reduce and the emission read
+        if (plp::launch_pair_stacks(n, m_max, d, A, b, m, k, pl, As, bs, ms + lo, st))
+            return fail(PLP_EUNSUPPORTED, "pair stacks: unsupported size");
+        if ((rc = check_launch("pair_stack_kernel"))) return rc;
+        rc = plp_reduce_batch_dev(ctx, stream, k, W, d, As, bs, ms + lo, abs_tol, keep + lo, flags + lo, r + lo,
+                                  xc + (size_t)lo * d, nlp + lo);
+        if (rc) return rc;
+        if (A_out) {
+            rc = plp_fm_emit_dev(ctx, stream, k, W, d, As, bs, ms + lo, keep + lo, 1, flags + lo, -1, 0, abs_tol, mo_max,
+                                 A_out + (size_t)lo * mo_max * d, b_out + (size_t)lo * mo_max, m_out + lo);
+            if (rc) return rc;
+        }
+        plp::launch_pair_bad(n, d, k, pl, reinterpret_cast<unsigned long long*>(keep + lo), flags + lo, r + lo,
+                             xc + (size_t)lo * d, nlp + lo, ms + lo, A_out ? m_out + lo : nullptr, st);
+        if ((rc = check_launch("pair_bad_kernel"))) return rc;
+    }
+    return PLP_OK;
+}
+
+int plp_intersect_pairs(plp_ctx* ctx, int n, int m_max, int d, const double* A, const double* b, const int32_t* m,
+                        double abs_tol, int64_t K, const int32_t* pairs, int64_t chunk, uint64_t* keep, int32_t* flags, double* r,
+                        double* xc, int32_t* nlp, int32_t* ms, int mo_max, double* A_out, double* b_out, int32_t* m_out) {
+    int rc = check_pair_stacks(ctx, n, m_max, d, A, b, K, pairs, keep && flags && r && xc && nlp && ms);
+    if (rc) return rc;
+    if (mo_max < 0) return fail(PLP_EINVAL, "bad sizes");
+    if (K == 0) return PLP_OK;
+    if (A_out && (!b_out || !m_out)) return fail(PLP_EINVAL, "NULL pointer");
+    if ((rc = check_listed(n, K, pairs))) return rc;
+    const size_t mo = A_out ? (size_t)mo_max : 0;
+    double *dA, *db, *dr, *dxc, *dAo, *dbo;
+    int32_t *dm, *dpairs, *dhead;
+    uint64_t* dkeep;
+    // (flags, nlp, ms and m_out come back as one block: a call declares at most eight outputs)
+    std::vector<int32_t> head((size_t)K * 4);
+    HostCall hc(ctx);
+    hc.in(dA, A, (size_t)n * m_max * d);
+    hc.in(db, b, (size_t)n * m_max);
+    hc.in(dm, m, n);
+    hc.in(dpairs, pairs, (size_t)K * 2);
+    hc.out(dkeep, keep, (size_t)K);
+    hc.out(dhead, head.data(), (size_t)K * 4);
+    hc.out(dr, r, (size_t)K);
+    hc.out(dxc, xc, (size_t)K * d);
+    hc.out(dAo, A_out, (size_t)K * mo * d);
+    hc.out(dbo, b_out, (size_t)K * mo);
+    hc.direct_out = true;
+    rc = hc.reserve();
+    if (rc) return rc;
+    rc = hc.upload();
+    if (rc) return rc;
+    rc = plp_intersect_pairs_dev(ctx, hc.st, n, m_max, d, dA, db, dm, abs_tol, K, dpairs, chunk, dkeep, dhead, dr, dxc, dhead + K,
+                                 dhead + 2 * K, mo_max, A_out ? dAo : nullptr, dbo, dhead + 3 * K);
+    if (rc) return rc;
+    rc = hc.download();
+    if (rc) return rc;
+    memcpy(flags, head.data(), (size_t)K * 4);
+    memcpy(nlp, head.data() + K, (size_t)K * 4);
+    memcpy(ms, head.data() + 2 * K, (size_t)K * 4);
+    if (A_out) memcpy(m_out, head.data() + 3 * K, (size_t)K * 4);
+    return PLP_OK;
 }
 
 int plp_selftest(plp_ctx* ctx, int group_size, double* out_d, uint32_t* out_u) {

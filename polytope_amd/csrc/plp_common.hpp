@@ -28,7 +28,10 @@ enum : int {
     // Also set when the engine called its Chebyshev LP optimal at a centre that VIOLATES a row of the polytope (centre_off
     // below; tests/golden/found/lane93_t21_k20730.npz: radius right, centre 5 outside -- a pivot next to twin rows): the
     // presolve and the walks of F2 / F3 start from that centre, so nothing of the fused answer is usable.
-    RF_F1OPEN = 32
+    RF_F1OPEN = 32,
+    // plp_intersect_pairs_dev only, beside RF_EMPTY: the listed pair is no pair of the table (an index outside [0, n), or
+    // twice the same cell -- plp_pair_index.hpp); nothing was stacked or reduced for it
+    RF_BADPAIR = 64
 };
 
 // tolerances of the simplex core (identical in oracle/plp_oracle.c)

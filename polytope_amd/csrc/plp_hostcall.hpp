@@ -97,6 +97,8 @@ struct plp_ctx {
     // dictionaries, one grow-only buffer per stream like as_scratch; bounding boxes: the engines' bases and centres
     std::unordered_map<void*, StreamBuf> vf_scratch;
     std::unordered_map<void*, StreamBuf> vf_basis;
+    // plp_intersect_pairs_dev: the stacks of one chunk of pairs (A_s | b_s; their row counts go to the caller's ms), per stream like the tables above
+    std::unordered_map<void*, StreamBuf> ps_scratch;
 };
 
 namespace {

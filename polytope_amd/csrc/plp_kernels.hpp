@@ -178,6 +178,14 @@ int launch_box_pairs_fill(int n, int d, const double* lb, const double* ub, doub
                           const int* cell_start, const int* cell_items, int n1, const long long* per_cell, int cell_lo,
                           int cell_hi, int* pairs, hipStream_t st);
 
+// the stacks of listed cell pairs (plp_pair_stack.hip; the rule: plp_pair_stack.hpp): A_s[K][2 m_max][d], b_s[K][2 m_max],
+// m_s[K].  Return 0, 2 for sizes outside 2 m_max <= 64, d <= 16.  launch_pair_bad: the outputs of the bad pairs of a chunk of
+// plp_intersect_pairs_dev (m_out may be NULL).
+int launch_pair_stacks(int n, int m_max, int d, const double* A, const double* b, const int* m, long long K, const int* pairs,
+                       double* A_s, double* b_s, int* m_s, hipStream_t st);
+void launch_pair_bad(int n, int d, long long K, const int* pairs, unsigned long long* keep, int* flags, double* r, double* xc,
+                     int* nlp, int* ms, int* m_out, hipStream_t st);
+
 int launch_assign(long long N, int d, const double* X, int F, const double* normals, const double* offsets,
                   double abs_tol, int* facet_of_point, double* dist, long long* argmax, double* maxd,
                   void* scratch, size_t scratch_bytes, hipStream_t st);

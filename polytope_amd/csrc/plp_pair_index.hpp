@@ -10,8 +10,16 @@
 //                    (i, j) = (0, 0), and the kernels write PAIR_BAD for it.
 //
 // The listed form is a template instantiation of its own, so the kernels of the dense calls keep their code.
+//
+// The same source compiles for the device and, for the host restatements of the tests (plp_pair_stack.hpp), under plain g++.
 #pragma once
+#if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#define PLP_PAIR_FN __host__ __device__ __forceinline__
+#else
+#include <math.h>
+#define PLP_PAIR_FN static inline
+#endif
 
 namespace plp {
 
@@ -19,8 +27,8 @@ constexpr unsigned char PAIR_BAD = 255;  // = PLP_PAIR_BAD (include/plp.h)
 
 // `valid`: p is a pair of the launch (lanes beyond the batch get a harmless pair and read nothing)
 template <bool LISTED>
-__device__ __forceinline__ bool pair_cells(long long p, bool valid, int n, int cross_n1, const int* __restrict__ list,
-                                           long long& i, long long& j) {
+PLP_PAIR_FN bool pair_cells(long long p, bool valid, int n, int cross_n1, const int* __restrict__ list, long long& i,
+                            long long& j) {
     if constexpr (LISTED) {
         const int a = valid ? list[2 * p] : 0, c = valid ? list[2 * p + 1] : 0;
         const bool ok = valid & ((unsigned)a < (unsigned)n) & ((unsigned)c < (unsigned)n) & (a != c);

@@ -1126,6 +1126,71 @@ def intersect(poly1, poly2, abs_tol=ABS_TOL):
     return poly1.intersect(poly2, abs_tol)
 
 
+def _pair_cell_ok(p):
+    """A cell the listed-pair kernels take: a Polytope of 1..32 finite rows in dimension <= 16."""
+    return isinstance(p, Polytope) and not isinstance(p, Region) and p.A.ndim == 2 and 1 <= p.A.shape[0] <= _MAX_ROWS // 2 \
+        and 1 <= p.A.shape[1] <= _MAX_DIM and bool(np.all(np.isfinite(p.b))) and bool(np.all(np.isfinite(p.A)))
+
+
+def intersect_pairs(cells, pairs, abs_tol=ABS_TOL):
+    """[cells[i].intersect(cells[j], abs_tol) for i, j in pairs] -- the same arrays, `minrep` and cached Chebyshev ball per
+    result, the same exceptions, `Polytope()` for a pair with an operand that is not full-dimensional.
+
+    On the 'hip' backend the listed pairs of cells inside the kernels' envelope (Polytopes of 1..32 finite rows, one
+    dimension <= 16) are ONE batch.intersect_pairs call on the cells' packed table (uploaded once, kept by _table_of): the
+    stacks are formed, reduced and compacted on the device and only the results' rows come back.  Pairs the fused reduce
+    leaves open (RF_F1OPEN) and pairs with a cell outside the envelope go through the single call.  On any other backend it
+    is the loop.  (The balls of a batch may differ from the single call's in the last bits where the Chebyshev LP has ties,
+    DESIGN 7; rows, minrep and verdicts do not.)"""
+    cells = list(cells)
+    plist = [(int(i), int(j)) for i, j in pairs]
+
+    def single(i, j):
+        return cells[i].intersect(cells[j], abs_tol)
+
+    used = sorted({k for ij in plist for k in ij})
+    if not _use_hip() or not plist or any(k < 0 or k >= len(cells) for k in used) \
+            or not all(isinstance(cells[k], Polytope) for k in used):
+        return [single(i, j) for i, j in plist]   # (a negative index, a Region, anything else: the loop's own behaviour)
+    solvers._require("hip")
+    ok = [k for k in used if _pair_cell_ok(cells[k])]
+    if len({cells[k].A.shape[1] for k in ok}) > 1 or len({cells[k].dim for k in used if cells[k].A.size}) > 1:
+        return [single(i, j) for i, j in plist]   # (mixed dimensions: the loop raises at the pair the reference raises at)
+    _cheby_fill([cells[k] for k in ok if cells[k].fulldim is None])
+    slot = {k: s for s, k in enumerate(k for k in ok if is_fulldim(cells[k]))}
+    out = [None] * len(plist)
+    batch_at = [t for t, (i, j) in enumerate(plist) if i in slot and j in slot and i != j]
+    if batch_at:
+        from . import batch
+        members = [cells[k] for k in slot]
+        At, bt, mt = _table_of(members).dev()
+        listed = np.array([(slot[plist[t][0]], slot[plist[t][1]]) for t in batch_at], dtype=np.int32)
+        if not isinstance(At, np.ndarray):
+            torch = _torch_or_none()
+            listed = torch.as_tensor(listed).to(At.device)
+        res = batch.intersect_pairs(At, bt, listed, m=mt, abs_tol=abs_tol, rows=True)
+        res = {k: (v if isinstance(v, np.ndarray) else v.cpu().numpy()) for k, v in res.items()}
+        for q, t in enumerate(batch_at):
+            fl = int(res["flags"][q])
+            if fl & (_RF_F1OPEN | batch.RF_BADPAIR) or int(res["m"][q]) < 0:
+                continue   # (left to the single call below)
+            if fl & _RF_LPFAIL:
+                raise RuntimeError("bounding_box: an LP of the box prefilter of `reduce` ended with status 1 or 4")
+            if fl & _RF_EMPTY:
+                out[t] = Polytope()
+                continue
+            mo = int(res["m"][q])
+            poly = Polytope(res["A"][q, :mo], res["b"][q, :mo], normalize=False)
+            poly.minrep = bool(fl & _RF_MINREP)
+            if not np.isnan(res["xc"][q]).any():
+                poly._chebR, poly._chebXc = np.double(res["r"][q]), res["xc"][q].copy()
+            out[t] = poly
+    for t, (i, j) in enumerate(plist):
+        if out[t] is None:
+            out[t] = single(i, j)
+    return out
+
+
 # ====================================================================================== union / convexity
 def _members(s):
     if len(s) == 0:

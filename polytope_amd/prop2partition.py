@@ -318,6 +318,72 @@ def overlap_sparse(partition, abs_tol=pc.ABS_TOL):
     return _pairs_csr(partition, "overlap", abs_tol)
 
 
+def _single_cells(partition, what):
+    """The elements of a partition (or list) as single polytopes: a Polytope, or the one member of a Region."""
+    from ._lib import UnsupportedSize
+    cells = []
+    for r in _regions_of(partition):
+        if isinstance(r, pc.Region):
+            if len(r.list_poly) != 1:
+                raise UnsupportedSize("%s: every element must be a single polytope (a Region of %d members)"
+                                      % (what, len(r.list_poly)))
+            r = r.list_poly[0]
+        if not isinstance(r, pc.Polytope):
+            raise TypeError("%s: Not a Polytope or Region, got instead:\n\t%s" % (what, type(r)))
+        cells.append(r)
+    return cells
+
+
+def overlay(first, second, abs_tol=pc.ABS_TOL):
+    """The overlay (common refinement) of two partitions: every full-dimensional a ∩ c of an element a of `first` with an
+    element c of `second` -> (cells, parents): cells a list of Polytope, each what a.intersect(c, abs_tol) returns, sorted by
+    (a, c); parents int32[K', 2], the indices (a, c) of each cell's two parents.  `first` / `second`: Partitions, or lists
+    of Polytopes / single-polytope Regions; an element Region of several members raises UnsupportedSize.
+
+    On the 'hip' backend the pairs come from batch.intersect_cross_sparse on the packed table of both lists: only pairs
+    whose outer boxes meet are stacked and reduced, and nothing of size len(first) * len(second) is formed (member polytopes
+    of 1..32 rows in one dimension d <= 16; anything else raises UnsupportedSize, as adjacency_sparse does).  On any other
+    backend it is the double loop."""
+    from ._lib import UnsupportedSize
+    ca, cc = _single_cells(first, "overlay"), _single_cells(second, "overlay")
+    cells, parents = [], []
+    if solvers.default_solver != "hip":
+        for i, a in enumerate(ca):
+            for j, c in enumerate(cc):
+                q = a.intersect(c, abs_tol)
+                if not pc.is_empty(q):
+                    cells.append(q)
+                    parents.append((i, j))
+        return cells, np.array(parents, dtype=np.int32).reshape(-1, 2)
+    if not ca or not cc:
+        return cells, np.zeros((0, 2), dtype=np.int32)
+    members = ca + cc
+    if not _pair_shapes_ok(members) or not all(np.all(np.isfinite(p.A)) and np.all(np.isfinite(p.b)) for p in members):
+        raise UnsupportedSize("overlay: the polytopes must share one dimension d <= 16 and have 1..32 finite rows each")
+    from . import batch
+    At, bt, mt = pc._table_of(members).dev()
+    res = batch.intersect_cross_sparse(At, bt, len(ca), m=mt, abs_tol=abs_tol)
+    res = {k: (v.cpu().numpy() if hasattr(v, "cpu") else v) for k, v in res.items()}
+    opened = set(int(k) for k in res["open"])
+    for k, (i, j) in enumerate(res["pairs"]):
+        fl = int(res["flags"][k])
+        if k in opened:   # no verdict from the fused reduce: the single call's verified path decides
+            q = ca[i].intersect(cc[j], abs_tol)
+            if pc.is_empty(q):
+                continue
+        else:
+            if fl & pc._RF_LPFAIL:
+                raise RuntimeError("bounding_box: an LP of the box prefilter of `reduce` ended with status 1 or 4")
+            mo = int(res["m"][k])
+            q = pc.Polytope(res["A"][k, :mo], res["b"][k, :mo], normalize=False)
+            q.minrep = bool(fl & pc._RF_MINREP)
+            if not np.isnan(res["xc"][k]).any():
+                q._chebR, q._chebXc = np.double(res["r"][k]), res["xc"][k].copy()
+        cells.append(q)
+        parents.append((int(i), int(j)))
+    return cells, np.array(parents, dtype=np.int32).reshape(-1, 2)
+
+
 ################################
 
 
