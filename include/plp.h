@@ -257,6 +257,38 @@ int plp_support_batch_dev(plp_ctx *ctx, void *stream, int64_t B, int m_max, int 
                           double *x, int32_t *status);
 
 /*
+ * Nearest points and Euclidean distances:  min |x - p|_2  s.t.  A x <= b  for B packed polytopes and K points each -- a
+ * strictly convex QP per (polytope, point), one dual active-set walk per lane, the rows of a polytope read once per
+ * tile and chunk of its points.
+ * In:  A[B][m_max][d], b[B][m_max], m[B] (NULL = m_max) as for plp_reduce_batch.  Rows are used at unit 2-norm; a zero row
+ *      with b >= 0 is ignored, a zero row with b < 0 makes the polytope empty;
+ *      X: the points, [K][d] shared by every polytope (x_shared != 0) or [B][K][d].
+ * Out: dist[B][K] = |x - p|_2;  x[B][K][d] the nearest point (NULL: not written);
+ *      face[B][K] (NULL ok): bit i set = row i is in the final active set (the keep-word convention);
+ *      lam[B][K][d] (NULL ok): the multipliers of the set bits of face in ascending row order, with respect to the rows as
+ *      given -- p - x = sum lam_j a_j -- zero-padded;  status[B][K]:
+ *        0  optimum.  With E = max(1, |x|_inf, |p|_inf) the point passed  max_i (n_i.x - beta_i) <= 1e-10 E  on every row and a
+ *           certificate on the rows of face: lam >= 0,  sum lam_j |beta_j - n_j.x| <= 1e-10 E max(dist, 1e-10 E),
+ *           |(p - x) - sum lam_j n_j|_2 <= 1e-12 E  (unit rows).  For a feasible x that bounds |x - x*| by
+ *           |r| + sqrt(|r|^2 + 2 gap) and dist - dist* by 2 (gap + |r| |x - x*|) / dist.  A point that violates no row comes
+ *           back as x = p bit for bit, dist = 0, face = 0;
+ *        2  the polytope is empty, certified by a Farkas combination y >= 0 on at most d + 1 rows with
+ *           |sum y_j n_j|_1 <= 1e-12 sum y_j  and  sum y_j beta_j < -1e-10 sum y_j:  dist = x = NaN;
+ *        1  NOT SETTLED HERE (dist = x = NaN, face = 0, lam = 0): the walk handed the problem back (nearly dependent active
+ *           rows, a run of steps of length zero, its iteration cap 2 (m + 2 d) + 4), an end check or the Farkas check
+ *           failed, or the point or a row of the polytope is not finite.  The caller settles these (polytope_amd.batch:
+ *           nearest_batch(resolve=True) enumerates row subsets on the host).
+ * d <= 4, m_max <= 64, K >= 1 and B * K <= 2^31 - 1, else PLP_EUNSUPPORTED.  B = 0: returns PLP_OK, nothing runs.
+ * The host-pointer form checks A, b and X for inf / nan when the context asks for it (plp_ctx_set_check_finite).
+ */
+int plp_nearest_batch(plp_ctx *ctx, int64_t B, int m_max, int d, const double *A, const double *b, const int32_t *m,
+                      int K, const double *X, int x_shared, double *dist, double *x, uint64_t *face, double *lam,
+                      int32_t *status);
+int plp_nearest_batch_dev(plp_ctx *ctx, void *stream, int64_t B, int m_max, int d, const double *A, const double *b,
+                          const int32_t *m, int K, const double *X, int x_shared, double *dist, double *x, uint64_t *face,
+                          double *lam, int32_t *status);
+
+/*
  * Vertices of B packed polytopes (H-representation to V-representation on the small-polytope path): every d-subset of a
  * polytope's rows is solved and tested against all rows, one polytope per wavefront, the rows read once.
  * In:  A[B][m_max][d], b[B][m_max], m[B] (NULL = m_max) as for plp_reduce_batch;

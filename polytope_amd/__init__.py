@@ -26,7 +26,7 @@ from .polytope import (  # noqa: F401
     is_empty, is_fulldim, is_convex, is_adjacent, is_subset,
     reduce, separate, box2poly,
     cheby_ball, bounding_box, envelope, extreme, qhull,
-    is_inside, union, mldivide, intersect, intersect_pairs, volume, volume_exact,
+    is_inside, union, mldivide, intersect, intersect_pairs, volume, volume_exact, nearest, distance,
 )
 from .prop2partition import (  # noqa: F401
     Partition, MetricPartition, find_adjacent_regions, adjacency_sparse, overlap_sparse, overlay)
@@ -34,7 +34,7 @@ from . import polytope, prop2partition, quickhull  # noqa: F401,E402  (submodule
 from .batch import (  # noqa: F401
     lpsolve_batch, cheby_ball_batch, bbox_batch, reduce_batch, contains_batch, assign_batch, adjacent_pairs, keep_to_bool,
     verify_careful_lps, lp_histograms, projection_batch, volume_batch, support_batch, subset_batch, extreme_batch, hull_batch,
-    volume_exact_batch, locate_batch, locate_grid, projection_hull_batch,
+    volume_exact_batch, locate_batch, locate_grid, projection_hull_batch, nearest_batch,
     adjacent_pairs_sparse, overlap_pairs_sparse, overlap_cross_sparse, box_pairs, pair_verdicts,
     pair_stacks, intersect_cross_sparse,   # (the packed intersect_pairs is batch.intersect_pairs: the root name is the Polytope-level call)
 )

@@ -758,6 +758,184 @@ def support_batch(A, b, C, m=None, xc=None, points=True, resolve=True):
     return dict(h=h, x=x, status=status)
 
 
+# ------------------------------------------------------------------------------------- nearest points
+_NEAREST_MAX_D = 4           # the shared-row kernel (csrc/plp_nearest.hip) holds the active set of d <= 4 rows in registers
+_NEAREST_END_TOL, _NEAREST_GAP_TOL, _NEAREST_RES_TOL = 1e-10, 1e-10, 1e-12   # the end checks of csrc/plp_nearest.hpp
+_NEAREST_SUBSETS = 1 << 17   # row subsets per numpy call of the host routine
+
+
+def _nearest_unit_rows(A, b):
+    """Rows at unit 2-norm as the kernel stages them -> n, beta, |a| (a zero row: n = 0, beta = 0 for b >= 0, else -1)."""
+    nrm = np.sqrt(np.sum(A * A, axis=1))
+    z = nrm == 0
+    s = np.where(z, 1.0, nrm)
+    return A / s[:, None], np.where(z, np.where(b < 0, -1.0, 0.0), b / s), s
+
+
+def _nearest_resolve_one(N, beta, p, xfeas=None):
+    """The nearest point of { n_i.x <= beta_i } (unit rows) to p by enumeration: it is the orthogonal projection of p onto
+    the affine hull of some face, so the closest FEASIBLE projection over all independent row subsets of size <= d is it.
+    xfeas: a feasible point or None -- a row with beta_i - n_i.p above the distance of a known feasible point cannot be
+    active and is left out first.  -> (dist, x, status, rows, lam): status 0 with both end checks of the kernel passed,
+    4 when the best candidate fails them or an input is not finite, -1 when no subset gives a feasible point."""
+    m, d = N.shape
+    nanx = np.full(d, np.nan)
+    none = np.zeros(0, np.int64)
+    if not (np.all(np.isfinite(p)) and np.all(np.isfinite(N)) and np.all(np.isfinite(beta))):
+        return np.nan, nanx, 4, none, np.zeros(0)
+    live = np.nonzero((np.abs(N).sum(axis=1) > 0) | (beta < 0))[0]
+    if np.any((np.abs(N[live]).sum(axis=1) == 0)):   # a zero row with b < 0
+        return np.nan, nanx, -1, none, np.zeros(0)
+    Nl, bl = N[live], beta[live]
+    rows = live
+    if xfeas is not None and np.all(np.isfinite(xfeas)) and live.size:
+        s0 = bl - Nl @ xfeas
+        if np.all(s0 >= 0):
+            dr = p - xfeas
+            ad = Nl @ dr
+            t = min(1.0, float(np.min(s0[ad > 0] / ad[ad > 0], initial=1.0)))
+            ub = float(np.linalg.norm(dr)) * (1.0 - t) * (1 + 1e-9) + 1e-12 * max(1.0, float(np.max(np.abs(p))))
+            rows = live[(bl - Nl @ p) <= ub]
+    pinf = max(1.0, float(np.max(np.abs(p), initial=0.0)))
+    best = (np.inf, None, none, np.zeros(0))
+    import itertools
+    for s in range(0, min(d, rows.size) + 1):
+        if s == 0:
+            if np.max(Nl @ p - bl, initial=-np.inf) <= 0:
+                return 0.0, p.copy(), 0, none, np.zeros(0)
+            continue
+        it = itertools.combinations(rows.tolist(), s)
+        while True:
+            S = np.array(list(itertools.islice(it, _NEAREST_SUBSETS)), dtype=np.int64).reshape(-1, s)
+            if not S.shape[0]:
+                break
+            NS = N[S]
+            G = NS @ NS.transpose(0, 2, 1)
+            ok = np.linalg.det(G) > 1e-12
+            if not ok.any():
+                continue
+            S, NS, G = S[ok], NS[ok], G[ok]
+            c = np.linalg.solve(G, (NS @ p - beta[S])[:, :, None])[:, :, 0]
+            x = p[None, :] - np.einsum("ns,nsk->nk", c, NS)
+            E = np.maximum(pinf, np.abs(x).max(axis=1))
+            viol = (x @ Nl.T - bl[None, :]).max(axis=1)
+            dd = np.where(viol <= _NEAREST_END_TOL * E, np.linalg.norm(x - p[None, :], axis=1), np.inf)
+            j = int(np.argmin(dd))
+            if dd[j] < best[0]:
+                best = (float(dd[j]), x[j], S[j], c[j])
+    dist, x, S, lam = best
+    if x is None:
+        return np.nan, nanx, -1, none, np.zeros(0)
+    # the kernel's two end checks on the candidate (feasibility held above)
+    E = max(pinf, float(np.max(np.abs(x))))
+    lam = np.maximum(lam, 0.0)
+    gap = float(np.sum(lam * np.abs(beta[S] - N[S] @ x)))
+    r = (p - x) - lam @ N[S]
+    good = gap <= _NEAREST_GAP_TOL * E * max(dist, _NEAREST_GAP_TOL * E) and float(np.linalg.norm(r)) <= _NEAREST_RES_TOL * E
+    if not good:
+        return np.nan, nanx, 4, none, np.zeros(0)
+    return dist, x, 0, S, lam
+
+
+def _nearest_resolve(be, A, b, m, X, shared, out):
+    """Raw status 1 settled on the host (nearest_batch: resolve=True), written into the arrays of `out`."""
+    status = out["status"]
+    host = (lambda a: a.cpu().numpy()) if be.torch is not None else (lambda a: a)
+    pi, ji = np.nonzero(host(status) == 1)
+    if not pi.size:
+        return
+    K, d = status.shape[1], A.shape[2]
+    pu, inv = np.unique(pi, return_inverse=True)
+    sel = pu if be.torch is None else be.torch.as_tensor(pu, device=be.device)
+    Ah, bh = host(A[sel]), host(b[sel])
+    mh = np.full(pu.size, A.shape[1]) if m is None else host(m[sel])
+    ball = None
+    n = pi.size
+    res = dict(dist=np.full(n, np.nan), x=np.full((n, d), np.nan), status=np.full(n, 4, np.int32), face=np.zeros(n, np.uint64),
+               lam=np.zeros((n, d)))
+    Xh = host(X if shared else X[sel])
+    units = {}
+    for t in range(n):
+        u = int(inv[t])
+        mk = int(min(max(mh[u], 0), A.shape[1]))
+        pt = Xh[ji[t]] if shared else Xh[u, ji[t]]
+        if not (np.all(np.isfinite(pt)) and np.all(np.isfinite(Ah[u, :mk])) and np.all(np.isfinite(bh[u, :mk]))):
+            continue   # status 4
+        if ball is None:   # Chebyshev centres of the polytopes concerned: the cull's feasible point, and who is empty
+            Af, bf = np.where(np.isfinite(Ah), Ah, 0.0), np.where(np.isfinite(bh), bh, 0.0)
+            ball = cheby_ball_batch(Af, bf, np.ascontiguousarray(mh, dtype=np.int32))
+        if u not in units:
+            units[u] = _nearest_unit_rows(Ah[u, :mk], bh[u, :mk])
+        N, beta, nrm = units[u]
+        okc = ball["status"][u] == 0 and ball["r"][u] >= 0
+        dd, xx, st, rows, lam = _nearest_resolve_one(N, beta, pt, ball["xc"][u] if okc else None)
+        if st == -1:
+            st = 2 if ball["status"][u] == 2 else 4
+        res["status"][t] = st
+        if st == 0:
+            order = np.argsort(rows)
+            res["dist"][t], res["x"][t] = dd, xx
+            res["face"][t] = np.uint64(sum(1 << int(i) for i in rows))
+            res["lam"][t, :rows.size] = (lam / nrm[rows])[order]
+    flat = pi * K + ji
+    for k, v in res.items():
+        if out.get(k) is None:
+            continue
+        dst = out[k].reshape((-1,) + tuple(out[k].shape[2:]))
+        if be.torch is not None:
+            v = be.torch.as_tensor(v.view(np.int64) if v.dtype == np.uint64 else v).to(be.device)
+            dst[be.torch.as_tensor(flat, device=be.device)] = v
+        else:
+            dst[flat] = v
+
+
+def nearest_batch(A, b, X, m=None, points=True, faces=False, resolve=True):
+    """Nearest points and Euclidean distances  min |x - p|_2  s.t.  A x <= b  of B packed polytopes to K points each: one
+    strictly convex QP per (polytope, point), solved by a dual active-set walk per lane, the rows of a polytope read once
+    for a whole chunk of its points (include/plp.h: plp_nearest_batch; csrc/plp_nearest.hpp).
+
+    A[B, m_max, d], b[B, m_max], m[B] as everywhere; X: the points, [K, d] shared by all polytopes or [B, K, d].
+    -> dict(dist[B, K], x[B, K, d] (None with points=False), face uint64[B, K] and lam[B, K, d] (None unless faces=True),
+    status int32[B, K]); numpy in, numpy out; CUDA tensors in, tensors out on torch's current stream (face as int64: the
+    same bits).  face: bit i set = row i is active at x; lam: the multipliers of those rows in ascending row order with
+    respect to the rows as given, p - x = sum lam_j a_j, zero-padded.
+    status: 0 optimum -- a point that violates no row comes back as x = p bit for bit with dist = 0; 2 the polytope is empty
+    (dist = x = NaN); 4 numerical failure or an input that is not finite; 1 (only with resolve=False) not settled by the
+    kernel.  Every status 0 passed, with E = max(1, |x|_inf, |p|_inf) and unit rows n_i: n_i.x - beta_i <= 1e-10 E on every row,
+    and on the rows of face  sum lam_j |beta_j - n_j.x| <= 1e-10 E max(dist, 1e-10 E)  and  |(p - x) - sum lam_j n_j|_2 <= 1e-12 E,
+    which bounds |x - x*| and dist - dist* (plp_nearest.hpp).  resolve=True (the default) settles what the kernel hands back
+    on the host: the closest feasible projection onto a row subset of size <= d (rows that cannot be active culled by the
+    Chebyshev centre's distance), under the same two checks or status 4; where no subset is feasible cheby_ball_batch decides
+    between 2 and 4.  A caller with resolve=True never sees status 1.
+    d <= 4 and m_max <= 64 only: other shapes raise UnsupportedSize.  There is NO fallback kernel for them."""
+    be = _Backend(A)
+    A, b, m, (B, m_max, d) = _packed(be, A, b, m)
+    X = _support_input(be, X)
+    shp = tuple(X.shape)
+    if len(shp) not in (2, 3):
+        raise ValueError("X must be [K, d] or [B, K, d], got %d dimensions" % len(shp))
+    if shp[-1] != d or (len(shp) == 3 and shp[0] != B):
+        raise ValueError("X must be [K, %d] or [%d, K, %d], got %s" % (d, B, d, list(shp)))
+    K = int(shp[-2])
+    if K < 1:
+        raise ValueError("X holds no point (K = 0)")
+    if d > _NEAREST_MAX_D or m_max > MAX_M:
+        raise _lib.UnsupportedSize("nearest_batch: m_max=%d d=%d outside the shared-row kernel (m <= 64, d <= 4)" % (m_max, d))
+    if B * K > 2 ** 31 - 1:
+        raise _lib.UnsupportedSize("nearest_batch: B * K exceeds 2^31 - 1")
+    shared = len(shp) == 2
+    out = dict(dist=be.out((B, K), zero=True), x=be.out((B, K, d), zero=True) if points else None,
+               face=be.out((B, K), np.uint64, zero=True) if faces else None, lam=be.out((B, K, d), zero=True) if faces else None,
+               status=be.out((B, K), np.int32, zero=True))
+    if B == 0:
+        return out
+    be.call("plp_nearest_batch", B, m_max, d, A, b, m, K, X, 1 if shared else 0, out["dist"], out["x"], out["face"], out["lam"],
+            out["status"], h2d=(A, b, m, X))
+    if resolve:
+        _nearest_resolve(be, A, b, m, X, shared, out)
+    return out
+
+
 def subset_batch(A, b, QA, Qb, m=None, mq=None, abs_tol=1e-7):
     """The exact H-in-H test  P_k <= Q_k  for B pairs: P_k = {A_k x <= b_k} lies in Q_k = {QA_k x <= Qb_k} iff the support
     function of P_k in the direction of every row of Q_k stays below that row's right-hand side.

@@ -980,6 +980,61 @@ int plp_support_batch(plp_ctx* ctx, int64_t B, int m_max, int d, const double* A
     return hc.download();
 }
 
+// ------------------------------------------------------------------------------- nearest points
+namespace {
+int nearest_check(plp_ctx* ctx, int64_t B, int m_max, int d, const double* A, const double* b, int K, const double* X,
+                  const double* dist, const int32_t* status) {
+    if (!ctx) return fail(PLP_EINVAL, "ctx is NULL");
+    if (B < 0 || m_max < 0 || d < 1) return fail(PLP_EINVAL, "bad sizes");
+    if (B == 0) return PLP_OK;
+    if (d > 4 || m_max > plp::MAX_M)
+        return fail(PLP_EUNSUPPORTED, "nearest: m_max=%d d=%d outside the shared-row kernel (m<=64, d<=4)", m_max, d);
+    if (K < 1) return fail(PLP_EUNSUPPORTED, "nearest: K=%d points (needs K >= 1)", K);
+    if (B > 2147483647ll / K) return fail(PLP_EUNSUPPORTED, "nearest: B * K exceeds 2^31 - 1");
+    if (!X || !dist || !status || (m_max > 0 && (!A || !b))) return fail(PLP_EINVAL, "NULL pointer");
+    return PLP_OK;
+}
+}  // namespace
+
+int plp_nearest_batch_dev(plp_ctx* ctx, void* stream, int64_t B, int m_max, int d, const double* A, const double* b,
+                          const int32_t* m, int K, const double* X, int x_shared, double* dist, double* x, uint64_t* face,
+                          double* lam, int32_t* status) {
+    int rc = nearest_check(ctx, B, m_max, d, A, b, K, X, dist, status);
+    if (rc || B == 0) return rc;
+    if (plp::launch_nearest(B, m_max, d, A, b, m, K, X, x_shared, dist, x, (unsigned long long*)face, lam, status,
+                            (hipStream_t)stream))
+        return fail(PLP_EUNSUPPORTED, "nearest: unsupported size");
+    return check_launch("nearest_kernel");
+}
+
+int plp_nearest_batch(plp_ctx* ctx, int64_t B, int m_max, int d, const double* A, const double* b, const int32_t* m, int K,
+                      const double* X, int x_shared, double* dist, double* x, uint64_t* face, double* lam, int32_t* status) {
+    int rc = nearest_check(ctx, B, m_max, d, A, b, K, X, dist, status);
+    if (rc || B == 0) return rc;
+    const size_t n = (size_t)B * K;
+    double *dA, *db, *dX, *ddist, *dx, *dlam;
+    uint64_t* dface;
+    int32_t *dm, *dst;
+    HostCall hc(ctx);
+    hc.in(dA, A, (size_t)B * m_max * d, 0, true);
+    hc.in(db, b, (size_t)B * m_max, 0, true);
+    hc.in(dm, m, B);
+    hc.in(dX, X, (x_shared ? (size_t)K : n) * d, 0, true);
+    hc.out(ddist, dist, n);
+    hc.out(dx, x, x ? n * d : 0);
+    hc.out(dface, face, face ? n : 0);
+    hc.out(dlam, lam, lam ? n * d : 0);
+    hc.out(dst, status, n);
+    rc = hc.reserve();
+    if (rc) return rc;
+    rc = hc.upload();
+    if (rc) return rc;
+    rc = plp_nearest_batch_dev(ctx, hc.st, B, m_max, d, dA, db, dm, K, dX, x_shared, ddist, x ? dx : nullptr,
+                               face ? dface : nullptr, lam ? dlam : nullptr, dst);
+    if (rc) return rc;
+    return hc.download();
+}
+
 // ------------------------------------------------------------------------------- vertex enumeration
 namespace {
 int extreme_check(plp_ctx* ctx, int64_t B, int m_max, int d, const double* A, const double* b, int v_max, const double* V,

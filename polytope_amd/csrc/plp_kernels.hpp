@@ -52,6 +52,11 @@ int launch_volume_hits(long long B, int m_max, int d, const double* A, const dou
 // x[B][K][d] (or nullptr), status[B][K] (0 optimum, 3 unbounded, 1 handed back).  2: unsupported size
 int launch_support(long long B, int m_max, int d, const double* A, const double* b, const int* mrows, int K, const double* C,
                    int c_shared, const double* xc, double* val, double* x, int* status, hipStream_t st);
+// nearest points / Euclidean distances of K points per polytope, rows staged once per (tile, K-chunk) at unit norm
+// (plp_nearest.hip; d <= 4, m_max <= 64): dist[B][K], status[B][K] (0 optimum, 2 empty, 1 handed back); x[B][K][d],
+// face[B][K], lam[B][K][d] each or nullptr.  2: unsupported size
+int launch_nearest(long long B, int m_max, int d, const double* A, const double* b, const int* mrows, int K, const double* X,
+                   int x_shared, double* dist, double* x, unsigned long long* face, double* lam, int* status, hipStream_t st);
 // vertices of small polytopes by enumeration of bases, one polytope per wavefront (plp_extreme.hip; d <= 4, m_max <= 64):
 // V[B][v_max][d], count[B], basis[B][v_max][d] (or nullptr), status[B] (0, 1 overflow, 2 empty).  2: unsupported size
 int launch_extreme(long long B, int m_max, int d, const double* A, const double* b, const int* mrows,

@@ -190,6 +190,14 @@ class Polytope(object):
         (strict; abs_tol=0 excludes the boundary).  ref :206-218."""
         return _contains_many([self], points, abs_tol, region=True)
 
+    def nearest(self, points):
+        """(x[N, d], dist[N]): the closest point of this polytope to every column of `points` ([d, N]); module-level nearest."""
+        return nearest(self, points)
+
+    def distance(self, points):
+        """dist[N]: the Euclidean distance of every column of `points` ([d, N]) to this polytope."""
+        return distance(self, points)
+
     def __eq__(self, other):
         return self <= other and other <= self
 
@@ -373,6 +381,15 @@ class Region(_NoDeviceState):
         if points.shape[0] != self.dim:
             raise ValueError("points should be column vectors")
         return _contains_many(self.list_poly, points, abs_tol, region=True, owner=self)
+
+    def nearest(self, points):
+        """(x[N, d], dist[N], member int32[N]): the closest point of the union of the members to every column of `points`
+        ([d, N]) and the member it lies in (lowest index on ties); module-level nearest."""
+        return nearest(self, points)
+
+    def distance(self, points):
+        """dist[N]: the Euclidean distance of every column of `points` ([d, N]) to this region."""
+        return distance(self, points)
 
     def locate(self, points, abs_tol=ABS_TOL):
         """For each column of `points` the index into `list_poly` of the FIRST member that contains it, or -1 (int32[N];
@@ -2336,6 +2353,83 @@ def volume_exact(poly):
         return 0.0   # (the empty Polytope())
     res = batch.volume_exact_batch(A[np.newaxis], np.asarray(poly.b, dtype=float).reshape(1, -1), areas=False)
     return float(res["volume"][0])
+
+
+# ====================================================================================== nearest points
+_NEAREST_BYTES = 256 << 20   # the [P, chunk] buffers of one nearest_batch call over a Region's members stay below this
+
+
+def _nearest_many(polys, points, owner=None):
+    """(x[N, d], dist[N], member int32[N]) over the non-empty descriptions of `polys`: per column of `points` the closest
+    point of the union, its distance and the index into `polys` of the member it lies in (the lowest on ties; -1 with
+    dist = inf and x = NaN where no member has a point: all empty, or the point is not finite).  'hip' only: one
+    batch.nearest_batch per chunk of points, every member against every point of the chunk, and the minimum over the
+    members -- on the device when the table is resident there."""
+    if not _use_hip():
+        raise ValueError("nearest / distance need the 'hip' backend (polytope_amd.batch.nearest_batch), got %r"
+                         % (solvers.default_solver,))
+    solvers._require("hip")
+    points = np.asarray(points, dtype=float)
+    if points.ndim != 2:
+        raise ValueError("points should be column vectors")
+    d, N = points.shape
+    idx = np.array([k for k, p in enumerate(polys) if p.A.size > 0], dtype=np.int64)
+    x, dist, member = np.full((N, d), np.nan), np.full(N, np.inf), np.full(N, -1, dtype=np.int32)
+    if idx.size == 0 or N == 0:
+        return x, dist, member
+    members = [polys[k] for k in idx]
+    if members[0].A.shape[1] != d:
+        raise ValueError("points should be column vectors")
+    from . import batch
+    if len(members) >= 8:
+        At, bt, mt = _table_of(members, owner).dev()
+    else:
+        At, bt, mt = _pack(members)
+    P = len(members)
+    on_dev = not isinstance(At, np.ndarray)
+    torch = _torch_or_none() if on_dev else None
+    # per (member, point): dist, x[d], status and the kernel's staging of them
+    chunk = max(1, min(N, _NEAREST_BYTES // (P * 8 * (d + 2))))
+    pts = np.ascontiguousarray(points.T)
+    for lo in range(0, N, chunk):
+        X = pts[lo:lo + chunk]
+        if on_dev:
+            batch._count_h2d(X)
+            X = torch.as_tensor(X).to(At.device)
+        res = batch.nearest_batch(At, bt, X, m=mt)
+        if on_dev:
+            dd = torch.where(res["status"] == 0, res["dist"], torch.full_like(res["dist"], float("inf")))
+            best, arg = torch.min(dd, dim=0)             # (the first of equal minima is not promised by torch.min:)
+            arg = torch.argmax((dd == best[None, :]).to(torch.int8), dim=0)
+            xs = res["x"][arg, torch.arange(arg.shape[0], device=arg.device)]
+            best, arg, xs = best.cpu().numpy(), arg.cpu().numpy(), xs.cpu().numpy()
+        else:
+            dd = np.where(res["status"] == 0, res["dist"], np.inf)
+            arg = np.argmin(dd, axis=0)
+            best = dd[arg, np.arange(arg.size)]
+            xs = res["x"][arg, np.arange(arg.size)]
+        ok = np.isfinite(best)
+        sl = slice(lo, lo + best.size)
+        dist[sl] = best
+        x[sl] = np.where(ok[:, None], xs, np.nan)
+        member[sl] = np.where(ok, idx[arg], -1)
+    return x, dist, member
+
+
+def nearest(polyreg, points):
+    """The closest point of a Polytope or Region to every column of `points` ([d, N] column vectors, the convention of
+    `contains`).  Polytope -> (x[N, d], dist[N]); Region -> (x[N, d], dist[N], member int32[N]): the minimum over the members,
+    the lowest index on ties.  An empty set gives x = NaN, dist = inf (member -1).  Dimension <= 4 and at most 64 rows per
+    polytope (batch.nearest_batch; other shapes raise UnsupportedSize); 'hip' backend only."""
+    if isinstance(polyreg, Region):
+        return _nearest_many(polyreg.list_poly, points, owner=polyreg)
+    x, dist, _ = _nearest_many([polyreg], points)
+    return x, dist
+
+
+def distance(polyreg, points):
+    """The Euclidean distance of every column of `points` ([d, N]) to a Polytope or Region: nearest(polyreg, points)[1]."""
+    return nearest(polyreg, points)[1]
 
 
 # ====================================================================================== adjacency

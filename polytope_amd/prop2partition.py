@@ -431,6 +431,24 @@ class Partition(pc._NoDeviceState):
             return hit
         return np.where(hit >= 0, region_of[np.maximum(hit, 0)], -1).astype(np.int32)
 
+    def nearest(self, points):
+        """(region int32[N], dist[N]): for each column of `points` ([d, N] column vectors, as `locate`) the index of the
+        region closest to it and the distance -- the containing region with distance 0 where `locate` finds one, and an
+        answer where it gives -1.  The lowest member (hence region) index on ties; -1 and inf where no region has a point.
+        One batch.nearest_batch over the flat member table per chunk of points ('hip' backend only)."""
+        regions = _regions_of(self)
+        points = np.asarray(points, dtype=float)
+        if points.ndim != 2:
+            raise ValueError("points should be column vectors")
+        if not regions:
+            return np.full(points.shape[1], -1, dtype=np.int32), np.full(points.shape[1], np.inf)
+        members, first, _ = _flat_members(regions, self)
+        _, dist, hit = pc._nearest_many(members, points, owner=self)
+        region_of = np.repeat(np.arange(len(regions)), np.diff(first))
+        if region_of.size == 0:
+            return hit, dist
+        return np.where(hit >= 0, region_of[np.maximum(hit, 0)], -1).astype(np.int32), dist
+
     def is_partition(self):
         """Return True if Regions are pairwise disjoint and cover domain (ref :102-105)."""
         return self.is_cover() and self.are_disjoint()
