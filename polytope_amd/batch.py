@@ -668,6 +668,21 @@ def _support_input(be, a):
     return be.arr(a)
 
 
+def _items_input(be, a, name, noun, B, d):
+    """The per-polytope items of the shared-row calls (the directions C of support_batch, the points X of nearest_batch) on
+    the backend of A: [K, d] shared by all polytopes or [B, K, d] -> (array, K, shared)."""
+    a = _support_input(be, a)
+    shp = tuple(a.shape)
+    if len(shp) not in (2, 3):
+        raise ValueError("%s must be [K, d] or [B, K, d], got %d dimensions" % (name, len(shp)))
+    if shp[-1] != d or (len(shp) == 3 and shp[0] != B):
+        raise ValueError("%s must be [K, %d] or [%d, K, %d], got %s" % (name, d, B, d, list(shp)))
+    K = int(shp[-2])
+    if K < 1:
+        raise ValueError("%s holds no %s (K = 0)" % (name, noun))
+    return a, K, len(shp) == 2
+
+
 def _support_pairs(be, A, b, m, C, shared, pi, ji, flat, h, x, status):
     """The LPs (polytope pi[t], direction ji[t]) as generic LPs  min -c.x  s.t. A x <= b  through lpsolve_batch, the rows
     gathered per pair, at most _SUPPORT_CHUNK LPs per call; results written to position flat[t] of h / x / status."""
@@ -712,16 +727,7 @@ def support_batch(A, b, C, m=None, xc=None, points=True, resolve=True):
     kernel's own certificate is not that one."""
     be = _Backend(A)
     A, b, m, (B, m_max, d) = _packed(be, A, b, m)
-    C = _support_input(be, C)
-    shp = tuple(C.shape)
-    if len(shp) not in (2, 3):
-        raise ValueError("C must be [K, d] or [B, K, d], got %d dimensions" % len(shp))
-    if shp[-1] != d or (len(shp) == 3 and shp[0] != B):
-        raise ValueError("C must be [K, %d] or [%d, K, %d], got %s" % (d, B, d, list(shp)))
-    K = int(shp[-2])
-    if K < 1:
-        raise ValueError("C holds no direction (K = 0)")
-    shared = len(shp) == 2
+    C, K, shared = _items_input(be, C, "C", "direction", B, d)
     if xc is not None:
         xc = _support_input(be, xc)
         if tuple(xc.shape) != (B, d):
@@ -910,20 +916,11 @@ def nearest_batch(A, b, X, m=None, points=True, faces=False, resolve=True):
     d <= 4 and m_max <= 64 only: other shapes raise UnsupportedSize.  There is NO fallback kernel for them."""
     be = _Backend(A)
     A, b, m, (B, m_max, d) = _packed(be, A, b, m)
-    X = _support_input(be, X)
-    shp = tuple(X.shape)
-    if len(shp) not in (2, 3):
-        raise ValueError("X must be [K, d] or [B, K, d], got %d dimensions" % len(shp))
-    if shp[-1] != d or (len(shp) == 3 and shp[0] != B):
-        raise ValueError("X must be [K, %d] or [%d, K, %d], got %s" % (d, B, d, list(shp)))
-    K = int(shp[-2])
-    if K < 1:
-        raise ValueError("X holds no point (K = 0)")
+    X, K, shared = _items_input(be, X, "X", "point", B, d)
     if d > _NEAREST_MAX_D or m_max > MAX_M:
         raise _lib.UnsupportedSize("nearest_batch: m_max=%d d=%d outside the shared-row kernel (m <= 64, d <= 4)" % (m_max, d))
     if B * K > 2 ** 31 - 1:
         raise _lib.UnsupportedSize("nearest_batch: B * K exceeds 2^31 - 1")
-    shared = len(shp) == 2
     out = dict(dist=be.out((B, K), zero=True), x=be.out((B, K, d), zero=True) if points else None,
                face=be.out((B, K), np.uint64, zero=True) if faces else None, lam=be.out((B, K, d), zero=True) if faces else None,
                status=be.out((B, K), np.int32, zero=True))

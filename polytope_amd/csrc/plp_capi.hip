@@ -1,6 +1,8 @@
 // plp_capi.hip -- extern "C" boundary of libplp_hip.so (declared in include/plp.h).
 // Host-pointer entry points stage through a grow-only device scratch arena owned by the
 // context, call the *_dev entry point on the context's stream and synchronise.
+#include <initializer_list>
+
 #include "plp_hostcall.hpp"
 #include "plp_locate.hpp"
 #include "plp_lp_plan.hpp"
@@ -929,26 +931,30 @@ int plp_volume_hits(plp_ctx* ctx, int64_t B, int m_max, int d, const double* A, 
     return hc.download();
 }
 
-// ------------------------------------------------------------------------------- support functions
+// ------------------------------------------------------------------------------- the shared-row kernels
 namespace {
-int support_check(plp_ctx* ctx, int64_t B, int m_max, int d, const double* A, const double* b, int K, const double* C,
-                  const double* xc, const double* val, const int32_t* status) {
+// the arguments every entry of the family checks (plp_row_tile.hpp): `what` the call, `items` its K things per polytope;
+// need: the pointers that may not be NULL
+int shared_row_check(const char* what, const char* items, plp_ctx* ctx, int64_t B, int m_max, int d, const double* A,
+                     const double* b, int K, std::initializer_list<const void*> need) {
     if (!ctx) return fail(PLP_EINVAL, "ctx is NULL");
     if (B < 0 || m_max < 0 || d < 1) return fail(PLP_EINVAL, "bad sizes");
     if (B == 0) return PLP_OK;
     if (d > 4 || m_max > plp::MAX_M)
-        return fail(PLP_EUNSUPPORTED, "support: m_max=%d d=%d outside the shared-row kernel (m<=64, d<=4)", m_max, d);
-    if (K < 1) return fail(PLP_EUNSUPPORTED, "support: K=%d directions (needs K >= 1)", K);
-    if (B > 2147483647ll / K) return fail(PLP_EUNSUPPORTED, "support: B * K exceeds 2^31 - 1");
-    if (!C || !xc || !val || !status || (m_max > 0 && (!A || !b))) return fail(PLP_EINVAL, "NULL pointer");
-    return PLP_OK;
+        return fail(PLP_EUNSUPPORTED, "%s: m_max=%d d=%d outside the shared-row kernel (m<=64, d<=4)", what, m_max, d);
+    if (K < 1) return fail(PLP_EUNSUPPORTED, "%s: K=%d %s (needs K >= 1)", what, K, items);
+    if (B > 2147483647ll / K) return fail(PLP_EUNSUPPORTED, "%s: B * K exceeds 2^31 - 1", what);
+    bool null = m_max > 0 && (!A || !b);
+    for (const void* q : need) null = null || !q;
+    return null ? fail(PLP_EINVAL, "NULL pointer") : PLP_OK;
 }
 }  // namespace
 
+// ------------------------------------------------------------------------------- support functions
 int plp_support_batch_dev(plp_ctx* ctx, void* stream, int64_t B, int m_max, int d, const double* A, const double* b,
                           const int32_t* m, int K, const double* C, int c_shared, const double* xc, double* val, double* x,
                           int32_t* status) {
-    int rc = support_check(ctx, B, m_max, d, A, b, K, C, xc, val, status);
+    int rc = shared_row_check("support", "directions", ctx, B, m_max, d, A, b, K, {C, xc, val, status});
     if (rc || B == 0) return rc;
     if (plp::launch_support(B, m_max, d, A, b, m, K, C, c_shared, xc, val, x, status, (hipStream_t)stream))
         return fail(PLP_EUNSUPPORTED, "support: unsupported size");
@@ -957,7 +963,7 @@ int plp_support_batch_dev(plp_ctx* ctx, void* stream, int64_t B, int m_max, int 
 
 int plp_support_batch(plp_ctx* ctx, int64_t B, int m_max, int d, const double* A, const double* b, const int32_t* m, int K,
                       const double* C, int c_shared, const double* xc, double* val, double* x, int32_t* status) {
-    int rc = support_check(ctx, B, m_max, d, A, b, K, C, xc, val, status);
+    int rc = shared_row_check("support", "directions", ctx, B, m_max, d, A, b, K, {C, xc, val, status});
     if (rc || B == 0) return rc;
     const size_t lps = (size_t)B * K;
     double *dA, *db, *dC, *dxc, *dval, *dx;
@@ -981,25 +987,10 @@ int plp_support_batch(plp_ctx* ctx, int64_t B, int m_max, int d, const double* A
 }
 
 // ------------------------------------------------------------------------------- nearest points
-namespace {
-int nearest_check(plp_ctx* ctx, int64_t B, int m_max, int d, const double* A, const double* b, int K, const double* X,
-                  const double* dist, const int32_t* status) {
-    if (!ctx) return fail(PLP_EINVAL, "ctx is NULL");
-    if (B < 0 || m_max < 0 || d < 1) return fail(PLP_EINVAL, "bad sizes");
-    if (B == 0) return PLP_OK;
-    if (d > 4 || m_max > plp::MAX_M)
-        return fail(PLP_EUNSUPPORTED, "nearest: m_max=%d d=%d outside the shared-row kernel (m<=64, d<=4)", m_max, d);
-    if (K < 1) return fail(PLP_EUNSUPPORTED, "nearest: K=%d points (needs K >= 1)", K);
-    if (B > 2147483647ll / K) return fail(PLP_EUNSUPPORTED, "nearest: B * K exceeds 2^31 - 1");
-    if (!X || !dist || !status || (m_max > 0 && (!A || !b))) return fail(PLP_EINVAL, "NULL pointer");
-    return PLP_OK;
-}
-}  // namespace
-
 int plp_nearest_batch_dev(plp_ctx* ctx, void* stream, int64_t B, int m_max, int d, const double* A, const double* b,
                           const int32_t* m, int K, const double* X, int x_shared, double* dist, double* x, uint64_t* face,
                           double* lam, int32_t* status) {
-    int rc = nearest_check(ctx, B, m_max, d, A, b, K, X, dist, status);
+    int rc = shared_row_check("nearest", "points", ctx, B, m_max, d, A, b, K, {X, dist, status});
     if (rc || B == 0) return rc;
     if (plp::launch_nearest(B, m_max, d, A, b, m, K, X, x_shared, dist, x, (unsigned long long*)face, lam, status,
                             (hipStream_t)stream))
@@ -1009,7 +1000,7 @@ int plp_nearest_batch_dev(plp_ctx* ctx, void* stream, int64_t B, int m_max, int 
 
 int plp_nearest_batch(plp_ctx* ctx, int64_t B, int m_max, int d, const double* A, const double* b, const int32_t* m, int K,
                       const double* X, int x_shared, double* dist, double* x, uint64_t* face, double* lam, int32_t* status) {
-    int rc = nearest_check(ctx, B, m_max, d, A, b, K, X, dist, status);
+    int rc = shared_row_check("nearest", "points", ctx, B, m_max, d, A, b, K, {X, dist, status});
     if (rc || B == 0) return rc;
     const size_t n = (size_t)B * K;
     double *dA, *db, *dX, *ddist, *dx, *dlam;

@@ -2,8 +2,8 @@
 // per polytope, the rows read once: nearest_kernel<D, RV> (plp_nearest.hip) behind plp_nearest_batch.
 //
 // Not an LP: a strictly convex QP with the identity as Hessian, solved per lane by a dual active-set walk in the manner of
-// Goldfarb and Idnani (Math. Programming 27, 1983).  The tiles are those of plp_support.hpp (one wavefront per workgroup,
-// NP polytopes of RV row slots in LDS, polytope-interleaved, 64 / NP lanes per polytope, one problem per lane).
+// Goldfarb and Idnani (Math. Programming 27, 1983).  The tiles, the LDS layout and the frame of the kernel are those of
+// plp_row_tile.hpp, with two staged scalars per row (beta_i, |a_i|); plp_support.hpp gives the three end tolerances.
 //
 // Rows.  Staged at unit 2-norm,  n_i = a_i / |a_i|,  beta_i = b_i / |a_i|,  with |a_i| kept beside them (the multipliers are
 // given back with respect to the rows as passed).  A zero row with b_i >= 0 binds nowhere and is staged as (0, 0); a zero row
@@ -72,7 +72,7 @@
 namespace plp {
 namespace nearest {
 
-constexpr int MAX_DIM = 4, MAX_ROWS = 64;
+constexpr int MAX_DIM = 4;
 constexpr double END_TOL = support::END_TOL;            // feasibility, relative to E
 constexpr double OPT_TOL_GAP = support::OPT_TOL_GAP;    // complementary slackness, relative to E max(dist, OPT_TOL_GAP E)
 constexpr double OPT_TOL_RES = support::OPT_TOL_RES;    // |(p - x) - sum lam_j n_j|_2, relative to E
@@ -80,19 +80,12 @@ constexpr double FARKAS_RES = 1e-12, FARKAS_GAP = 1e-10;
 constexpr double STOP_TOL = 1e-12;   // the walk stops when no row is violated by more than this times E (END_TOL / 100)
 constexpr double DEP_TOL = 1e-12;    // |z|^2 below this: n_t is taken as dependent on W (an angle of 1e-6 to their span)
 constexpr int ZERO_RUN = 6;          // steps of length zero in a row before the walk hands back
-constexpr int K_ROUNDS = 8;          // rounds of one K-chunk (plp_nearest.hip): rows are staged once per 8 rounds at most
+constexpr int K_ROUNDS = 8;          // rounds of one K-chunk (rowtile::chunk_rounds): rows are staged once per 8 rounds at most
 
 constexpr int iter_cap(int m, int D) { return 2 * (m + 2 * D) + 4; }
-constexpr int row_slots(int m_max) { return support::row_slots(m_max); }
-constexpr int polytopes_per_group(int K, int rv) { return support::polytopes_per_group(K, rv); }
-// n_i, beta_i and |a_i| per row slot
-constexpr size_t lds_bytes(int D, int rv, int np) { return (size_t)np * rv * (D + 2) * sizeof(double); }
-// rounds of a K-chunk for L lanes per polytope: K_ROUNDS, more only where the second grid index would pass 65535
-constexpr int chunk_rounds(int K, int L) {
-    const long long rounds = ((long long)K + L - 1) / L;
-    const long long need = (rounds + 65534) / 65535;
-    return need > K_ROUNDS ? (int)need : K_ROUNDS;
-}
+using rowtile::polytopes_per_group, rowtile::row_slots;   // (as in plp_support.hpp)
+// rounds of a K-chunk for L lanes per polytope
+constexpr int chunk_rounds(int K, int L) { return rowtile::chunk_rounds(K, L, K_ROUNDS); }
 
 template <int D>
 PLP_LANE_FN double dotd(const double (&a)[D], const double (&b)[D]) {
@@ -189,7 +182,7 @@ template <int D, int RV>
 PLP_LANE_FN void solve_one(const double* pN, const double* pbeta, const double* pnrm, const int LS, const int m,
                            const double (&p)[D], double& dist, double (&x)[D], uint64_t& face, double (&lam)[D], int& status) {
     static_assert(D >= 1 && D <= MAX_DIM, "the active set is held in registers for D <= 4");
-    static_assert(RV <= MAX_ROWS, "face is one 64-bit word");
+    static_assert(RV <= rowtile::MAX_ROWS, "face is one 64-bit word");
     auto row_of = [&](const int i, double (&a)[D]) {
         const double* base = pN + (size_t)(i * D) * LS;
 #pragma unroll

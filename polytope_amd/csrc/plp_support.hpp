@@ -6,19 +6,7 @@
 // cost.  A workgroup (one wavefront) stages the rows of its polytopes into LDS once, as a_i and beta_i, and every lane
 // walks one direction of one polytope; K directions of a polytope take L lanes and ceil(K / L) rounds.
 //
-// Tiles.  L = min(64, next power of two >= K) lanes per polytope would put 64 / L polytopes on the wavefront; the rows of
-// NP polytopes take NP * RV * (D + 1) * 8 bytes of LDS, so NP is capped per RV (and L raised to 64 / NP, the extra lanes
-// idle) at a footprint that leaves room for four workgroups on a CU's 160 KiB:
-//
-//     RV (row slots)   polytopes per workgroup, at most   LDS at the cap, D = 3 / D = 4   workgroups per CU by LDS
-//         16                     64                              32 KiB / 40 KiB                     5 / 4
-//         32                     32                              32 KiB / 40 KiB                     5 / 4
-//         64                     16                              32 KiB / 40 KiB                     5 / 4
-//
-// (K >= 33: one polytope per workgroup, 0.5 .. 2.5 KiB.)  LDS layout: POLYTOPE-INTERLEAVED as in plp_reduce_lane.hpp --
-// element (row i, column k) of the tile's polytope p at sA[(i * D + k) * NP + p], beta_i at sbeta[i * NP + p].  The lanes
-// of one polytope read one address (a broadcast); lanes of different polytopes read consecutive doubles: within a
-// 32-lane half at most 32 of them, 256 bytes = every bank once.
+// Tiles, the LDS layout and the frame of the kernel: plp_row_tile.hpp (one staged scalar per row, beta_i).
 //
 // Status per (polytope, direction), the contract of bbox_lane_kernel:
 //     0  optimum: val = c.x, x = xc + x'
@@ -47,24 +35,15 @@
 #include <stddef.h>
 
 #include "plp_lane_lp.hpp"
+#include "plp_row_tile.hpp"
 
 namespace plp {
 namespace support {
 
 constexpr double END_TOL = 1e-10;   // end check, feasibility: relative to min(max(1, |beta|_max), max(1, |x|_inf))
-constexpr int MAX_DIM = 4, MAX_ROWS = 64;
-
-// row slots for polytopes of up to m_max rows (0: not taken)
-constexpr int row_slots(int m_max) { return m_max < 0 || m_max > MAX_ROWS ? 0 : (m_max <= 16 ? 16 : (m_max <= 32 ? 32 : 64)); }
-// polytopes per workgroup at most (the table above)
-constexpr int np_cap(int rv) { return 1024 / rv; }
-// polytopes per workgroup for K directions: 64 / L, capped; each gets 64 / NP lanes
-constexpr int polytopes_per_group(int K, int rv) {
-    int L = 1;
-    while (L < 64 && L < K) L <<= 1;
-    return 64 / L < np_cap(rv) ? 64 / L : np_cap(rv);
-}
-constexpr size_t lds_bytes(int D, int rv, int np) { return (size_t)np * rv * (D + 1) * sizeof(double); }
+constexpr int MAX_DIM = 4;
+// (the tile rules under the names they had here before plp_row_tile.hpp: host restatements written against those still build)
+using rowtile::polytopes_per_group, rowtile::row_slots;
 
 // beta_i = b_i - a_i.xc, the sum in column order
 template <int D>

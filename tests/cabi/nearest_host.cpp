@@ -1,84 +1,52 @@
 // Host build of polytope_amd/csrc/plp_nearest.hpp (the per-problem function of nearest_kernel, plp_nearest.hip): TEST
-// INFRASTRUCTURE, compiled with g++ -ffp-contract=off by tests/nearest_host.py.  nearest_host is plp_nearest_batch in a
-// plain loop: per polytope the rows staged as the kernel stages them (n_i, beta_i, |a_i|, zero rows beyond m), then one
-// solve_one per point -- the device's answers are held against these bit for bit.
+// INFRASTRUCTURE, compiled with g++ -ffp-contract=off by tests/nearest_host.py.  nearest_host is plp_nearest_batch in the
+// plain loop of row_tile_host.hpp: per polytope the rows staged as the kernel stages them (n_i, beta_i, |a_i|, zero rows
+// beyond m), then one solve_one per point -- the device's answers are held against these bit for bit.
 //
 // -DNEAREST_HOST_MAIN adds a main(): a stand-alone program for a run under -fsanitize=address,undefined without anything
 // loaded into an interpreter.  It runs the same loop over the records of the files named on its command line (written by
 // tests/nearest_host.py: write_records -- int64 B, m_max, d, K, x_shared, then A, b as doubles, m as int32, X as doubles),
 // or, without arguments, over polytopes it makes itself.
-#include <stdint.h>
-
 #include "../../polytope_amd/csrc/plp_nearest.hpp"
-
-namespace {
-
-template <int D, int RV>
-void run_d(long long B, int m_max, const double* A, const double* b, const int* m, int K, const double* X, int x_shared,
-           double* dist, double* x, uint64_t* face, double* lam, int* status) {
-    for (long long p = 0; p < B; ++p) {
-        int mk = m ? m[p] : m_max;
-        mk = mk < 0 ? 0 : (mk > m_max ? m_max : mk);
-        double sN[RV * D], sbeta[RV], snrm[RV];
-        for (int i = 0; i < RV; ++i) {
-            const bool live = i < mk;
-            const double* src = A + ((size_t)p * m_max + (live ? i : 0)) * D;
-            double n[D];
-            plp::nearest::stage_row<D>(src, live ? b[(size_t)p * m_max + i] : 0.0, live, n, sbeta[i], snrm[i]);
-            for (int k = 0; k < D; ++k) sN[i * D + k] = n[k];
-        }
-        for (int j = 0; j < K; ++j) {
-            const size_t q = (size_t)p * K + j;
-            const double* src = X + (x_shared ? (size_t)j : q) * D;
-            double pt[D], xo[D], lo[D], dd;
-            for (int k = 0; k < D; ++k) pt[k] = src[k];
-            uint64_t fc;
-            int st;
-            plp::nearest::solve_one<D, RV>(sN, sbeta, snrm, 1, mk, pt, dd, xo, fc, lo, st);
-            dist[q] = dd;
-            status[q] = st;
-            if (face) face[q] = fc;
-            for (int k = 0; k < D; ++k) {
-                if (x) x[q * D + k] = xo[k];
-                if (lam) lam[q * D + k] = lo[k];
-            }
-        }
-    }
-}
-
-template <int D>
-void run_rv(long long B, int m_max, const double* A, const double* b, const int* m, int K, const double* X, int x_shared,
-            double* dist, double* x, uint64_t* face, double* lam, int* status) {
-    const int rv = plp::nearest::row_slots(m_max);
-    if (rv == 16) run_d<D, 16>(B, m_max, A, b, m, K, X, x_shared, dist, x, face, lam, status);
-    else if (rv == 32) run_d<D, 32>(B, m_max, A, b, m, K, X, x_shared, dist, x, face, lam, status);
-    else run_d<D, 64>(B, m_max, A, b, m, K, X, x_shared, dist, x, face, lam, status);
-}
-
-}  // namespace
+#include "row_tile_host.hpp"
 
 // the arguments of plp_nearest_batch without the context; 0, or 2 for a size the kernel does not take
 extern "C" int nearest_host(long long B, int m_max, int d, const double* A, const double* b, const int* m, int K,
                             const double* X, int x_shared, double* dist, double* x, uint64_t* face, double* lam, int* status) {
-    if (d < 1 || d > 4 || plp::nearest::row_slots(m_max) == 0 || K < 1) return 2;
-    switch (d) {
-        case 1: run_rv<1>(B, m_max, A, b, m, K, X, x_shared, dist, x, face, lam, status); break;
-        case 2: run_rv<2>(B, m_max, A, b, m, K, X, x_shared, dist, x, face, lam, status); break;
-        case 3: run_rv<3>(B, m_max, A, b, m, K, X, x_shared, dist, x, face, lam, status); break;
-        default: run_rv<4>(B, m_max, A, b, m, K, X, x_shared, dist, x, face, lam, status); break;
-    }
-    return 0;
+    return rowhost::dispatch(m_max, d, K, [&](auto dim, auto rows) {
+        constexpr int D = decltype(dim)::value, RV = decltype(rows)::value;
+        rowhost::run<D, RV, 2>(
+            B, m_max, A, b, m, K,
+            [](long long, const double* a, double bi, bool live, auto& n, auto& s) {
+                plp::nearest::stage_row<D>(a, bi, live, n, s[0], s[1]);
+            },
+            [&](long long, int j, size_t q, int mk, const double* sN, const auto& planes) {
+                const double* src = X + (x_shared ? (size_t)j : q) * D;
+                double pt[D], xo[D], lo[D], dd;
+                for (int k = 0; k < D; ++k) pt[k] = src[k];
+                uint64_t fc;
+                int st;
+                plp::nearest::solve_one<D, RV>(sN, planes[0], planes[1], 1, mk, pt, dd, xo, fc, lo, st);
+                dist[q] = dd;
+                status[q] = st;
+                if (face) face[q] = fc;
+                for (int k = 0; k < D; ++k) {
+                    if (x) x[q * D + k] = xo[k];
+                    if (lam) lam[q * D + k] = lo[k];
+                }
+            });
+    });
 }
 
 // polytopes per workgroup and points of one K-chunk the launcher picks for (K, m_max): the tests cross them with their sizes
 extern "C" int nearest_polytopes_per_group(int K, int m_max) {
-    const int rv = plp::nearest::row_slots(m_max);
-    return rv ? plp::nearest::polytopes_per_group(K, rv) : 0;
+    const int rv = plp::rowtile::row_slots(m_max);
+    return rv ? plp::rowtile::polytopes_per_group(K, rv) : 0;
 }
 extern "C" int nearest_chunk_points(int K, int m_max) {
-    const int rv = plp::nearest::row_slots(m_max);
+    const int rv = plp::rowtile::row_slots(m_max);
     if (!rv) return 0;
-    const int L = 64 / plp::nearest::polytopes_per_group(K, rv);
+    const int L = 64 / plp::rowtile::polytopes_per_group(K, rv);
     return plp::nearest::chunk_rounds(K, L) * L;
 }
 extern "C" int nearest_iter_cap(int m, int d) { return plp::nearest::iter_cap(m, d); }
@@ -86,14 +54,7 @@ extern "C" int nearest_iter_cap(int m, int d) { return plp::nearest::iter_cap(m,
 #ifdef NEAREST_HOST_MAIN
 #include <stdio.h>
 
-#include <vector>
-
 namespace {
-uint64_t g_s = 0x9e3779b97f4a7c15ull;
-double unif() {   // xorshift64*, [0, 1)
-    g_s ^= g_s >> 12; g_s ^= g_s << 25; g_s ^= g_s >> 27;
-    return (double)((g_s * 0x2545f4914f6cdd1dull) >> 11) * (1.0 / 9007199254740992.0);
-}
 long long g_n = 0, g_c[3] = {0, 0, 0}, g_bad = 0;
 
 void run_record(long long B, int m_max, int d, int K, int x_shared, const double* A, const double* b, const int* m,
@@ -136,30 +97,17 @@ int main(int argc, char** argv) {
         fclose(fp);
     }
     if (argc < 2) {
-        const int shapes[][2] = {{5, 1}, {7, 2}, {16, 3}, {17, 3}, {33, 4}, {64, 4}, {0, 2}, {3, 3}};
-        for (const auto& sh : shapes) {
+        rowhost::Rng g;
+        for (const auto& sh : rowhost::SHAPES) {
             const int m_max = sh[0], d = sh[1];
             for (int K : {1, 9, 65}) {
                 for (int xs = 0; xs < 2; ++xs) {
-                    const long long B = 23;
-                    std::vector<double> A((size_t)B * m_max * d), b((size_t)B * m_max), X((xs ? (size_t)K : (size_t)B * K) * d);
-                    std::vector<int> m(B);
-                    for (long long p = 0; p < B; ++p) {
-                        m[p] = m_max ? 1 + (int)(unif() * m_max) : 0;
-                        if (p % 5 == 0) m[p] = m_max;
-                        for (int i = 0; i < m_max; ++i) {
-                            double* a = &A[((size_t)p * m_max + i) * d];
-                            if (i < 2 * d) {   // box rows |x_k| <= 3 first
-                                for (int k = 0; k < d; ++k) a[k] = 0.0;
-                                a[i % d] = i < d ? 1.0 : -1.0;
-                                b[(size_t)p * m_max + i] = 3.0;
-                            } else {
-                                for (int k = 0; k < d; ++k) a[k] = 2.0 * unif() - 1.0;
-                                b[(size_t)p * m_max + i] = p % 7 == 3 ? -4.0 : 1.0 + unif();   // (some are empty)
-                            }
-                        }
-                    }
-                    for (double& v : X) v = 12.0 * unif() - 6.0;
+                    const long long B = rowhost::B_MADE;
+                    std::vector<double> A, b, X((xs ? (size_t)K : (size_t)B * K) * d);
+                    std::vector<int> m;
+                    rowhost::make_polytopes(g, m_max, d, A, b, m,   // (some are empty)
+                                            [&](long long p, double*) { return p % 7 == 3 ? -4.0 : 1.0 + g.unif(); });
+                    for (double& v : X) v = 12.0 * g.unif() - 6.0;
                     if (K > 1) X[0] = __builtin_nan("");
                     run_record(B, m_max, d, K, xs, A.data(), b.data(), m.data(), X.data());
                 }

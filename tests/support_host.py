@@ -4,11 +4,13 @@ answers against the host build bit for bit, and against the oracle) share: famil
 import ctypes as C
 import functools
 import os
-import subprocess
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import host_build as hb
+
+ROOT = hb.ROOT
+SRC = os.path.join(ROOT, "tests", "cabi", "support_host.cpp")
 
 # (m_max, d) of the random families; the seed of family k is SEED0 + k (kept here: the GPU tests reuse them)
 SHAPES = ((5, 1), (7, 2), (16, 3), (17, 3), (33, 4), (64, 4))
@@ -37,10 +39,12 @@ HANDBACK_CAPS = {"random": 0.01, "ragged": 0.01, "unbounded": 0.01, "scaled": 0.
 
 def build(tmpdir, as_path=False):
     """Compiles the host build into tmpdir -> the loaded library, or (as_path) the path of the shared object."""
-    out = os.path.join(str(tmpdir), "libsupport_host.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", out,
-                           os.path.join(ROOT, "tests", "cabi", "support_host.cpp")])
+    out = hb.build(SRC, "libsupport_host.so", tmpdir)
     return out if as_path else load(out)
+
+
+def build_program(tmpdir):
+    return hb.build_program(SRC, "SUPPORT_HOST_MAIN", "support_host_asan", tmpdir)
 
 
 def load(out):
@@ -51,10 +55,6 @@ def load(out):
     L.support_polytopes_per_group.restype = C.c_int
     L.support_polytopes_per_group.argtypes = [C.c_int, C.c_int]
     return L
-
-
-def _p(a):
-    return None if a is None else C.c_void_p(a.ctypes.data)
 
 
 def run(L, A, b, C_, xc, m=None, points=True):
@@ -69,7 +69,8 @@ def run(L, A, b, C_, xc, m=None, points=True):
     h = np.empty((B, K))
     x = np.empty((B, K, d)) if points else None
     st = np.empty((B, K), np.int32)
-    rc = L.support_host(B, m_max, d, _p(A), _p(b), _p(m), K, _p(C_), 1 if C_.ndim == 2 else 0, _p(xc), _p(h), _p(x), _p(st))
+    rc = L.support_host(B, m_max, d, hb.ptr(A), hb.ptr(b), hb.ptr(m), K, hb.ptr(C_), 1 if C_.ndim == 2 else 0, hb.ptr(xc), hb.ptr(h),
+                        hb.ptr(x), hb.ptr(st))
     assert rc == 0
     return h, x, st
 

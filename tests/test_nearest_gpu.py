@@ -101,6 +101,17 @@ def test_second_grid_index(L, pa):
             same(pa.nearest_batch(A, b, X, m=m, faces=True, resolve=False), nh.run(L, A, b, X, m))   # (host pointers)
 
 
+def test_dev_entry_without_row_counts(L, pa):
+    """m = None on CUDA tensors: the device-pointer entry with a NULL m (every polytope has m_max rows), which the other
+    tests reach through host pointers only; (17, 2): 32 row slots, B = 5 and K = 3 a tail tile."""
+    import torch
+    dev = torch.device("cuda", 0)
+    A, b, _ = polytopes(17, 2, 5, 171)
+    X = 2.5 * np.random.default_rng(172).standard_normal((5, 3, 2))
+    out = pa.nearest_batch(*(torch.as_tensor(v).to(dev) for v in (A, b, X)), faces=True, resolve=False)
+    same(out, nh.run(L, A, b, X, None))
+
+
 @pytest.mark.parametrize("fam", nh.FAMILIES)
 def test_soak_families_equal_the_host_build(L, pa, fam):
     """Every soak family at SOAK_SHAPES, B = 30, K = 7 normal points + one NaN, shared and per polytope."""

@@ -213,6 +213,15 @@ def test_tile_table(L):
     assert L.support_polytopes_per_group(4, 65) == 0
 
 
+def test_sanitized_program_runs(tmp_path):
+    """The stand-alone program of the host build (-DSUPPORT_HOST_MAIN: the polytopes it makes itself, every d and row-slot
+    count, interior / boundary / NaN centres) under -fsanitize=address,undefined: exit 0, every status consistent."""
+    import subprocess
+    r = subprocess.run([sh.build_program(tmp_path)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True)
+    assert r.returncode == 0, r.stdout[-2000:]
+    assert "inconsistent: 0" in r.stdout
+
+
 def test_argument_errors_need_no_library(monkeypatch):
     """Wrong rank of C, d mismatch, B mismatch, K = 0, a bad xc: ValueError before anything of the library is touched."""
     from polytope_amd import _lib, batch
