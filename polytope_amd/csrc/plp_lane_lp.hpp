@@ -20,7 +20,8 @@
 // The same source compiles for the host (g++, tests/cabi/lane_lp_host.cpp: the engine against the oracle's simplex on
 // millions of LPs without a GPU) and for the device.  -DPLP_LANE_PLAIN_WALK: walk3 as one general loop behind its first
 // pass (A/B builds; tests/cabi/lane_walk_ab_host.cpp holds the default form, with its second and third pass peeled, to the
-// same bits).
+// same bits).  -DPLP_LANE_NO_VERTEX_ROUND: every pass of the general loop forms its direction, no vote for the vertex
+// round (A/B builds; tests/cabi/lane_state_ab_host.cpp holds the default form to the same bits).
 #pragma once
 #include <math.h>
 
@@ -108,7 +109,9 @@ enum : int {
     WE_RETRY_PAIR, WE_RETRY_TRIPLE, WE_RETRY_DEGEN,      // handed back: parallel pair, dependent triple, degenerate run / cap
     WE_DROP2, WE_DROP3,                                  // a row dropped at an edge / at a vertex
     WE_PASS_FACET, WE_PASS_EDGE, WE_PASS_GENERAL,        // passes by kind (the first one is not counted)
-    WE_COUNT
+    WE_COUNT,                                            // (the tallies tests/cabi/lane_walk_ab_host.cpp copies out)
+    WE_PASS_VERTEX = WE_COUNT,                           // passes of the general loop taken as a vertex round (walk3)
+    WE_COUNT_ALL                                         // a tally array must hold WE_COUNT_ALL entries, whatever its host copies out
 };
 #ifndef PLP_LANE_TALLY
 #define PLP_LANE_TALLY(e) ((void)0)
@@ -205,6 +208,52 @@ PLP_LANE_FN void edge_pass3(Lp3& S, const double c0, const double c1, const doub
 }
 #endif   // !PLP_LANE_PLAIN_WALK
 
+// A lane that runs with THREE active rows n0, n1, n2 and nowhere to go inside them: the multipliers of
+// c + sum lambda_j n_j = 0 from the three cross products.  All >= -tol: ST_OPT.  Otherwise the row with the most negative
+// (weighted) multiplier goes and d is the edge of the other two, oriented off it; dependent rows are handed back.
+PLP_LANE_FN void vertex3(Lp3& S, const double c0, const double c1, const double c2, const double cn1, const double n00,
+                         const double n01, const double n02, const double n10, const double n11, const double n12,
+                         const double n20, const double n21, const double n22, double& d0, double& d1, double& d2) {
+    double u00, u01, u02, u10, u11, u12, u20, u21, u22;
+    cross3(n10, n11, n12, n20, n21, n22, u00, u01, u02);   // u0 = n1 x n2
+    cross3(n20, n21, n22, n00, n01, n02, u10, u11, u12);   // u1 = n2 x n0
+    cross3(n00, n01, n02, n10, n11, n12, u20, u21, u22);   // u2 = n0 x n1
+    const double det = dot3(n00, n01, n02, u00, u01, u02);
+    const double g00 = dot3(n00, n01, n02, n00, n01, n02), g11 = dot3(n10, n11, n12, n10, n11, n12);
+    const double g22 = dot3(n20, n21, n22, n20, n21, n22);
+    if (!(det * det > 1e-18 * (g00 * g11 * g22))) {
+        S.status = ST_RETRY;   // three active planes that (nearly) share a line
+        PLP_LANE_TALLY(WE_RETRY_TRIPLE);
+    } else {
+        // lambda_j = -(c.u_j) / det ; compare sign-corrected numerators lambda_j |det| = -(c.u_j) sgn(det)
+        const double sg = det > 0.0 ? 1.0 : -1.0;
+        const double l0 = -sg * dot3(c0, c1, c2, u00, u01, u02);
+        const double l1 = -sg * dot3(c0, c1, c2, u10, u11, u12);
+        const double l2 = -sg * dot3(c0, c1, c2, u20, u21, u22);
+        // lambda_j |n_j| / |c|  =  l_j |n_j| / (|det| |c|), with w_j = (1 + n_j.n_j) / 2 >= |n_j| in its place
+        const double a0 = l0 * (0.5 * (1.0 + g00)), a1 = l1 * (0.5 * (1.0 + g11)), a2 = l2 * (0.5 * (1.0 + g22));
+        const double tol = LANE_TOL_D * fabs(det) * cn1;
+        if (a0 >= -tol && a1 >= -tol && a2 >= -tol) { S.status = ST_OPT; PLP_LANE_TALLY(WE_OPT3); }
+        else {
+            PLP_LANE_TALLY(WE_DROP3);
+            // most negative goes; the edge of the other two, oriented off the dropped row: -sgn(det) u_j
+            int j = 0;
+            double am = a0;
+            if (a1 < am) { am = a1; j = 1; }
+            if (a2 < am) { am = a2; j = 2; }
+            double gg;   // n_a.n_a n_b.n_b of the two rows that stay: u_j is THEIR cross product
+            if (j == 0) { d0 = -sg * u00; d1 = -sg * u01; d2 = -sg * u02; S.w0 = S.w1; S.w1 = S.w2; gg = g11 * g22; }
+            else if (j == 1) { d0 = -sg * u10; d1 = -sg * u11; d2 = -sg * u12; S.w1 = S.w2; gg = g22 * g00; }
+            else { d0 = -sg * u20; d1 = -sg * u21; d2 = -sg * u22; gg = g00 * g11; }
+            S.nact = 2;
+            if (!(dot3(d0, d1, d2, d0, d1, d2) > LANE_PAIR_SIN2 * gg)) {
+                S.status = ST_RETRY;
+                PLP_LANE_TALLY(WE_RETRY_PAIR);
+            }
+        }
+    }
+}
+
 // One LP, to the end.  ROWS(i, a0, a1, a2): row i of the polytope (zeroed rows allowed: they never block).
 // RATIO(d0, d1, d2, x0, x1, x2, tolp, bs, bd, bi): the ratio test -- over the rows with a.d > tolp the one with the smallest
 // (beta_i - a_i.x)+ / a_i.d, the FIRST such row on ties; bs / bd its slack and a.d, bi its index (-1: none).  The caller
@@ -262,7 +311,16 @@ PLP_LANE_FN void walk3(Lp3& S, const double c0, const double c1, const double c2
 #endif
     while (ANY(S.status < 0)) {
         const bool run = S.status < 0;
-        if (run) PLP_LANE_TALLY(WE_PASS_GENERAL);
+        // THE VERTEX ROUND: a lane on three active rows has nowhere to go inside them (its direction is 0, it is stalled
+        // whenever it runs).  Where a vote says that every lane still running stands so -- from the second general pass of
+        // a walk on, nearly always -- the wavefront goes past the directions and the stall test, straight to the multipliers;
+        // a lane does there what this pass does for it anyway.
+#ifndef PLP_LANE_NO_VERTEX_ROUND
+        const bool vround = !ANY(run && S.nact < 3);
+#else
+        constexpr bool vround = false;
+#endif
+        if (run) PLP_LANE_TALLY(vround ? WE_PASS_VERTEX : WE_PASS_GENERAL);
         // ---------------- direction: -c projected onto the planes of the active rows (scaled by positive factors)
         double d0 = -c0, d1 = -c1, d2 = -c2;
         double n00 = 0, n01 = 0, n02 = 0, n10 = 0, n11 = 0, n12 = 0, n20 = 0, n21 = 0, n22 = 0;
@@ -280,7 +338,10 @@ PLP_LANE_FN void walk3(Lp3& S, const double c0, const double c1, const double c2
 #endif
         bool stalled = false;      // no descent left inside the active planes: look at the multipliers
         double dscale = cn1;       // |d|_1 of a direction that is "as long as c" (what TOL_D is relative to)
-        if (S.nact == 1) {
+        if (vround) {
+            d0 = d1 = d2 = 0.0;
+            stalled = true;
+        } else if (S.nact == 1) {
             const double nn = dot3(n00, n01, n02, n00, n01, n02);
             double sc;
             proj1(c0, c1, c2, cn1, n00, n01, n02, nn, d0, d1, d2, sc, ANY);
@@ -302,7 +363,7 @@ PLP_LANE_FN void walk3(Lp3& S, const double c0, const double c1, const double c2
         } else if (S.nact == 3) {
             d0 = d1 = d2 = 0.0;
         }
-        {
+        if (!vround) {
             const double dn1 = fabs(d0) + fabs(d1) + fabs(d2);
             stalled = !(dn1 > LANE_TOL_D * dscale);
         }
@@ -338,44 +399,7 @@ PLP_LANE_FN void walk3(Lp3& S, const double c0, const double c1, const double c2
                         proj1(c0, c1, c2, cn1, n00, n01, n02, dot3(n00, n01, n02, n00, n01, n02), d0, d1, d2, sc, [](bool q) { return q; });
                     }
                 } else {
-                    double u00, u01, u02, u10, u11, u12, u20, u21, u22;
-                    cross3(n10, n11, n12, n20, n21, n22, u00, u01, u02);   // u0 = n1 x n2
-                    cross3(n20, n21, n22, n00, n01, n02, u10, u11, u12);   // u1 = n2 x n0
-                    cross3(n00, n01, n02, n10, n11, n12, u20, u21, u22);   // u2 = n0 x n1
-                    const double det = dot3(n00, n01, n02, u00, u01, u02);
-                    const double g00 = dot3(n00, n01, n02, n00, n01, n02), g11 = dot3(n10, n11, n12, n10, n11, n12);
-                    const double g22 = dot3(n20, n21, n22, n20, n21, n22);
-                    if (!(det * det > 1e-18 * (g00 * g11 * g22))) {
-                        S.status = ST_RETRY;   // three active planes that (nearly) share a line
-                        PLP_LANE_TALLY(WE_RETRY_TRIPLE);
-                    } else {
-                        // lambda_j = -(c.u_j) / det ; compare sign-corrected numerators lambda_j |det| = -(c.u_j) sgn(det)
-                        const double sg = det > 0.0 ? 1.0 : -1.0;
-                        const double l0 = -sg * dot3(c0, c1, c2, u00, u01, u02);
-                        const double l1 = -sg * dot3(c0, c1, c2, u10, u11, u12);
-                        const double l2 = -sg * dot3(c0, c1, c2, u20, u21, u22);
-                        // lambda_j |n_j| / |c|  =  l_j |n_j| / (|det| |c|), with w_j = (1 + n_j.n_j) / 2 >= |n_j| in its place
-                        const double a0 = l0 * (0.5 * (1.0 + g00)), a1 = l1 * (0.5 * (1.0 + g11)), a2 = l2 * (0.5 * (1.0 + g22));
-                        const double tol = LANE_TOL_D * fabs(det) * cn1;
-                        if (a0 >= -tol && a1 >= -tol && a2 >= -tol) { S.status = ST_OPT; PLP_LANE_TALLY(WE_OPT3); }
-                        else {
-                            PLP_LANE_TALLY(WE_DROP3);
-                            // most negative goes; the edge of the other two, oriented off the dropped row: -sgn(det) u_j
-                            int j = 0;
-                            double am = a0;
-                            if (a1 < am) { am = a1; j = 1; }
-                            if (a2 < am) { am = a2; j = 2; }
-                            double gg;   // n_a.n_a n_b.n_b of the two rows that stay: u_j is THEIR cross product
-                            if (j == 0) { d0 = -sg * u00; d1 = -sg * u01; d2 = -sg * u02; S.w0 = S.w1; S.w1 = S.w2; gg = g11 * g22; }
-                            else if (j == 1) { d0 = -sg * u10; d1 = -sg * u11; d2 = -sg * u12; S.w1 = S.w2; gg = g22 * g00; }
-                            else { d0 = -sg * u20; d1 = -sg * u21; d2 = -sg * u22; gg = g00 * g11; }
-                            S.nact = 2;
-                            if (!(dot3(d0, d1, d2, d0, d1, d2) > LANE_PAIR_SIN2 * gg)) {
-                                S.status = ST_RETRY;
-                                PLP_LANE_TALLY(WE_RETRY_PAIR);
-                            }
-                        }
-                    }
+                    vertex3(S, c0, c1, c2, cn1, n00, n01, n02, n10, n11, n12, n20, n21, n22, d0, d1, d2);
                 }
             }
         }
