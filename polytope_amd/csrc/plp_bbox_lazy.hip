@@ -31,45 +31,18 @@ __global__ __launch_bounds__(64, 3) void bbox_lazy_kernel(long long B, int m_max
     if (p >= B) return;
     const int m = mrows ? mrows[p] : m_max;
     const bool has = lane < m;
-    // ---- F1 (set-up as cheby_w_kernel); my row also goes to LDS for the lazy LPs
-    typename wide::RowVec<NC>::type Tv = (typename wide::RowVec<NC>::type)(0.0);
-    double T16 = 0.0;
-    double nrm2 = 0.0;
-    bool finite = true;
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-        const double v = has ? A[(p * m_max + lane) * D + k] : 0.0;
-        ROW_SET(k, v);
-        sA[lane * D + k] = v;
-        nrm2 = nrm2 + v * v;
-        finite = finite & isfinite(v);
-    }
+    // ---- F1 (plp_wide.hpp); my row also goes to LDS for the box LPs
     const double bi = has ? b[p * m_max + lane] : 0.0;
-    finite = finite & isfinite(bi);
-    const double nrm = sqrt(nrm2);
-    const bool zero = !(nrm > 0.0);
-    bool rowact = has & !zero;
-    ROW_SET(D, rowact ? nrm : 0.0);
-    double beta = rowact ? bi : 0.0;
-    int rowvar = NC + lane, rowneg = 0;
-    if (lane <= NC) {
-        sh.cost[lane] = lane == D ? -1.0 : 0.0;
-        sh.cv[lane] = (lane + 1) << 1;
-    }
-    const bool infeasible0 = __ballot(has & zero & (bi < -TOL_FEAS)) != 0;
-    const bool bad = (__ballot(!finite) != 0) | (m > 64);
-    __syncthreads();
-    int st, iters = 0;
-    if (bad) st = ST_NUM;
-    else if (infeasible0) st = ST_INFEAS;
-    else st = wide::wide_run<NC>(lane, m, Tv, T16, beta, rowvar, rowneg, rowact, sh, NC, true, bi / nrm, iters);
-    const double mine = rowneg ? -beta : beta;
-    double x[NC];
+    typename wide::RowVec<NC>::type Tv;
+    double T16;
+    wide::ChebyRow c;
+    wide::cheby_setup<D>(Tv, T16, c, lane, has, [&](int k) { return A[(p * m_max + lane) * D + k]; }, [&]() { return bi; }, sh);
 #pragma unroll
-    for (int j = 0; j < NC; ++j) {
-        const uint64_t ob = __ballot(rowvar == j);
-        x[j] = ob ? wide::uniform_lane(mine, __ffsll((long long)ob) - 1) : 0.0;
-    }
+    for (int k = 0; k < D; ++k) sA[lane * D + k] = ROW_GET(k);
+    __syncthreads();
+    const int st = wide::cheby_run<D>(Tv, T16, c, lane, m, sh, m > 64);
+    double x[NC];
+    wide::cheby_point<D>(c, x);
     const bool ok = (st == ST_OPT) & (x[D] >= BBOX_LAZY_MIN_R);
     bool handed = !ok;
     // ---- my slack at the centre (bbox_r_kernel: s by an fma chain, beta = max(b - s, 0))
@@ -131,47 +104,23 @@ __global__ __launch_bounds__(64 * NW) void bbox_wsplit_kernel(long long B, int m
     const bool has = lane < m;
     double bi = 0.0;
     if (w == 0) {
-        // ---- F1 (set-up as bbox_lazy_kernel); my row also goes to LDS for the box LPs
+        // ---- F1 (plp_wide.hpp); my row also goes to LDS for the box LPs
         wide::WideShared<NC>& sh = shw[0];
-        typename wide::RowVec<NC>::type Tv = (typename wide::RowVec<NC>::type)(0.0);
-        double T16 = 0.0;
-        double nrm2 = 0.0;
-        bool finite = true;
-#pragma unroll
-        for (int k = 0; k < D; ++k) {
-            const double v = has ? A[(p * m_max + lane) * D + k] : 0.0;
-            ROW_SET(k, v);
-            sA[lane * D + k] = v;
-            nrm2 = nrm2 + v * v;
-            finite = finite & isfinite(v);
-        }
         bi = has ? b[p * m_max + lane] : 0.0;
-        finite = finite & isfinite(bi);
-        const double nrm = sqrt(nrm2);
-        const bool zero = !(nrm > 0.0);
-        bool rowact = has & !zero;
-        ROW_SET(D, rowact ? nrm : 0.0);
-        double beta = rowact ? bi : 0.0;
-        int rowvar = NC + lane, rowneg = 0;
-        if (lane <= NC) {
-            sh.cost[lane] = lane == D ? -1.0 : 0.0;
-            sh.cv[lane] = (lane + 1) << 1;
-        }
-        const bool infeasible0 = __ballot(has & zero & (bi < -TOL_FEAS)) != 0;
-        const bool bad = (__ballot(!finite) != 0) | (m > 64);
-        wide::wave_sync();
-        int st, iters = 0;
-        if (bad) st = ST_NUM;
-        else if (infeasible0) st = ST_INFEAS;
-        else st = wide::wide_run<NC>(lane, m, Tv, T16, beta, rowvar, rowneg, rowact, sh, NC, true, bi / nrm, iters);
-        const double mine = rowneg ? -beta : beta;
-        double xr = 0.0;
+        typename wide::RowVec<NC>::type Tv;
+        double T16;
+        wide::ChebyRow c;
+        wide::cheby_setup<D>(Tv, T16, c, lane, has, [&](int k) { return A[(p * m_max + lane) * D + k]; }, [&]() { return bi; }, sh);
 #pragma unroll
-        for (int j = 0; j < NC; ++j) {
-            const uint64_t ob = __ballot(rowvar == j);
-            const double xj = ob ? wide::uniform_lane(mine, __ffsll((long long)ob) - 1) : 0.0;
-            if (lane == 0) sx[j] = xj;
-            if (j == D) xr = xj;
+        for (int k = 0; k < D; ++k) sA[lane * D + k] = ROW_GET(k);
+        wide::wave_sync();
+        const int st = wide::cheby_run<D>(Tv, T16, c, lane, m, sh, m > 64);
+        double xf[NC];
+        wide::cheby_point<D>(c, xf);
+        const double xr = xf[D];
+        if (lane == 0) {
+#pragma unroll
+            for (int j = 0; j < NC; ++j) sx[j] = xf[j];
         }
         if (lane == 0) {
             sflag[0] = ((st == ST_OPT) & (xr >= BBOX_LAZY_MIN_R)) ? 1u : 0u;

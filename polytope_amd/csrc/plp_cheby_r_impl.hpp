@@ -27,66 +27,7 @@ namespace {
 template <int D>
 struct RowsPerLane { static constexpr int value = lp_rows_per_lane(D); };
 
-// Solve the Chebyshev LP of the rows handed out by `rowA(rr, kk)` / `rowb(rr)` (rr = row index < m).
-// Returns the LP status; x[0..D-1] = centre, x[D] = radius, replicated over the group (valid if status 0).
-template <int D, int GS, int R, bool FAST, class FA, class FB>
-__device__ __forceinline__ int cheby_r_lp(const Grp& g, bool valid, int m, int row0, FA rowA, FB rowb, double* x) {
-    SimplexR<D + 1, R, !FAST, true> S;
-    S.reset(D + 1, m, row0);
-    double qi[R];
-    unsigned actb = 0u;
-    bool inf0 = false, finite = true;
-#pragma unroll
-    for (int k = 0; k < R; ++k) {
-        const bool h = valid & (row0 + k < m) & (m <= GS * R);
-        double nrm2 = 0.0;
-#pragma unroll
-        for (int kk = 0; kk < D; ++kk) {
-            const double v = h ? rowA(row0 + k, kk) : 0.0;
-            S.T[k][kk] = v;
-            nrm2 = nrm2 + v * v;
-            finite = finite & isfinite(v);
-        }
-        const double bk = h ? rowb(row0 + k) : 0.0;
-        finite = finite & isfinite(bk);
-        const double nrm = sqrt(nrm2);
-        const bool zero = !(nrm > 0.0);
-        const bool on = h & !zero;
-        S.T[k][D] = on ? nrm : 0.0;
-        S.beta[k] = on ? bk : 0.0;
-        qi[k] = bk / nrm;
-        actb |= on ? (1u << k) : 0u;
-        inf0 = inf0 | (h & zero & (bk < -TOL_FEAS));
-    }
-    S.ract = actb;
-    const bool infeasible0 = grp_ballot(inf0, g) != 0;
-    const bool bad = (grp_ballot(!finite, g) != 0) | (m > GS * R);
-    S.cost[D] = -1.0;
-    if constexpr (FAST) {
-        S.mode = M_P2;
-    } else {
-#pragma unroll
-        for (int k = 0; k < R; ++k) S.init_q[k] = qi[k];
-        S.init_elig = actb;
-        S.mode = M_INIT;
-        S.init_col = D;
-        S.mode_after_init = M_P2;
-    }
-    if (!valid | bad) { S.mode = M_DONE; S.status = ST_NUM; }
-    else if (infeasible0) { S.mode = M_DONE; S.status = ST_INFEAS; }
-    if constexpr (FAST) S.template run_fast<GS, true>(g, qi, actb);
-    else S.run(g);
-#pragma unroll
-    for (int j = 0; j <= D; ++j) {
-        bool found;
-        const double mine = S.x_of(j, found);
-        const uint64_t ob = grp_ballot(found, g);
-        const double v = bcast(mine, g.gbase + (ob ? __ffsll((long long)ob) - 1 : 0));
-        x[j] = ob ? v : 0.0;
-    }
-    return S.status;
-}
-
+// cheby_r_lp (plp_simplex_r.hpp) on the fast path, and once more on the general engine where that asks for it.
 template <int D, int GS, int R, class FA, class FB>
 __device__ __forceinline__ int cheby_r_solve(const Grp& g, bool valid, int m, int row0, FA rowA, FB rowb, double* x,
                                              int force_retry) {

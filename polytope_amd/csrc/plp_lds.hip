@@ -379,6 +379,61 @@ __global__ __launch_bounds__(64) void lp_lds_kernel(long long B, int m_max, int 
     }
 }
 
+namespace {
+
+// ---- The Chebyshev-ball LP (F1, polytope.py:1283-1288) of this engine, stated once: fills S / D from the rows
+// `rowA(i, k)` / `rowb(i)`, i < mloop (mloop >= m: the functors are asked for every one of them and answer 0 from row m on,
+// which lets a site keep the rows it reads; `rowinv(i, 1 / ||a_i||)` after each), and runs lds_step to the end.  The rows
+// normalised, the norm in column d, beta = b on live rows, cost[d] = -1, forced first pivot "r enters, row argmin
+// b_i / ||a_i|| leaves"; ST_NUM without a pivot for non-finite input, ST_INFEAS for a zero row with b < -TOL_FEAS.
+// The status is S.status, x is read with lds_x_of.  All 64 threads of the workgroup; D is free for this LP on entry.
+template <class FA, class FB, class FI>
+__device__ __forceinline__ void lds_cheby(LdsState& S, const LdsDict& D, const int m, const int mloop, const int d,
+                                          const int lane, FA rowA, FB rowb, FI rowinv) {
+    const int nc = d + 1, ld = D.ld;
+    S.m = m; S.n = nc; S.nc = nc;
+    S.cfree = (1u << nc) - 1u;
+    S.dead = 0u; S.ndeg = 0; S.iters = 0; S.maxit = 50 * (m + nc) + 100;
+    S.mode = M_INIT; S.status = -1; S.init_col = d; S.mode_after_init = M_P2;
+    S.negz = 0.0; S.negz2 = 0.0; S.carry = false;
+    bool finite = true, inf0 = false;
+    for (int i = lane; i < mloop; i += 64) {
+        const bool h = i < m;
+        double* Ti = D.T + (size_t)i * ld;
+        double nrm2 = 0.0;
+        for (int k = 0; k < d; ++k) {
+            const double v = rowA(i, k);
+            if (h) Ti[k] = v;
+            nrm2 = nrm2 + v * v;
+            finite = finite & isfinite(v);
+        }
+        const double bi = rowb(i);
+        finite = finite & isfinite(bi);
+        const double nrm = sqrt(nrm2);
+        rowinv(i, 1.0 / nrm);
+        if (h) {
+            const bool zero = !(nrm > 0.0);
+            Ti[d] = zero ? 0.0 : nrm;
+            D.beta[i] = zero ? 0.0 : bi;
+            D.qk[i] = bi / nrm;
+            D.rowvar[i] = nc + i;
+            D.rowfl[i] = zero ? 0 : 2;
+            inf0 = inf0 | (zero & (bi < -TOL_FEAS));
+        }
+    }
+    if (lane < nc) {
+        D.cost[lane] = lane == d ? -1.0 : 0.0;
+        D.cost2[lane] = 0.0;
+        D.cv[lane] = (lane + 1) << 1;
+    }
+    if (__ballot(!finite) != 0) { S.mode = M_DONE; S.status = ST_NUM; }
+    else if (__ballot(inf0) != 0) { S.mode = M_DONE; S.status = ST_INFEAS; }
+    __syncthreads();
+    while (S.mode != M_DONE) lds_step(S, D, lane);
+}
+
+}  // namespace
+
 __global__ __launch_bounds__(64) void cheby_lds_kernel(long long B, int m_max, int d, const double* __restrict__ A,
                                                        const double* __restrict__ b, const int* __restrict__ mrows,
                                                        double* __restrict__ r, double* __restrict__ xc,
@@ -393,44 +448,8 @@ __global__ __launch_bounds__(64) void cheby_lds_kernel(long long B, int m_max, i
         const LdsDict D = lds_carve(smem_raw, m_max, ld);
         __syncthreads();
         LdsState S;
-        S.m = m; S.n = nc; S.nc = nc;
-        S.cfree = (1u << nc) - 1u;
-        S.dead = 0u; S.ndeg = 0; S.iters = 0; S.maxit = 50 * (m + nc) + 100;
-        S.mode = M_INIT; S.status = -1; S.init_col = d; S.mode_after_init = M_P2;
-        S.negz = 0.0; S.negz2 = 0.0; S.carry = false;
-        bool finite = true, inf0 = false;
-        for (int i = lane; i < m; i += 64) {
-            const double* Ar = A + (p * m_max + i) * d;
-            double* Ti = D.T + (size_t)i * ld;
-            double nrm2 = 0.0;
-            for (int k = 0; k < d; ++k) {
-                const double v = Ar[k];
-                Ti[k] = v;
-                nrm2 = nrm2 + v * v;
-                finite = finite & isfinite(v);
-            }
-            const double bi = b[p * m_max + i];
-            finite = finite & isfinite(bi);
-            const double nrm = sqrt(nrm2);
-            const bool zero = !(nrm > 0.0);
-            Ti[d] = zero ? 0.0 : nrm;
-            D.beta[i] = zero ? 0.0 : bi;
-            D.qk[i] = bi / nrm;
-            D.rowvar[i] = nc + i;
-            D.rowfl[i] = zero ? 0 : 2;
-            inf0 = inf0 | (zero & (bi < -TOL_FEAS));
-        }
-        if (lane < nc) {
-            D.cost[lane] = lane == d ? -1.0 : 0.0;
-            D.cost2[lane] = 0.0;
-            D.cv[lane] = (lane + 1) << 1;
-        }
-        const bool bad = __ballot(!finite) != 0;
-        const bool infeasible0 = __ballot(inf0) != 0;
-        if (bad) { S.mode = M_DONE; S.status = ST_NUM; }
-        else if (infeasible0) { S.mode = M_DONE; S.status = ST_INFEAS; }
-        __syncthreads();
-        while (S.mode != M_DONE) lds_step(S, D, lane);
+        lds_cheby(S, D, m, m, d, lane, [&](int i, int k) { return A[(p * m_max + i) * d + k]; },
+                  [&](int i) { return b[p * m_max + i]; }, [](int, double) {});
         const bool ok = S.status == ST_OPT;
         for (int j = 0; j < nc; ++j) {
             const double xj = lds_x_of(D, m, j, lane);
@@ -459,43 +478,8 @@ __global__ __launch_bounds__(64) void cheby_gather_lds_kernel(long long nlp, int
         const LdsDict D = lds_carve(smem_raw, m_cap, ld);
         __syncthreads();
         LdsState S;
-        S.m = m; S.n = nc; S.nc = nc;
-        S.cfree = (1u << nc) - 1u;
-        S.dead = 0u; S.ndeg = 0; S.iters = 0; S.maxit = 50 * (m + nc) + 100;
-        S.mode = M_INIT; S.status = -1; S.init_col = d; S.mode_after_init = M_P2;
-        S.negz = 0.0; S.negz2 = 0.0; S.carry = false;
-        bool finite = true, inf0 = false;
-        for (int i = lane; i < m; i += 64) {
-            const long long src = rows[o + i];
-            const double* Ar = A + src * d;
-            double* Ti = D.T + (size_t)i * ld;
-            double nrm2 = 0.0;
-            for (int k = 0; k < d; ++k) {
-                const double v = Ar[k];
-                Ti[k] = v;
-                nrm2 = nrm2 + v * v;
-                finite = finite & isfinite(v);
-            }
-            const double bi = b[src];
-            finite = finite & isfinite(bi);
-            const double nrm = sqrt(nrm2);
-            const bool zero = !(nrm > 0.0);
-            Ti[d] = zero ? 0.0 : nrm;
-            D.beta[i] = zero ? 0.0 : bi;
-            D.qk[i] = bi / nrm;
-            D.rowvar[i] = nc + i;
-            D.rowfl[i] = zero ? 0 : 2;
-            inf0 = inf0 | (zero & (bi < -TOL_FEAS));
-        }
-        if (lane < nc) {
-            D.cost[lane] = lane == d ? -1.0 : 0.0;
-            D.cost2[lane] = 0.0;
-            D.cv[lane] = (lane + 1) << 1;
-        }
-        if (__ballot(!finite) != 0) { S.mode = M_DONE; S.status = ST_NUM; }
-        else if (__ballot(inf0) != 0) { S.mode = M_DONE; S.status = ST_INFEAS; }
-        __syncthreads();
-        while (S.mode != M_DONE) lds_step(S, D, lane);
+        lds_cheby(S, D, m, m, d, lane, [&](int i, int k) { return A[(long long)rows[o + i] * d + k]; },
+                  [&](int i) { return b[rows[o + i]]; }, [](int, double) {});
         const double rr = lds_x_of(D, m, d, lane);
         if (lane == 0) out[p] = S.status != ST_OPT ? __builtin_nan("") : (rr >= 0.0 ? rr : 0.0);
     }
@@ -587,50 +571,24 @@ __global__ __launch_bounds__(64) void reduce_lds_kernel(long long B, int m_max, 
         }
         const LdsDict D = lds_carve(smem_raw, m_max, ld);
         __syncthreads();
-        // ---------------------------------------------------------------- rows -> LDS; F1 (as cheby_lds_kernel)
+        // ---------------------------------------------------------------- rows -> LDS; F1 (lds_cheby)
         LdsState S;
-        S.m = m; S.n = nc1; S.nc = nc1;
-        S.cfree = (1u << nc1) - 1u;
-        S.dead = 0u; S.ndeg = 0; S.iters = 0; S.maxit = 50 * (m + nc1) + 100;
-        S.mode = M_INIT; S.status = -1; S.init_col = d; S.mode_after_init = M_P2;
-        S.negz = 0.0; S.negz2 = 0.0; S.carry = false;
-        bool finite = true, inf0 = false;
-        for (int i = lane; i < m_max; i += 64) {
-            const bool h = i < m;
-            double* Ti = D.T + (size_t)i * ld;
-            double nrm2 = 0.0;
-            for (int k = 0; k < d; ++k) {
-                const double v = h ? Ag[(p * m_max + i) * d + k] : 0.0;
+        lds_cheby(
+            S, D, m, m_max, d, lane,
+            [&](int i, int k) {
+                const double v = i < m ? Ag[(p * m_max + i) * d + k] : 0.0;
                 R.A[i * d + k] = v;
-                if (h) Ti[k] = v;
-                nrm2 = nrm2 + v * v;
-                finite = finite & isfinite(v);
-            }
-            const double bi = h ? bg[p * m_max + i] : 0.0;
-            finite = finite & isfinite(bi);
-            R.b[i] = bi;
-            const double nrm = sqrt(nrm2);
-            R.s[i] = 1.0 / nrm;
-            R.state[i] = h ? ROW_LIVE : ROW_DEAD;
-            if (h) {
-                const bool zero = !(nrm > 0.0);
-                Ti[d] = zero ? 0.0 : nrm;
-                D.beta[i] = zero ? 0.0 : bi;
-                D.qk[i] = bi / nrm;
-                D.rowvar[i] = nc1 + i;
-                D.rowfl[i] = zero ? 0 : 2;
-                inf0 = inf0 | (zero & (bi < -TOL_FEAS));
-            }
-        }
-        if (lane < nc1) {
-            D.cost[lane] = lane == d ? -1.0 : 0.0;
-            D.cost2[lane] = 0.0;
-            D.cv[lane] = (lane + 1) << 1;
-        }
-        if (__ballot(!finite) != 0) { S.mode = M_DONE; S.status = ST_NUM; }
-        else if (__ballot(inf0) != 0) { S.mode = M_DONE; S.status = ST_INFEAS; }
-        __syncthreads();
-        while (S.mode != M_DONE) lds_step(S, D, lane);
+                return v;
+            },
+            [&](int i) {
+                const double bi = i < m ? bg[p * m_max + i] : 0.0;
+                R.b[i] = bi;
+                return bi;
+            },
+            [&](int i, double inv) {
+                R.s[i] = inv;
+                R.state[i] = i < m ? ROW_LIVE : ROW_DEAD;
+            });
         double xcl = 0.0;  // lane j < d: xc[j]
         for (int j = 0; j < d; ++j) {
             const double xj = lds_x_of(D, m, j, lane);

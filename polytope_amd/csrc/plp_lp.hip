@@ -133,54 +133,25 @@ __global__ __launch_bounds__(BLOCK) void cheby_kernel(long long B, int m_max, in
         const int m = valid ? (mrows ? mrows[p] : m_max) : 0;
         const int i = g.gl;
         const bool has_row = valid && i < m;
-        Simplex<NC, false> S;
-        S.reset(NC, m, i);
-        bool finite = true;
-        double bi = 0.0, nrm2 = 0.0;
+        double a[D], bi = 0.0;
+#pragma unroll
+        for (int k = 0; k < D; ++k) a[k] = 0.0;
         if (has_row) {
             const double* Ar = A + (p * m_max + i) * D;
 #pragma unroll
-            for (int k = 0; k < D; ++k) {
-                S.T[k] = Ar[k];
-                nrm2 = nrm2 + S.T[k] * S.T[k];
-                finite = finite && isfinite(S.T[k]);
-            }
+            for (int k = 0; k < D; ++k) a[k] = Ar[k];
             bi = b[p * m_max + i];
-            finite = finite && isfinite(bi);
         }
-        const double nrm = sqrt(nrm2);
-        S.T[D] = nrm;
-        S.beta = bi;
-        const bool zero = !(nrm > 0.0);
-        S.rowact = has_row && !zero;
-        if (!S.rowact) { S.beta = 0.0; S.T[D] = 0.0; }
-        const bool infeasible0 = grp_ballot(has_row && zero && bi < -TOL_FEAS, g) != 0;
-        const bool bad = grp_ballot(!finite, g) != 0 || m > gs;
-        S.cost[D] = -1.0;
-        S.mode = M_INIT;
-        S.init_col = D;
-        S.init_q = bi / nrm;
-        S.init_elig = S.rowact;
-        S.mode_after_init = M_P2;
-        if (!valid || bad) { S.mode = M_DONE; S.status = ST_NUM; }
-        else if (infeasible0) { S.mode = M_DONE; S.status = ST_INFEAS; }
-
-        S.run(g);
-
-        const bool ok = S.status == ST_OPT;
-        const double mine = S.x_value();
-        const bool holds = S.holds_x();
+        double x[NC], inv_nrm;
+        const int st = cheby_lp<D>(g, valid, has_row, m, gs, a, bi, x, inv_nrm);
+        const bool ok = st == ST_OPT;
         const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+        if (valid && g.gl == 0) {
 #pragma unroll
-        for (int j = 0; j < NC; ++j) {
-            const uint64_t ob = grp_ballot(holds && S.rowvar == j, g);
-            const double v = bcast(mine, g.gbase + (ob ? __ffsll((long long)ob) - 1 : 0));
-            const double xj = ok ? (ob ? v : 0.0) : qnan;
-            if (valid && g.gl == 0) {
-                if (j < D) xc[p * D + j] = xj; else r[p] = xj;
-            }
+            for (int j = 0; j < D; ++j) xc[p * D + j] = ok ? x[j] : qnan;
+            r[p] = ok ? x[D] : qnan;
         }
-        if (valid && g.gl == 0) status[p] = S.status;
+        if (valid && g.gl == 0) status[p] = st;
     }
 }
 

@@ -181,16 +181,15 @@ __device__ __forceinline__ void server_slot(int slot, int n, const int* __restri
     }
 }
 
-// The same batch entry on the one-LP-per-wavefront engine (plp_wide.hpp: wave-uniform pivot column and row, the body of
-// cheby_gather_w_kernel): a list of any length up to 64 rows takes a wavefront of its own.  Measured on the launch path at
+// The same batch entry on the one-LP-per-wavefront engine (plp_wide.hpp: wave-uniform pivot column and row,
+// cheby_radius_rows on the gathered rows): a list of any length up to 64 rows takes a wavefront of its own.  Measured on the launch path at
 // d = 4 (PLP_RDIFF_WIDE_MIND=4): 9.7 ms of device time for the 751 batches of config 4 against 10.9 ms on the lane groups.
 template <int D>
 __device__ __forceinline__ void server_slot_w(int q, const int* __restrict__ rec, int cap, const double* __restrict__ A,
                                               const double* __restrict__ b, ulonglong2* __restrict__ out_host,
                                               unsigned long long word) {
     using namespace wide;
-    constexpr int NC = D + 1;
-    __shared__ WideShared<NC> sh;
+    __shared__ WideShared<D + 1> sh;
     const int lane = threadIdx.x;
     const int* r = rec + (size_t)q * (cap + 2);
     const int p = __hip_atomic_load(r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -198,42 +197,11 @@ __device__ __forceinline__ void server_slot_w(int q, const int* __restrict__ rec
     int myrow = __hip_atomic_load(r + 2 + (lane < cap ? lane : 0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     const bool has = lane < m;
     const long long row = has ? myrow : 0;
-    typename RowVec<NC>::type Tv = (typename RowVec<NC>::type)(0.0);
-    double T16 = 0.0;
-    double nrm2 = 0.0;
-    bool finite = true;
+    double a[D];
 #pragma unroll
-    for (int k = 0; k < D; ++k) {
-        const double v = has ? A[row * D + k] : 0.0;
-        ROW_SET(k, v);
-        nrm2 = nrm2 + v * v;
-        finite = finite & isfinite(v);
-    }
-    const double bi = has ? b[row] : 0.0;
-    finite = finite & isfinite(bi);
-    const double nrm = sqrt(nrm2);
-    const bool zero = !(nrm > 0.0);
-    bool rowact = has & !zero;
-    ROW_SET(D, rowact ? nrm : 0.0);
-    double beta = rowact ? bi : 0.0;
-    int rowvar = NC + lane, rowneg = 0;
-    wave_sync();   // (the last LP's reads of the block are done)
-    if (lane <= NC) {
-        sh.cost[lane] = lane == D ? -1.0 : 0.0;
-        sh.cv[lane] = (lane + 1) << 1;
-    }
-    const bool infeasible0 = __ballot(has & zero & (bi < -TOL_FEAS)) != 0;
-    const bool bad = (__ballot(!finite) != 0) | (m > 64);
-    wave_sync();
-    int st, iters = 0;
-    if (bad) st = ST_NUM;
-    else if (infeasible0) st = ST_INFEAS;
-    else st = wide_run<NC>(lane, m, Tv, T16, beta, rowvar, rowneg, rowact, sh, NC, true, bi / nrm, iters);
-    const double mine = rowneg ? -beta : beta;
-    const uint64_t ob = __ballot(rowvar == D);
-    const double rv = ob ? uniform_lane(mine, __ffsll((long long)ob) - 1) : 0.0;
+    for (int k = 0; k < D; ++k) a[k] = has ? A[row * D + k] : 0.0;
+    const double rad = cheby_radius_rows<D>(lane, m, has, a, has ? b[row] : 0.0, sh);
     if (lane == 0) {
-        const double rad = st != ST_OPT ? __builtin_nan("") : (rv >= 0.0 ? rv : 0.0);
         unsigned long long* dst = reinterpret_cast<unsigned long long*>(out_host + p);
         __hip_atomic_store(dst, (unsigned long long)__double_as_longlong(rad), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

@@ -76,54 +76,21 @@ __device__ __forceinline__ void reduce_general_tile(unsigned char* smem_raw, con
     const bool has_row = valid && i < m && m <= gs;
     // ---------------------------------------------------------------- my row
     double a[D];
-    bool finite = true;
-    double nrm2 = 0.0;
 #pragma unroll
-    for (int k = 0; k < D; ++k) {
-        a[k] = has_row ? myA[i * D + k] : 0.0;
-        nrm2 = nrm2 + a[k] * a[k];
-        finite = finite && isfinite(a[k]);
-    }
+    for (int k = 0; k < D; ++k) a[k] = has_row ? myA[i * D + k] : 0.0;
     const double bi = has_row ? myb[i] : 0.0;
-    finite = finite && isfinite(bi);
-    const double nrm = sqrt(nrm2);
-    const double an_i = 1.0 / nrm;
-    // ---------------------------------------------------------------- F1: Chebyshev ball
+    // ---------------------------------------------------------------- F1: Chebyshev ball (cheby_lp, plp_simplex.hpp)
     double xc[D];
-    double rr = 0.0;
+    double rr = 0.0, an_i;
     bool ball, fulldim, f1open = false;
     {
-        Simplex<D + 1, false, true> S;
-        S.reset(D + 1, m, i);
+        double x1[D + 1];
+        const int st1 = cheby_lp<D>(g, valid, has_row, m, gs, a, bi, x1, an_i);
+        const bool ok = st1 == ST_OPT;
+        f1open = valid && !ok && st1 != ST_INFEAS;   // (RF_F1OPEN, plp_common.hpp)
 #pragma unroll
-        for (int k = 0; k < D; ++k) S.T[k] = a[k];
-        const bool zero = !(nrm > 0.0);
-        S.T[D] = nrm;
-        S.beta = bi;
-        S.rowact = has_row && !zero;
-        if (!S.rowact) { S.beta = 0.0; S.T[D] = 0.0; }
-        const bool infeasible0 = grp_ballot(has_row && zero && bi < -TOL_FEAS, g) != 0;
-        const bool bad = grp_ballot(!finite, g) != 0 || m > gs;
-        S.cost[D] = -1.0;
-        S.mode = M_INIT;
-        S.init_col = D;
-        S.init_q = bi / nrm;
-        S.init_elig = S.rowact;
-        S.mode_after_init = M_P2;
-        if (!valid || bad) { S.mode = M_DONE; S.status = ST_NUM; }
-        else if (infeasible0) { S.mode = M_DONE; S.status = ST_INFEAS; }
-        S.run(g);
-        const bool ok = S.status == ST_OPT;
-        f1open = valid && !ok && S.status != ST_INFEAS;   // (RF_F1OPEN, plp_common.hpp)
-        const double mine = S.x_value();
-        const bool holds = S.holds_x();
-#pragma unroll
-        for (int j = 0; j <= D; ++j) {
-            const uint64_t ob = grp_ballot(holds && S.rowvar == j, g);
-            const double v = bcast(mine, g.gbase + (ob ? __ffsll((long long)ob) - 1 : 0));
-            const double xj = ob ? v : 0.0;
-            if (j < D) xc[j < D ? j : 0] = xj; else rr = xj;
-        }
+        for (int j = 0; j < D; ++j) xc[j] = x1[j];
+        rr = x1[D];
         ball = ok && rr >= 0.0;        // cheby_ball: status 0 and r >= 0 (:1289-1293)
         {   // a centre that violates a row (centre_off, plp_common.hpp) is no centre: RF_F1OPEN
             double sk = 0.0;

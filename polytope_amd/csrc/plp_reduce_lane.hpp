@@ -154,7 +154,11 @@ __device__ __forceinline__ void reduce_lane_tile(
     uint64_t live = 0ull;
     unsigned has = 0u;
     bool retry = force_retry != 0;
-    // ---------------------------------------------------------------- F1: Chebyshev ball (as reduce_r_tile<D,4,4>)
+    // ---------------------------------------------------------------- F1: Chebyshev ball
+    // cheby_r_lp (plp_simplex_r.hpp) WRITTEN OUT, on the interleaved tile: the one site of the engine that does not call it.
+    // Called from here it costs this kernel registers it does not have (d = 3: 2 instead of 1 spilled VGPRs in
+    // reduce_lane_kernel, 3 instead of 2 in reduce_lane_mix_kernel; DESIGN.md, "Chebyshev LP: one statement per engine").
+    // A change to the F1 rule there is made here as well.
     {
         SimplexR<D + 1, R, false, true> S;
         double qi[R];

@@ -302,112 +302,49 @@ __device__ __forceinline__ void reduce_r_tile(
         // ---------------------------------------------------------------- F1: Chebyshev ball
         if constexpr (LAZY) {
             // one polytope per wavefront: F1 on the one-LP-per-wavefront engine (plp_wide.hpp: the entering column is
-            // wave-uniform, the row a register vector); set-up and read-out as in the branch below
+            // wave-uniform, the row a register vector)
             constexpr int NC = D + 1;
             wide::WideShared<NC>& sh = *reinterpret_cast<wide::WideShared<NC>*>(lzrho);
             static_assert(sizeof(wide::WideShared<NC>) <= lazy::lds_bytes<D>(), "F1's LDS block");
             const int lane = g.lane;
             const bool h = valid & (lane < m) & (m <= rows);
             has = h ? 1u : 0u;
-            typename wide::RowVec<NC>::type Tv = (typename wide::RowVec<NC>::type)(0.0);
-            double T16 = 0.0;
-            double nrm2 = 0.0;
-            bool finite = true;
-#pragma unroll
-            for (int kk = 0; kk < D; ++kk) {
-                const double v = h ? myA[row0 * D + kk] : 0.0;
-                ROW_SET(kk, v);
-                nrm2 = nrm2 + v * v;
-                finite = finite & isfinite(v);
-            }
-            const double bk = h ? myb[row0] : 0.0;
-            finite = finite & isfinite(bk);
-            const double nrm = sqrt(nrm2);
-            myan[row0] = 1.0 / nrm;
-            const bool zero = !(nrm > 0.0);
-            bool rowact = h & !zero;
-            ROW_SET(D, rowact ? nrm : 0.0);
-            double beta = rowact ? bk : 0.0;
-            int rowvar = NC + lane, rowneg = 0;
-            if (lane <= NC) {
-                sh.cost[lane] = lane == D ? -1.0 : 0.0;
-                sh.cv[lane] = (lane + 1) << 1;
-            }
-            const bool infeasible0 = __ballot(h & zero & (bk < -TOL_FEAS)) != 0;
-            const bool bad = (__ballot(!finite) != 0) | (m > rows);
+            typename wide::RowVec<NC>::type Tv;
+            double T16;
+            wide::ChebyRow c;
+            wide::cheby_setup<D>(Tv, T16, c, lane, h, [&](int kk) { return myA[row0 * D + kk]; }, [&]() { return myb[row0]; }, sh);
+            myan[row0] = c.inv_nrm;
             __syncthreads();
-            int st1, it1 = 0;
-            if (!valid | bad) st1 = ST_NUM;
-            else if (infeasible0) st1 = ST_INFEAS;
-            else st1 = wide::wide_run<NC>(lane, m, Tv, T16, beta, rowvar, rowneg, rowact, sh, NC, true, bk / nrm, it1);
-            const double mine = rowneg ? -beta : beta;
+            const int st1 = wide::cheby_run<D>(Tv, T16, c, lane, m, sh, !valid | (m > rows));
+            double x1[NC];
+            wide::cheby_point<D>(c, x1);
 #pragma unroll
-            for (int j = 0; j <= D; ++j) {
-                const uint64_t ob = __ballot(rowvar == j);
-                const double xj = ob ? wide::uniform_lane(mine, __ffsll((long long)ob) - 1) : 0.0;
-                if (j < D) xc[j < D ? j : 0] = xj; else rr = xj;
-            }
+            for (int j = 0; j < D; ++j) xc[j] = x1[j];
+            rr = x1[D];
             ball = (st1 == ST_OPT) & (rr >= 0.0);  // cheby_ball: status 0 and r >= 0 (:1289-1293)
             fulldim = ball & (rr > abs_tol);
             f1open = valid & (st1 != ST_OPT) & (st1 != ST_INFEAS);   // (RF_F1OPEN, plp_common.hpp)
         } else
         {
-            SimplexR<D + 1, R, false, true> S;  // forced first pivot handed to run_fast
-            double qi[R];
-            S.reset(D + 1, m, row0);
-            unsigned actb = 0u;
-            bool inf0 = false, finite = true;
-#pragma unroll
-            for (int k = 0; k < R; ++k) {
-                const bool h = valid & (row0 + k < m) & (m <= rows);
-                has |= h ? (1u << k) : 0u;
-                double nrm2 = 0.0;
-#pragma unroll
-                for (int kk = 0; kk < D; ++kk) {
-                    const double v = h ? myA[(row0 + k) * D + kk] : 0.0;
-                    S.T[k][kk] = v;
-                    nrm2 = nrm2 + v * v;
-                    finite = finite & isfinite(v);
-                }
-                const double bk = h ? myb[row0 + k] : 0.0;
-                finite = finite & isfinite(bk);
-                const double nrm = sqrt(nrm2);
-                myan[row0 + k] = 1.0 / nrm;
-                const bool zero = !(nrm > 0.0);
-                const bool on = h & !zero;
-                S.T[k][D] = on ? nrm : 0.0;
-                S.beta[k] = on ? bk : 0.0;
-                qi[k] = bk / nrm;
-                actb |= on ? (1u << k) : 0u;
-                inf0 = inf0 | (h & zero & (bk < -TOL_FEAS));
-            }
-            S.ract = actb;
-            const bool infeasible0 = grp_ballot(inf0, g) != 0;
-            const bool bad = (grp_ballot(!finite, g) != 0) | (m > rows);
-            S.cost[D] = -1.0;
-            S.mode = M_P2;
-            if (!valid | bad) { S.mode = M_DONE; S.status = ST_NUM; }
-            else if (infeasible0) { S.mode = M_DONE; S.status = ST_INFEAS; }
-            S.template run_fast<GS, true>(g, qi, actb);
-            retry = retry | (valid & (S.status == ST_RETRY));
+            // cheby_r_lp (plp_simplex_r.hpp) on the rows in LDS; 1 / ||a|| of every row goes there too, for the dedupe
+            double x1[D + 1];
+            int it1 = 0;
+            const int st1 = cheby_r_lp<D, GS, R, true>(
+                g, valid, m, row0, [&](int r_, int kk) { return myA[r_ * D + kk]; }, [&](int r_) { return myb[r_]; }, x1,
+                [&](int r_, double inv) { myan[r_] = inv; }, has, &it1);
+            retry = retry | (valid & (st1 == ST_RETRY));
 #ifdef PLP_STAGE_STATS
             {
-                const int wm = stat_wave_max(valid ? S.iters : 0);
+                const int wm = stat_wave_max(valid ? it1 : 0);
                 if (threadIdx.x == 0) { PLP_STAT_ADD(0, 1); PLP_STAT_ADD(1, wm); }
-                if (valid & (g.gl == 0)) { PLP_STAT_ADD(2, S.iters); PLP_STAT_ADD(11, 1); }
+                if (valid & (g.gl == 0)) { PLP_STAT_ADD(2, it1); PLP_STAT_ADD(11, 1); }
             }
 #endif
-            const bool ok = S.status == ST_OPT;
-            f1open = valid & !ok & (S.status != ST_INFEAS);   // (RF_F1OPEN, plp_common.hpp)
+            const bool ok = st1 == ST_OPT;
+            f1open = valid & !ok & (st1 != ST_INFEAS);   // (RF_F1OPEN, plp_common.hpp)
 #pragma unroll
-            for (int j = 0; j <= D; ++j) {
-                bool found;
-                const double mine = S.x_of(j, found);
-                const uint64_t ob = grp_ballot(found, g);
-                const double v = bcast(mine, g.gbase + (ob ? __ffsll((long long)ob) - 1 : 0));
-                const double xj = ob ? v : 0.0;
-                if (j < D) xc[j < D ? j : 0] = xj; else rr = xj;
-            }
+            for (int j = 0; j < D; ++j) xc[j] = x1[j];
+            rr = x1[D];
             ball = ok & (rr >= 0.0);  // cheby_ball: status 0 and r >= 0 (:1289-1293)
             fulldim = ball & (rr > abs_tol);
         }
@@ -1224,50 +1161,21 @@ __global__ __launch_bounds__(64 * NW, PLP_REDUCE_WSPLIT_WAVES(D)) void reduce_ws
     // ---------------------------------------------------------------- F1: Chebyshev ball (wavefront 0) while the others dedupe
     constexpr int NC1 = D + 1;
     wide::WideShared<NC1>& sh1 = *reinterpret_cast<wide::WideShared<NC1>*>(shb);
-    typename wide::RowVec<NC1>::type Tv = (typename wide::RowVec<NC1>::type)(0.0);
-    double T16 = 0.0, beta1 = 0.0, q01 = 0.0;
-    int rowvar1 = NC1 + lane, rowneg1 = 0;
-    bool rowact1 = false, infeasible0 = false, bad1 = false;
+    typename wide::RowVec<NC1>::type Tv;
+    double T16;
+    wide::ChebyRow c1;
     if (w == 0) {
-        double nrm2 = 0.0;
-        bool finite = true;
-#pragma unroll
-        for (int kk = 0; kk < D; ++kk) {
-            const double v = has ? myA[lane * D + kk] : 0.0;
-            ROW_SET(kk, v);
-            nrm2 = nrm2 + v * v;
-            finite = finite & isfinite(v);
-        }
-        const double bk = has ? myb[lane] : 0.0;
-        finite = finite & isfinite(bk);
-        const double nrm = sqrt(nrm2);
-        myan[lane] = 1.0 / nrm;
-        const bool zero = !(nrm > 0.0);
-        rowact1 = has & !zero;
-        ROW_SET(D, rowact1 ? nrm : 0.0);
-        beta1 = rowact1 ? bk : 0.0;
-        q01 = bk / nrm;
-        if (lane <= NC1) {
-            sh1.cost[lane] = lane == D ? -1.0 : 0.0;
-            sh1.cv[lane] = (lane + 1) << 1;
-        }
-        infeasible0 = __ballot(has & zero & (bk < -TOL_FEAS)) != 0;
-        bad1 = (__ballot(!finite) != 0) | (m > rows);
+        wide::cheby_setup<D>(Tv, T16, c1, lane, has, [&](int kk) { return myA[lane * D + kk]; }, [&]() { return myb[lane]; }, sh1);
+        myan[lane] = c1.inv_nrm;
     }
     __syncthreads();  // 1/||a|| of every row
     if (w == 0) {
-        int st1, it1 = 0;
-        if (bad1) st1 = ST_NUM;
-        else if (infeasible0) st1 = ST_INFEAS;
-        else st1 = wide::wide_run<NC1>(lane, m, Tv, T16, beta1, rowvar1, rowneg1, rowact1, sh1, NC1, true, q01, it1);
-        const double mine = rowneg1 ? -beta1 : beta1;
-        double xc1[D], rr1 = 0.0;
+        int st1 = wide::cheby_run<D>(Tv, T16, c1, lane, m, sh1, m > rows);
+        double x1[NC1], xc1[D];
+        wide::cheby_point<D>(c1, x1);
 #pragma unroll
-        for (int j = 0; j <= D; ++j) {
-            const uint64_t ob = __ballot(rowvar1 == j);
-            const double xj = ob ? wide::uniform_lane(mine, __ffsll((long long)ob) - 1) : 0.0;
-            if (j < D) xc1[j < D ? j : 0] = xj; else rr1 = xj;
-        }
+        for (int j = 0; j < D; ++j) xc1[j] = x1[j];
+        const double rr1 = x1[D];
         bool ball1 = (st1 == ST_OPT) & (rr1 >= 0.0);  // cheby_ball: status 0 and r >= 0 (:1289-1293)
         bool full1 = ball1 & (rr1 > abs_tol);
         {   // a centre that violates a row (centre_off, plp_common.hpp) is no centre: RF_F1OPEN

@@ -324,4 +324,54 @@ struct Simplex {
     }
 };
 
+// ---- The Chebyshev-ball LP (F1, polytope.py:1283-1288) of this engine, stated once: cheby_kernel (plp_lp.hip) and the F1
+// stage of reduce_general_tile (plp_reduce_general.hpp) call it.  My row a x <= bi (lane g.gl of the group; zeros where
+// !has_row -- where the row comes from and what makes a lane hold one is the site's business): the rows normalised, the norm
+// in column D, beta = b on live rows, cost[D] = -1, forced first pivot "r enters, row argmin b_i / ||a_i|| leaves"; ST_NUM
+// without a pivot for an invalid group, non-finite input or m > gs, ST_INFEAS for a zero row with b < -TOL_FEAS.
+// Returns the LP status; x[0..D-1] = centre, x[D] = radius, replicated over the group (they mean something for status 0);
+// inv_nrm = 1 / ||a||.
+template <int D>
+__device__ __forceinline__ int cheby_lp(const Grp& g, const bool valid, const bool has_row, const int m, const int gs,
+                                        const double (&a)[D], const double bi, double (&x)[D + 1], double& inv_nrm) {
+    Simplex<D + 1, false, true> S;
+    S.reset(D + 1, m, g.gl);
+    bool finite = true;
+    double nrm2 = 0.0;
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+        S.T[k] = a[k];
+        nrm2 = nrm2 + a[k] * a[k];
+        finite = finite && isfinite(a[k]);
+    }
+    finite = finite && isfinite(bi);
+    const double nrm = sqrt(nrm2);
+    inv_nrm = 1.0 / nrm;
+    const bool zero = !(nrm > 0.0);
+    S.T[D] = nrm;
+    S.beta = bi;
+    S.rowact = has_row && !zero;
+    if (!S.rowact) { S.beta = 0.0; S.T[D] = 0.0; }
+    const bool infeasible0 = grp_ballot(has_row && zero && bi < -TOL_FEAS, g) != 0;
+    const bool bad = grp_ballot(!finite, g) != 0 || m > gs;
+    S.cost[D] = -1.0;
+    S.mode = M_INIT;
+    S.init_col = D;
+    S.init_q = bi / nrm;
+    S.init_elig = S.rowact;
+    S.mode_after_init = M_P2;
+    if (!valid || bad) { S.mode = M_DONE; S.status = ST_NUM; }
+    else if (infeasible0) { S.mode = M_DONE; S.status = ST_INFEAS; }
+    S.run(g);
+    const double mine = S.x_value();
+    const bool holds = S.holds_x();
+#pragma unroll
+    for (int j = 0; j <= D; ++j) {
+        const uint64_t ob = grp_ballot(holds && S.rowvar == j, g);
+        const double v = bcast(mine, g.gbase + (ob ? __ffsll((long long)ob) - 1 : 0));
+        x[j] = ob ? v : 0.0;
+    }
+    return S.status;
+}
+
 }  // namespace plp

@@ -680,4 +680,82 @@ struct SimplexR {
     }
 };
 
+// ---- The Chebyshev-ball LP (F1, polytope.py:1283-1288) of this engine, stated once: the stand-alone kernels
+// (plp_cheby_r_impl.hpp) and the F1 stage of the fused reduce tiles (plp_reduce_r_impl.hpp, plp_reduce_lane.hpp) call it.
+// The rows come from `rowA(rr, kk)` / `rowb(rr)` (rr = row index < m, asked for where the row exists only); after row rr
+// is set up `rowinv(rr, 1 / ||a_rr||)` is called for a site's side store; `has`: bit k = my row k exists.  The rows
+// normalised, the norm in column D, beta = b on live rows, cost[D] = -1, forced first pivot "r enters, row argmin b_i / ||a_i|| leaves";
+// ST_NUM without a pivot for an invalid group, non-finite input or m > GS * R, ST_INFEAS for a zero row with b < -TOL_FEAS.
+// Returns the LP status; x[0..D-1] = centre, x[D] = radius, replicated over the group (they mean something for status 0).
+// FAST: run_fast (may end ST_RETRY), else the general engine.  RUN = false: set-up and read-out only (debug builds).
+template <int D, int GS, int R, bool FAST, bool RUN = true, class FA, class FB, class FH>
+__device__ __forceinline__ int cheby_r_lp(const Grp& g, bool valid, int m, int row0, FA rowA, FB rowb, double* x, FH rowinv,
+                                          unsigned& has, int* iters = nullptr) {
+    SimplexR<D + 1, R, !FAST, true> S;
+    S.reset(D + 1, m, row0);
+    double qi[R];
+    unsigned actb = 0u;
+    bool inf0 = false, finite = true;
+    has = 0u;
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+        const bool h = valid & (row0 + k < m) & (m <= GS * R);
+        has |= h ? (1u << k) : 0u;
+        double nrm2 = 0.0;
+#pragma unroll
+        for (int kk = 0; kk < D; ++kk) {
+            const double v = h ? rowA(row0 + k, kk) : 0.0;
+            S.T[k][kk] = v;
+            nrm2 = nrm2 + v * v;
+            finite = finite & isfinite(v);
+        }
+        const double bk = h ? rowb(row0 + k) : 0.0;
+        finite = finite & isfinite(bk);
+        const double nrm = sqrt(nrm2);
+        rowinv(row0 + k, 1.0 / nrm);
+        const bool zero = !(nrm > 0.0);
+        const bool on = h & !zero;
+        S.T[k][D] = on ? nrm : 0.0;
+        S.beta[k] = on ? bk : 0.0;
+        qi[k] = bk / nrm;
+        actb |= on ? (1u << k) : 0u;
+        inf0 = inf0 | (h & zero & (bk < -TOL_FEAS));
+    }
+    S.ract = actb;
+    const bool infeasible0 = grp_ballot(inf0, g) != 0;
+    const bool bad = (grp_ballot(!finite, g) != 0) | (m > GS * R);
+    S.cost[D] = -1.0;
+    if constexpr (FAST) {
+        S.mode = M_P2;
+    } else {
+#pragma unroll
+        for (int k = 0; k < R; ++k) S.init_q[k] = qi[k];
+        S.init_elig = actb;
+        S.mode = M_INIT;
+        S.init_col = D;
+        S.mode_after_init = M_P2;
+    }
+    if (!valid | bad) { S.mode = M_DONE; S.status = ST_NUM; }
+    else if (infeasible0) { S.mode = M_DONE; S.status = ST_INFEAS; }
+    if constexpr (RUN) {
+        if constexpr (FAST) S.template run_fast<GS, true>(g, qi, actb);
+        else S.run(g);
+    }
+    if (iters) *iters = S.iters;
+#pragma unroll
+    for (int j = 0; j <= D; ++j) {
+        bool found;
+        const double mine = S.x_of(j, found);
+        const uint64_t ob = grp_ballot(found, g);
+        const double v = bcast(mine, g.gbase + (ob ? __ffsll((long long)ob) - 1 : 0));
+        x[j] = ob ? v : 0.0;
+    }
+    return S.status;
+}
+template <int D, int GS, int R, bool FAST, class FA, class FB>
+__device__ __forceinline__ int cheby_r_lp(const Grp& g, bool valid, int m, int row0, FA rowA, FB rowb, double* x) {
+    unsigned has;
+    return cheby_r_lp<D, GS, R, FAST>(g, valid, m, row0, rowA, rowb, x, [](int, double) {}, has);
+}
+
 }  // namespace plp

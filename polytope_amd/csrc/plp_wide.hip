@@ -39,43 +39,17 @@ __global__ __launch_bounds__(64) void cheby_w_kernel(long long B, int m_max, con
     if (p >= B) return;
     const int m = mrows ? mrows[p] : m_max;
     const bool has = lane < m;
-    typename RowVec<NC>::type Tv = (typename RowVec<NC>::type)(0.0);
-    double T16 = 0.0;
-    double nrm2 = 0.0;
-    bool finite = true;
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-        const double v = has ? A[(p * m_max + lane) * D + k] : 0.0;
-        ROW_SET(k, v);
-        nrm2 = nrm2 + v * v;
-        finite = finite & isfinite(v);
-    }
-    const double bi = has ? b[p * m_max + lane] : 0.0;
-    finite = finite & isfinite(bi);
-    const double nrm = sqrt(nrm2);
-    const bool zero = !(nrm > 0.0);
-    bool rowact = has & !zero;
-    ROW_SET(D, rowact ? nrm : 0.0);
-    double beta = rowact ? bi : 0.0;
-    int rowvar = NC + lane, rowneg = 0;
-    if (lane <= NC) {
-        sh.cost[lane] = lane == D ? -1.0 : 0.0;
-        sh.cv[lane] = (lane + 1) << 1;
-    }
-    const bool infeasible0 = __ballot(has & zero & (bi < -TOL_FEAS)) != 0;
-    const bool bad = (__ballot(!finite) != 0) | (m > 64);
+    typename RowVec<NC>::type Tv;
+    double T16;
+    ChebyRow c;
+    cheby_setup<D>(Tv, T16, c, lane, has, [&](int k) { return A[(p * m_max + lane) * D + k]; },
+                   [&]() { return b[p * m_max + lane]; }, sh);
     __syncthreads();
-    int st, iters = 0;
-    if (bad) st = ST_NUM;
-    else if (infeasible0) st = ST_INFEAS;
-    else st = wide_run<NC>(lane, m, Tv, T16, beta, rowvar, rowneg, rowact, sh, NC, true, bi / nrm, iters);
+    const int st = cheby_run<D>(Tv, T16, c, lane, m, sh, m > 64);
     const double qnan = __longlong_as_double(0x7ff8000000000000ll);
-    const double mine = rowneg ? -beta : beta;
 #pragma unroll
     for (int j = 0; j < NC; ++j) {
-        const uint64_t ob = __ballot(rowvar == j);
-        const double v = ob ? uniform_lane(mine, __ffsll((long long)ob) - 1) : 0.0;
-        const double xj = (st == ST_OPT) ? v : qnan;
+        const double xj = (st == ST_OPT) ? cheby_x(c, j) : qnan;
         if (lane == 0) {
             if (j < D) xc[p * D + j] = xj; else r_out[p] = xj;
         }
@@ -101,39 +75,13 @@ __global__ __launch_bounds__(64) void cheby_gather_w_kernel(long long nlp, const
     const int m = off[p + 1] - o;
     const bool has = lane < m;
     const long long row = has ? rows[o + lane] : 0;
-    typename RowVec<NC>::type Tv = (typename RowVec<NC>::type)(0.0);
-    double T16 = 0.0;
-    double nrm2 = 0.0;
-    bool finite = true;
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-        const double v = has ? A[row * D + k] : 0.0;
-        ROW_SET(k, v);
-        nrm2 = nrm2 + v * v;
-        finite = finite & isfinite(v);
-    }
-    const double bi = has ? b[row] : 0.0;
-    finite = finite & isfinite(bi);
-    const double nrm = sqrt(nrm2);
-    const bool zero = !(nrm > 0.0);
-    bool rowact = has & !zero;
-    ROW_SET(D, rowact ? nrm : 0.0);
-    double beta = rowact ? bi : 0.0;
-    int rowvar = NC + lane, rowneg = 0;
-    if (lane <= NC) {
-        sh.cost[lane] = lane == D ? -1.0 : 0.0;
-        sh.cv[lane] = (lane + 1) << 1;
-    }
-    const bool infeasible0 = __ballot(has & zero & (bi < -TOL_FEAS)) != 0;
-    const bool bad = (__ballot(!finite) != 0) | (m > 64);
+    typename RowVec<NC>::type Tv;
+    double T16;
+    ChebyRow c;
+    cheby_setup<D>(Tv, T16, c, lane, has, [&](int k) { return A[row * D + k]; }, [&]() { return b[row]; }, sh);
     __syncthreads();
-    int st, iters = 0;
-    if (bad) st = ST_NUM;
-    else if (infeasible0) st = ST_INFEAS;
-    else st = wide_run<NC>(lane, m, Tv, T16, beta, rowvar, rowneg, rowact, sh, NC, true, bi / nrm, iters);
-    const double mine = rowneg ? -beta : beta;
-    const uint64_t ob = __ballot(rowvar == D);
-    const double r = ob ? uniform_lane(mine, __ffsll((long long)ob) - 1) : 0.0;
+    const int st = cheby_run<D>(Tv, T16, c, lane, m, sh, m > 64);
+    const double r = cheby_radius<D>(c);
     if (lane == 0) out[p] = st != ST_OPT ? __builtin_nan("") : (r >= 0.0 ? r : 0.0);
 }
 
@@ -193,39 +141,14 @@ __device__ __forceinline__ void adjacent_w_body(int n, int m_max, const double* 
     const int m = mi + mj;
     const bool has = lane < m;
     const long long row = has ? ((lane < mi) ? i * m_max + lane : j * m_max + (lane - mi)) : 0;
-    typename RowVec<NC>::type Tv = (typename RowVec<NC>::type)(0.0);
-    double T16 = 0.0;
-    double nrm2 = 0.0;
-    bool finite = true;
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-        const double v = has ? A[row * D + k] : 0.0;
-        ROW_SET(k, v);
-        nrm2 = nrm2 + v * v;
-        finite = finite & isfinite(v);
-    }
-    const double bi = has ? b[row] + inflate : 0.0;  // b1 += abs_tol; b2 += abs_tol
-    finite = finite & isfinite(bi);
-    const double nrm = sqrt(nrm2);
-    const bool zero = !(nrm > 0.0);
-    bool rowact = has & !zero;
-    ROW_SET(D, rowact ? nrm : 0.0);
-    double beta = rowact ? bi : 0.0;
-    int rowvar = NC + lane, rowneg = 0;
-    if (lane <= NC) {
-        sh.cost[lane] = lane == D ? -1.0 : 0.0;
-        sh.cv[lane] = (lane + 1) << 1;
-    }
-    const bool infeasible0 = __ballot(has & zero & (bi < -TOL_FEAS)) != 0;
-    const bool bad = (__ballot(!finite) != 0) | (m > 64);
+    typename RowVec<NC>::type Tv;
+    double T16;
+    ChebyRow c;
+    cheby_setup<D>(Tv, T16, c, lane, has, [&](int k) { return A[row * D + k]; },
+                   [&]() { return b[row] + inflate; }, sh);  // b1 += abs_tol; b2 += abs_tol
     __syncthreads();
-    int st, iters = 0;
-    if (bad) st = ST_NUM;
-    else if (infeasible0) st = ST_INFEAS;
-    else st = wide_run<NC>(lane, m, Tv, T16, beta, rowvar, rowneg, rowact, sh, NC, true, bi / nrm, iters);
-    const double mine = rowneg ? -beta : beta;
-    const uint64_t ob = __ballot(rowvar == D);
-    const double r = ob ? uniform_lane(mine, __ffsll((long long)ob) - 1) : 0.0;
+    const int st = cheby_run<D>(Tv, T16, c, lane, m, sh, m > 64);
+    const double r = cheby_radius<D>(c);
     const bool yes = (st == ST_OPT) & (r > thresh);
     // (mark: "unbounded" / the iteration limit is not a verdict -- the careful pass that follows decides, plp_kernels.hpp)
     const unsigned char verdict = yes ? 1 : ((mark != 0) & ((st == ST_UNBND) | (st == ST_ITER)) ? PAIR_OPEN : 0);

@@ -1,6 +1,6 @@
 // plp_wide.hpp -- the one-LP-per-wavefront simplex engine (see plp_wide.hip for the design notes): wave reductions, the
-// register-vector row, the per-wavefront LDS block and wide_run().  Shared by cheby_w_kernel (plp_wide.hip) and the F1
-// stage of reduce_lazy_kernel (plp_reduce_r_impl.hpp).
+// register-vector row, the per-wavefront LDS block, wide_run(), the Chebyshev-ball LP on it (cheby_setup / cheby_run /
+// cheby_radius / cheby_point: every F1 of this engine) and the dense F2 / F3 LP (solve_dense).
 #pragma once
 #include "plp_kernels.hpp"
 #include "plp_wave.hpp"
@@ -277,48 +277,104 @@ __device__ __forceinline__ int wide_run(const int lane, const int m, typename Ro
     return status;
 }
 
-// The Chebyshev radius of the polytope whose m <= 64 rows a x <= bi the lanes hold, one each (`has`: this lane holds one),
-// as cheby_ball reads it (polytope.py:1289-1297): the radius when the LP is optimal with r >= 0, 0 when optimal with
-// r < 0, NaN when it ended without a verdict.  The body of server_slot_w (plp_rdiff.hip): the norm column, wide_run's
-// forced first pivot, the read-out.  Wave-uniform result; `sh`: this wavefront's LDS block.
-template <int D>
-__device__ __forceinline__ double cheby_radius_rows(const int lane, const int m, const bool has, const double (&a)[D],
-                                                    const double bi_in, WideShared<D + 1>& sh) {
+// ---- The Chebyshev-ball LP (F1, polytope.py:1283-1288) of this engine, stated once: every kernel that solves it on a
+// wavefront calls cheby_setup, its own barrier, cheby_run and one of the two read-outs.  What a call site may vary:
+//   * where the row comes from (a packed table, a gathered row index, a stacked pair with b + inflate, LDS): it hands
+//     over two functors, which the set-up calls under `has`;
+//   * side stores (the row to LDS, 1 / ||a|| = c.inv_nrm);
+//   * its own extra condition for "no verdict" (m > 64, !valid): cheby_run's `bad_extra`;
+//   * the barrier between set-up and run -- __syncthreads() where other wavefronts wait on what the site stored beside
+//     the set-up, wave_sync() otherwise; nothing here contains a workgroup barrier -- and a leading wave_sync() where
+//     the LDS block is reused from an earlier LP.
+// ChebyRow: what the set-up leaves besides the row.  The row (Tv / T16) stays a pair of plain local variables of the caller,
+// as everywhere on this engine: as a struct member the compiler keeps the register vector in scratch memory.
+struct ChebyRow {
+    double beta;
+    double q0;        // b_i / ||a_i||: the forced first pivot leaves at the smallest one
+    double inv_nrm;   // 1 / ||a_i||
+    int rowvar, rowneg;
+    bool rowact;
+    bool bad, infeasible0;   // wave votes: a non-finite entry; a zero row with b < -TOL_FEAS
+};
+
+// Set-up: the rows normalised (the norm in column D), beta = b on live rows, cost[D] = -1 into the wavefront's block.
+// rowA(k) / rowb(): the lane's row a x <= b, asked for where `has` only (a site's loads stay under its own guard).
+template <int D, class FA, class FB>
+__device__ __forceinline__ void cheby_setup(typename RowVec<D + 1>::type& Tv, double& T16, ChebyRow& c, const int lane,
+                                            const bool has, FA rowA, FB rowb, WideShared<D + 1>& sh) {
     constexpr int NC = D + 1;
-    typename RowVec<NC>::type Tv = (typename RowVec<NC>::type)(0.0);
-    double T16 = 0.0;
+    Tv = (typename RowVec<NC>::type)(0.0);
+    T16 = 0.0;
     double nrm2 = 0.0;
     bool finite = true;
 #pragma unroll
     for (int k = 0; k < D; ++k) {
-        const double v = has ? a[k] : 0.0;
+        const double v = has ? rowA(k) : 0.0;
         ROW_SET(k, v);
         nrm2 = nrm2 + v * v;
         finite = finite & isfinite(v);
     }
-    const double bi = has ? bi_in : 0.0;
+    const double bi = has ? rowb() : 0.0;
     finite = finite & isfinite(bi);
     const double nrm = sqrt(nrm2);
     const bool zero = !(nrm > 0.0);
-    bool rowact = has & !zero;
-    ROW_SET(D, rowact ? nrm : 0.0);
-    double beta = rowact ? bi : 0.0;
-    int rowvar = NC + lane, rowneg = 0;
-    wave_sync();   // (the last LP's reads of the block are done)
+    c.rowact = has & !zero;
+    ROW_SET(D, c.rowact ? nrm : 0.0);
+    c.beta = c.rowact ? bi : 0.0;
+    c.q0 = bi / nrm;
+    c.inv_nrm = 1.0 / nrm;
+    c.rowvar = NC + lane;
+    c.rowneg = 0;
     if (lane <= NC) {
         sh.cost[lane] = lane == D ? -1.0 : 0.0;
         sh.cv[lane] = (lane + 1) << 1;
     }
-    const bool infeasible0 = __ballot(has & zero & (bi < -TOL_FEAS)) != 0;
-    const bool bad = (__ballot(!finite) != 0) | (m > 64);
-    wave_sync();
+    c.infeasible0 = __ballot(has & zero & (bi < -TOL_FEAS)) != 0;
+    c.bad = __ballot(!finite) != 0;
+}
+
+// Run: the status (ST_NUM without a pivot when the input is bad, ST_INFEAS for the zero row, else wide_run with the
+// forced first pivot); the optimal dictionary stays in Tv / T16 / c.
+template <int D>
+__device__ __forceinline__ int cheby_run(typename RowVec<D + 1>::type& Tv, double& T16, ChebyRow& c, const int lane,
+                                         const int m, WideShared<D + 1>& sh, const bool bad_extra) {
     int st, iters = 0;
-    if (bad) st = ST_NUM;
-    else if (infeasible0) st = ST_INFEAS;
-    else st = wide_run<NC>(lane, m, Tv, T16, beta, rowvar, rowneg, rowact, sh, NC, true, bi / nrm, iters);
-    const double mine = rowneg ? -beta : beta;
-    const uint64_t ob = __ballot(rowvar == D);
-    const double rv = ob ? uniform_lane(mine, __ffsll((long long)ob) - 1) : 0.0;
+    if (c.bad | bad_extra) st = ST_NUM;
+    else if (c.infeasible0) st = ST_INFEAS;
+    else st = wide_run<D + 1>(lane, m, Tv, T16, c.beta, c.rowvar, c.rowneg, c.rowact, sh, D + 1, true, c.q0, iters);
+    return st;
+}
+
+// Read-out: structural j is read from the lane whose row holds it, 0 when it ended nonbasic.  Wave-uniform.  One ballot
+// per variable: the sites that need the radius only ask for it alone.
+__device__ __forceinline__ double cheby_x(const ChebyRow& c, const int j) {
+    const double mine = c.rowneg ? -c.beta : c.beta;
+    const uint64_t ob = __ballot(c.rowvar == j);
+    return ob ? uniform_lane(mine, __ffsll((long long)ob) - 1) : 0.0;
+}
+template <int D>
+__device__ __forceinline__ double cheby_radius(const ChebyRow& c) { return cheby_x(c, D); }
+template <int D>
+__device__ __forceinline__ void cheby_point(const ChebyRow& c, double (&x)[D + 1]) {   // x[0..D-1] centre, x[D] radius
+#pragma unroll
+    for (int j = 0; j <= D; ++j) x[j] = cheby_x(c, j);
+}
+
+// The Chebyshev radius of the polytope whose m <= 64 rows a x <= bi the lanes hold, one each (`has`: this lane holds one),
+// as cheby_ball reads it (polytope.py:1289-1297): the radius when the LP is optimal with r >= 0, 0 when optimal with
+// r < 0, NaN when it ended without a verdict.  Wave-uniform result; `sh`: this wavefront's LDS block, which may still
+// be in use by the wavefront's last LP.
+template <int D>
+__device__ __forceinline__ double cheby_radius_rows(const int lane, const int m, const bool has, const double (&a)[D],
+                                                    const double bi, WideShared<D + 1>& sh) {
+    typename RowVec<D + 1>::type Tv;
+    double T16;
+    ChebyRow c;
+    wave_sync();   // (the last LP's reads of the block are done)
+    cheby_setup<D>(Tv, T16, c, lane, has, [&](int k) { return a[k]; }, [&]() { return bi; }, sh);
+    wave_sync();
+    const int st = cheby_run<D>(Tv, T16, c, lane, m, sh, m > 64);
+    const double rv = cheby_radius<D>(c);
     return st != ST_OPT ? __builtin_nan("") : (rv >= 0.0 ? rv : 0.0);
 }
 
