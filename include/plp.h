@@ -569,6 +569,36 @@ int plp_pair_list_dev(plp_ctx *ctx, void *stream, int n, int m_max, int d, const
                       const int32_t *m, double inflate, double thresh, int64_t K, const int32_t *pairs, uint8_t *out);
 
 /*
+ * Closest points and Euclidean distances of a LIST of cell pairs:  min |x - y|_2  s.t.  A_i x <= b_i,  A_j y <= b_j  for
+ * pair t = (pairs[t][0], pairs[t][1]) = (i, j) of the n cells -- a GJK iteration per pair on the Minkowski difference, its
+ * support points from the support LP of plp_support_batch, two lanes per pair (csrc/plp_pair_dist.hpp).
+ * In:  A[n][m_max][d], b[n][m_max], m[n] (NULL = m_max);  xc[n][d]: a STRICTLY interior point per cell, as for
+ *      plp_support_batch;  pairs[K][2] int32, a pair may be listed more than once and in either order.
+ * Out: dist[K] = |x - y|_2;  lb[K] (NULL ok): the lower bound -h_i(-u) - h_j(u), u = (x - y) / dist, the iteration ended with,
+ *      held to [0, dist];  x[K][d], y[K][d] (NULL ok): the closest points, x in cell i and y in cell j;  status[K]:
+ *        0  settled.  With E = max(1, |x|_inf, |y|_inf):  dist - max(lb, 0) <= 1e-10 E  or  dist <= 1e-10 E  (the cells meet:
+ *           lb = 0), and x, y are inside every row of their cells to 1e-10 E on unit-scaled slack.  With the bounds of the
+ *           two support values that gives  -2e-10 E <= dist - dist* <= 5e-10 E'  (E' the extent of the last support points;
+ *           the derivation is in csrc/plp_pair_dist.hpp);
+ *        1  NOT SETTLED HERE (dist = lb = x = y = NaN): a support LP was handed back, a centre is not strictly inside its
+ *           cell or not finite, a row is not finite, the round cap (16), or a stall.  The caller settles these
+ *           (polytope_amd.batch: distance_pairs(resolve=True));
+ *        3  a support LP came back unbounded: a cell is unbounded in a direction the iteration asked for, which includes a
+ *           cell without rows.  NaN outputs; not settled by this call;
+ *        PLP_PAIR_BAD (255)  an index outside [0, n) or i == j, device-pointer form only: NaN outputs, and nothing of the table
+ *           is read for the pair.  The host-pointer form returns PLP_EINVAL for such a list before anything runs.
+ * d <= 4, m_max <= 64 and K <= 2^31 - 1, else PLP_EUNSUPPORTED.  K = 0 or n = 0: returns PLP_OK, nothing runs.
+ * The host-pointer form checks A and b for inf / nan when the context asks for it (plp_ctx_set_check_finite).  The call
+ * runs on the caller's stream and needs no scratch.
+ */
+int plp_pair_dist(plp_ctx *ctx, int n, int m_max, int d, const double *A, const double *b, const int32_t *m,
+                  const double *xc, int64_t K, const int32_t *pairs, double *dist, double *lb, double *x, double *y,
+                  int32_t *status);
+int plp_pair_dist_dev(plp_ctx *ctx, void *stream, int n, int m_max, int d, const double *A, const double *b,
+                      const int32_t *m, const double *xc, int64_t K, const int32_t *pairs, double *dist, double *lb,
+                      double *x, double *y, int32_t *status);
+
+/*
  * The broad phase in front of plp_pair_list: the pairs of cells whose outer boxes meet.  Cell p has the box lb[p][d],
  * ub[p][d], padded to L_p = lb_p - pad', U_p = ub_p + pad' with pad' = pad * max(1, the box's largest finite |bound|); NaN
  * bounds and infinite sides span their axis (as plp_locate_grid_count).  (i, j) is a CANDIDATE iff

@@ -27,6 +27,7 @@ from .polytope import (  # noqa: F401
     reduce, separate, box2poly,
     cheby_ball, bounding_box, envelope, extreme, qhull,
     is_inside, union, mldivide, intersect, intersect_pairs, volume, volume_exact, nearest, distance,
+    distance_pairs, set_distance,
 )
 from .prop2partition import (  # noqa: F401
     Partition, MetricPartition, find_adjacent_regions, adjacency_sparse, overlap_sparse, overlay)
@@ -37,6 +38,7 @@ from .batch import (  # noqa: F401
     volume_exact_batch, locate_batch, locate_grid, projection_hull_batch, nearest_batch,
     adjacent_pairs_sparse, overlap_pairs_sparse, overlap_cross_sparse, box_pairs, pair_verdicts,
     pair_stacks, intersect_cross_sparse,   # (the packed intersect_pairs is batch.intersect_pairs: the root name is the Polytope-level call)
+    # (likewise distance_pairs: the packed call is batch.distance_pairs)
 )
 from .polytope import region_diff_batch  # noqa: F401,E402  (the Polytope-level call; the packed one is batch.region_diff_batch)
 from .polytope import envelope_batch, is_convex_batch  # noqa: F401,E402  (the raw launch is batch.envelope_outer_batch)

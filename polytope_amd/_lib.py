@@ -99,6 +99,9 @@ SIGNATURES = {
     "plp_pair_list": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_double, C.c_double, C.c_int64, _vp, _vp]),
     "plp_pair_list_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_double, C.c_double, C.c_int64, _vp,
                                     _vp]),
+    "plp_pair_dist": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "plp_pair_dist_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp,
+                                    _vp]),
     "plp_box_pairs_count": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, C.c_double, _vp, _vp, _vp, C.c_int, _vp]),
     "plp_box_pairs_count_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_double, _vp, _vp, _vp, C.c_int, _vp]),
     "plp_box_pairs_fill": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, C.c_double, _vp, _vp, _vp, C.c_int, _vp, C.c_int,

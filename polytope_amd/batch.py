@@ -1677,6 +1677,201 @@ def intersect_pairs(A, b, pairs, m=None, abs_tol=1e-7, rows=True, chunk=None, mo
     return res
 
 
+# ------------------------------------------------------------------------------------- distances of listed pairs
+_PAIR_DIST_MAX_D = 4            # the kernel (csrc/plp_pair_dist.hip) holds a simplex of d + 1 <= 5 points in registers
+_PAIR_DIST_TOL = 1e-10          # the gap test of csrc/plp_pair_dist.hpp, relative to E = max(1, |x|_inf, |y|_inf)
+_PAIR_DIST_ROUNDS = 64          # rounds of the host iteration before it gives up (status 4)
+PAIR_BAD = 255
+
+
+def _hull_nearest_origin(W, lam):
+    """Wolfe's sub-algorithm in numpy: W[n, d] (the last point new, lam[n - 1] = 0) -> (kept indices, lam on them) with
+    sum lam_k W_k the point of conv(W) nearest to the origin, or (None, None) for a corral that is affinely dependent."""
+    keep = np.arange(W.shape[0])
+    lam = np.asarray(lam, dtype=float).copy()
+    for _ in range(W.shape[0] + 2):
+        V = W[keep]
+        if keep.size == 1:
+            return keep, np.ones(1)
+        Em = (V[1:] - V[0]).T
+        a, _, rank, _ = np.linalg.lstsq(Em, -V[0], rcond=None)
+        if rank < keep.size - 1 or not np.all(np.isfinite(a)):
+            return None, None
+        al = np.concatenate([[1.0 - a.sum()], a])
+        if np.all(al > 0.0):
+            return keep, al
+        neg = al <= 0.0
+        den = lam - al
+        ratio = np.where(neg & (den > 0.0), lam / np.where(den > 0.0, den, 1.0), np.where(neg, 0.0, np.inf))
+        kz = int(np.argmin(ratio))
+        lam = lam + ratio[kz] * (al - lam)
+        lam[kz] = 0.0
+        stay = lam > 0.0
+        if not stay.any():
+            return None, None
+        keep, lam = keep[stay], lam[stay]
+    return None, None
+
+
+def _pair_dist_resolve(be, A, b, m, pairs, out):
+    """Raw status 1 settled on the host (distance_pairs: resolve=True), written into the arrays of `out`: the iteration of
+    csrc/plp_pair_dist.hpp in numpy, its support points from lpsolve_batch (two calls per round for all open pairs), which
+    starts from no centre -- flat cells are settled too.  -> codes 0, 2 (a cell is empty), 3 (unbounded), 4."""
+    host = (lambda a: a.cpu().numpy()) if be.torch is not None else (lambda a: a)
+    open_ = np.nonzero(host(out["status"]) == 1)[0]
+    if not open_.size:
+        return
+    d, m_max = A.shape[2], A.shape[1]
+    ph = host(pairs)[open_].astype(np.int64)
+    cells, inv = np.unique(ph, return_inverse=True)
+    inv = inv.reshape(ph.shape)
+    sel = cells if be.torch is None else be.torch.as_tensor(cells, device=be.device)
+    Ah, bh = host(A[sel]), host(b[sel])
+    mh = np.full(cells.size, m_max, np.int32) if m is None else np.clip(host(m[sel]), 0, m_max).astype(np.int32)
+    live = np.arange(m_max)[None, :] < mh[:, None]
+    fin = (np.isfinite(Ah).all(axis=2) | ~live).all(axis=1) & (np.isfinite(bh) | ~live).all(axis=1)
+    Ah, bh = np.where(live[:, :, None], Ah, 0.0), np.where(live, bh, 0.0)
+    n = open_.size
+    res = dict(dist=np.full(n, np.nan), lb=np.full(n, np.nan), x=np.full((n, d), np.nan), y=np.full((n, d), np.nan),
+               status=np.full(n, 4, np.int32))
+    ci, cj = inv[:, 0], inv[:, 1]
+    run = fin[ci] & fin[cj]
+    u = np.zeros((n, d))
+    u[:, 0] = 1.0
+    W, P, Q, lam = [None] * n, [None] * n, [None] * n, [None] * n
+    cur = [None] * n   # (dist, E, x, y) of the current simplex
+    for _ in range(_PAIR_DIST_ROUNDS):
+        act = np.nonzero(run)[0]
+        if not act.size:
+            break
+        si = lpsolve_batch(u[act], Ah[ci[act]], bh[ci[act]], mh[ci[act]])
+        sj = lpsolve_batch(-u[act], Ah[cj[act]], bh[cj[act]], mh[cj[act]])
+        for q, t in enumerate(act):
+            a, c = int(si["status"][q]), int(sj["status"][q])
+            if a or c:
+                res["status"][t] = 2 if 2 in (a, c) else (3 if 3 in (a, c) else 4)
+                run[t] = False
+                continue
+            p, r = si["x"][q], sj["x"][q]
+            w = p - r
+            lbv = float(u[t] @ w)
+            if cur[t] is not None and cur[t][0] - max(lbv, 0.0) <= _PAIR_DIST_TOL * cur[t][1]:
+                dd, _, xx, yy = cur[t]
+                res["dist"][t], res["lb"][t], res["x"][t], res["y"][t], res["status"][t] = dd, min(max(lbv, 0.0), dd), xx, yy, 0
+                run[t] = False
+                continue
+            if W[t] is None:
+                W[t], P[t], Q[t], lam[t] = w[None], p[None], r[None], np.zeros(1)
+            else:
+                if np.any(np.all(W[t] == w[None], axis=1)) or W[t].shape[0] > d:
+                    run[t] = False   # a stall: status 4
+                    continue
+                W[t], P[t], Q[t], lam[t] = np.vstack([W[t], w]), np.vstack([P[t], p]), np.vstack([Q[t], r]), np.append(lam[t], 0.0)
+            keep, l = _hull_nearest_origin(W[t], lam[t])
+            if keep is None:
+                run[t] = False
+                continue
+            W[t], P[t], Q[t], lam[t] = W[t][keep], P[t][keep], Q[t][keep], l
+            xx, yy = l @ P[t], l @ Q[t]
+            v = xx - yy
+            dd = float(np.linalg.norm(v))
+            E = max(1.0, float(np.max(np.abs(xx))), float(np.max(np.abs(yy))))
+            fell = cur[t] is None or dd < cur[t][0]
+            cur[t] = (dd, E, xx, yy)
+            if dd <= _PAIR_DIST_TOL * E:
+                res["dist"][t], res["lb"][t], res["x"][t], res["y"][t], res["status"][t] = dd, 0.0, xx, yy, 0
+                run[t] = False
+            elif not fell or W[t].shape[0] > d:
+                run[t] = False
+            else:
+                u[t] = v / dd
+    for k, v in res.items():
+        if out.get(k) is None:
+            continue
+        if be.torch is not None:
+            out[k][be.torch.as_tensor(open_, device=be.device)] = be.torch.as_tensor(v).to(be.device)
+        else:
+            out[k][open_] = v
+
+
+def distance_pairs(A, b, pairs, m=None, xc=None, points=True, resolve=True):
+    """Closest points and Euclidean distances of listed cell pairs of a table:  min |x - y|_2  s.t.  A_i x <= b_i,  A_j y <= b_j
+    for pair t = (pairs[t, 0], pairs[t, 1]) = (i, j) of the n cells A[n, m_max, d], b[n, m_max], m[n] -- a GJK iteration per
+    pair on the device, its support points from the support LP of support_batch, two lanes per pair (include/plp.h:
+    plp_pair_dist; csrc/plp_pair_dist.hpp).  pairs int32[K, 2]; a pair may appear more than once, in either order.
+    xc[n, d]: a strictly interior point per cell; None: cheby_ball_batch runs first -- a cell it finds infeasible gives
+    status 2 for its pairs, one without a usable centre (r <= 0, r = inf, the LP not optimal) a NaN centre, which the kernel
+    hands back as status 1 (as support_batch).
+    -> dict(dist[K], lb[K], x[K, d], y[K, d] (None with points=False), status int32[K]); numpy in, numpy out; CUDA tensors
+    in, tensors out on torch's current stream.  x lies in cell i, y in cell j, dist = |x - y|, lb <= dist the lower bound
+    -h_i(-u) - h_j(u), u = (x - y) / dist, of the last round (0 where the cells meet).
+    status: 0 settled -- dist - max(lb, 0) <= 1e-10 E or dist <= 1e-10 E with E = max(1, |x|_inf, |y|_inf), x and y inside
+    every row to 1e-10 E on unit-scaled slack, which holds dist within 5e-10 of the extent above and 2e-10 E below the true
+    distance (plp_pair_dist.hpp has the derivation); 2 a cell is empty; 3 a cell is unbounded in a direction the iteration
+    asked for (a cell without rows is); 4 no convergence or an input that is not finite; 1 (only with resolve=False) not
+    settled by the kernel.  dist = lb = x = y = NaN wherever the status is not 0.
+    resolve=True (the default) settles raw status 1 on the host: the same iteration in numpy with support points from
+    lpsolve_batch (the certified path, which needs no centre, so flat cells are settled too).
+    numpy: an index outside [0, n) or a pair (i, i) raises ValueError; CUDA tensors (nothing synchronises, so the list is
+    not read by the host): such a pair gets status 255 (PAIR_BAD), NaN outputs, and nothing of the table is read for it.
+    d <= 4 and m_max <= 64 only: other shapes raise UnsupportedSize.  There is NO fallback kernel for them."""
+    be = _Backend(A)
+    A, b, m, (n, m_max, d) = _packed(be, A, b, m)
+    # (inf / nan in numpy inputs: ValueError from the library, which checks them while staging -- plp_ctx_set_check_finite)
+    pairs = be.arr(pairs, np.int32)
+    if len(pairs.shape) != 2 or pairs.shape[1] != 2:
+        raise ValueError("pairs must be [K, 2]")
+    K = int(pairs.shape[0])
+    if d > _PAIR_DIST_MAX_D or m_max > MAX_M:
+        raise _lib.UnsupportedSize("distance_pairs: m_max=%d d=%d outside the shared-row kernel (m <= 64, d <= 4)" % (m_max, d))
+    if K > 2 ** 31 - 1:
+        raise _lib.UnsupportedSize("distance_pairs: K exceeds 2^31 - 1")
+    out = dict(dist=be.out((K,), zero=True), lb=be.out((K,), zero=True), x=be.out((K, d), zero=True) if points else None,
+               y=be.out((K, d), zero=True) if points else None, status=be.out((K,), np.int32, zero=True))
+    if K == 0:
+        return out
+    if be.torch is None:
+        bad = (pairs < 0) | (pairs >= n)
+        bad = bad[:, 0] | bad[:, 1] | (pairs[:, 0] == pairs[:, 1])
+        if bad.any():
+            t = int(np.nonzero(bad)[0][0])
+            raise ValueError("distance_pairs: pair %d = (%d, %d): indices must be two different cells of [0, %d)"
+                             % (t, pairs[t, 0], pairs[t, 1], n))
+    elif n == 0:   # (no table: every listed pair is a bad one, and the library writes nothing)
+        out["status"].fill_(PAIR_BAD)
+        for k in ("dist", "lb", "x", "y"):
+            if out[k] is not None:
+                out[k].fill_(float("nan"))
+        return out
+    xp = be.torch if be.torch is not None else np
+    infeasible = None
+    if xc is not None:
+        xc = _support_input(be, xc)
+        if tuple(xc.shape) != (n, d):
+            raise ValueError("xc must be [n, d] = [%d, %d], got %s" % (n, d, list(xc.shape)))
+    else:
+        ball = cheby_ball_batch(A, b, m)
+        r = ball["r"]
+        ok = (ball["status"] == 0) & (r > 0) & (r < float("inf"))
+        nan = float("nan") if be.torch is None else be.torch.full((), float("nan"), dtype=be.torch.float64, device=be.device)
+        xc = xp.where(ok[:, None], ball["xc"], nan)
+        infeasible = ball["status"] == 2
+    be.call("plp_pair_dist", n, m_max, d, A, b, m, xc, K, pairs, out["dist"], out["lb"], out["x"], out["y"], out["status"],
+            h2d=(A, b, m, xc, pairs))
+    if infeasible is not None and bool(infeasible.any()):
+        # (a list on the device may hold indices outside [0, n): those pairs keep their 255)
+        pc = pairs.clip(0, n - 1) if be.torch is None else pairs.clamp(0, n - 1)
+        hit = (infeasible[pc[:, 0].long() if be.torch is not None else pc[:, 0]] |
+               infeasible[pc[:, 1].long() if be.torch is not None else pc[:, 1]]) & (out["status"] != PAIR_BAD)
+        out["status"][hit] = 2
+        for k in ("dist", "lb", "x", "y"):
+            if out[k] is not None:
+                out[k][hit] = float("nan")
+    if resolve:
+        _pair_dist_resolve(be, A, b, m, pairs, out)
+    return out
+
+
 def intersect_cross_sparse(A, b, n1, m=None, abs_tol=1e-7, boxes=None, max_candidates=1 << 24, chunk=None):
     """The overlay of two lists of cells in one table (n1 cells, then n - n1): the full-dimensional intersections a ∩ c of a
     cell a < n1 of the first list with a cell c of the second, without any n1 x n2 object.

@@ -1026,6 +1026,65 @@ int plp_nearest_batch(plp_ctx* ctx, int64_t B, int m_max, int d, const double* A
     return hc.download();
 }
 
+// ------------------------------------------------------------------------------- distances of listed cell pairs
+namespace {
+int pair_dist_check(plp_ctx* ctx, int n, int m_max, int d, const double* A, const double* b, const double* xc, int64_t K,
+                    const int32_t* pairs, const double* dist, const int32_t* status) {
+    if (!ctx) return fail(PLP_EINVAL, "ctx is NULL");
+    if (n < 0 || K < 0 || m_max < 0 || d < 1) return fail(PLP_EINVAL, "bad sizes");
+    if (n == 0 || K == 0) return PLP_OK;
+    if (d > 4 || m_max > plp::MAX_M)
+        return fail(PLP_EUNSUPPORTED, "pair_dist: m_max=%d d=%d outside the shared-row kernel (m<=64, d<=4)", m_max, d);
+    if (K > 2147483647ll) return fail(PLP_EUNSUPPORTED, "pair_dist: K exceeds 2^31 - 1");
+    if ((m_max > 0 && (!A || !b)) || !xc || !pairs || !dist || !status) return fail(PLP_EINVAL, "NULL pointer");
+    return PLP_OK;
+}
+}  // namespace
+
+// (no scratch: the kernel keeps its state in registers and LDS, so there is nothing per stream to reserve)
+int plp_pair_dist_dev(plp_ctx* ctx, void* stream, int n, int m_max, int d, const double* A, const double* b, const int32_t* m,
+                      const double* xc, int64_t K, const int32_t* pairs, double* dist, double* lb, double* x, double* y,
+                      int32_t* status) {
+    int rc = pair_dist_check(ctx, n, m_max, d, A, b, xc, K, pairs, dist, status);
+    if (rc || n == 0 || K == 0) return rc;
+    if (plp::launch_pair_dist(n, m_max, d, A, b, m, xc, K, pairs, dist, lb, x, y, status, (hipStream_t)stream))
+        return fail(PLP_EUNSUPPORTED, "pair_dist: unsupported size");
+    return check_launch("pair_dist_kernel");
+}
+
+int plp_pair_dist(plp_ctx* ctx, int n, int m_max, int d, const double* A, const double* b, const int32_t* m, const double* xc,
+                  int64_t K, const int32_t* pairs, double* dist, double* lb, double* x, double* y, int32_t* status) {
+    int rc = pair_dist_check(ctx, n, m_max, d, A, b, xc, K, pairs, dist, status);
+    if (rc || n == 0 || K == 0) return rc;
+    for (int64_t t = 0; t < K; ++t) {
+        const int32_t i = pairs[2 * t], j = pairs[2 * t + 1];
+        if (i < 0 || i >= n || j < 0 || j >= n || i == j)
+            return fail(PLP_EINVAL, "pair %lld = (%d, %d): indices must be two different cells of [0, %d)", (long long)t, i, j, n);
+    }
+    const size_t kd = (size_t)K * d;
+    double *dA, *db, *dxc, *ddist, *dlb, *dx, *dy;
+    int32_t *dm, *dpairs, *dst;
+    HostCall hc(ctx);
+    hc.in(dA, A, (size_t)n * m_max * d, 0, true);
+    hc.in(db, b, (size_t)n * m_max, 0, true);
+    hc.in(dm, m, n);
+    hc.in(dxc, xc, (size_t)n * d);   // (a centre may be NaN: its pairs come back as status 1)
+    hc.in(dpairs, pairs, (size_t)K * 2);
+    hc.out(ddist, dist, K);
+    hc.out(dlb, lb, lb ? K : 0);
+    hc.out(dx, x, x ? kd : 0);
+    hc.out(dy, y, y ? kd : 0);
+    hc.out(dst, status, K);
+    rc = hc.reserve();
+    if (rc) return rc;
+    rc = hc.upload();
+    if (rc) return rc;
+    rc = plp_pair_dist_dev(ctx, hc.st, n, m_max, d, dA, db, dm, dxc, K, dpairs, ddist, lb ? dlb : nullptr, x ? dx : nullptr,
+                           y ? dy : nullptr, dst);
+    if (rc) return rc;
+    return hc.download();
+}
+
 // ------------------------------------------------------------------------------- vertex enumeration
 namespace {
 int extreme_check(plp_ctx* ctx, int64_t B, int m_max, int d, const double* A, const double* b, int v_max, const double* V,

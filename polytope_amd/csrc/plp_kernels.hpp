@@ -57,6 +57,11 @@ int launch_support(long long B, int m_max, int d, const double* A, const double*
 // face[B][K], lam[B][K][d] each or nullptr.  2: unsupported size
 int launch_nearest(long long B, int m_max, int d, const double* A, const double* b, const int* mrows, int K, const double* X,
                    int x_shared, double* dist, double* x, unsigned long long* face, double* lam, int* status, hipStream_t st);
+// closest points / Euclidean distances of K listed cell pairs of a table of n cells, two lanes per pair (plp_pair_dist.hip;
+// d <= 4, m_max <= 64): dist[K], status[K] (0 settled, 1 handed back, 3 unbounded, 255 a bad pair); lb[K], x[K][d], y[K][d]
+// each or nullptr.  2: unsupported size
+int launch_pair_dist(int n, int m_max, int d, const double* A, const double* b, const int* mrows, const double* xc, long long K,
+                     const int* pairs, double* dist, double* lb, double* x, double* y, int* status, hipStream_t st);
 // vertices of small polytopes by enumeration of bases, one polytope per wavefront (plp_extreme.hip; d <= 4, m_max <= 64):
 // V[B][v_max][d], count[B], basis[B][v_max][d] (or nullptr), status[B] (0, 1 overflow, 2 empty).  2: unsupported size
 int launch_extreme(long long B, int m_max, int d, const double* A, const double* b, const int* mrows,

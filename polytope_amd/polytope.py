@@ -2866,3 +2866,63 @@ def projection_esp(poly1, keep_dim, del_dim):
     if "glpk" not in solvers.installed_solvers:
         raise Exception("projection_esp error: Equality set projection requires `cvxopt.glpk` to run.")
     raise Exception("projection_esp: not provided")
+
+
+# ====================================================================================== distances between cells
+def distance_pairs(cells, pairs):
+    """(dist[K], x[K, d], y[K, d]) for the listed pairs (i, j) of a list of Polytopes: the Euclidean distance of cells[i] and
+    cells[j] and a closest pair of points, x in cells[i] and y in cells[j] (dist = 0 where they meet).  dist = inf and NaN
+    points where a cell is empty; NaN throughout where the call could not settle a pair (an unbounded cell, no
+    convergence).  ONE batch.distance_pairs call on the cells' packed table (kept by _table_of, as intersect_pairs does).
+    Dimension <= 4 and at most 64 rows per cell (other shapes raise UnsupportedSize); 'hip' backend only."""
+    if not _use_hip():
+        raise ValueError("distance_pairs / set_distance need the 'hip' backend (polytope_amd.batch.distance_pairs), got %r"
+                         % (solvers.default_solver,))
+    solvers._require("hip")
+    cells = list(cells)
+    plist = np.array([(int(i), int(j)) for i, j in pairs], dtype=np.int64).reshape(-1, 2)
+    K = plist.shape[0]
+    if K and (plist.min() < 0 or plist.max() >= len(cells) or np.any(plist[:, 0] == plist[:, 1])):
+        raise ValueError("distance_pairs: pairs must name two different cells of [0, %d)" % len(cells))
+    dims = {c.A.shape[1] for c in cells if c.A.size}
+    if len(dims) > 1:
+        raise ValueError("distance_pairs: cells of different dimensions")
+    d = dims.pop() if dims else 0
+    dist, x, y = np.full(K, np.inf), np.full((K, d), np.nan), np.full((K, d), np.nan)
+    slot = {k: s for s, k in enumerate(k for k, c in enumerate(cells) if c.A.size)}
+    at = np.array([t for t in range(K) if plist[t, 0] in slot and plist[t, 1] in slot], dtype=np.int64)
+    if not at.size:
+        return dist, x, y
+    from . import batch
+    members = [cells[k] for k in slot]
+    if len(members) >= 8:
+        At, bt, mt = _table_of(members).dev()
+    else:
+        At, bt, mt = _pack(members)
+    listed = np.array([(slot[plist[t, 0]], slot[plist[t, 1]]) for t in at], dtype=np.int32)
+    if not isinstance(At, np.ndarray):
+        batch._count_h2d(listed)
+        listed = _torch_or_none().as_tensor(listed).to(At.device)
+    res = batch.distance_pairs(At, bt, listed, m=mt)
+    res = {k: (v if isinstance(v, np.ndarray) else v.cpu().numpy()) for k, v in res.items()}
+    st = res["status"]
+    dist[at] = np.where(st == 0, res["dist"], np.where(st == 2, np.inf, np.nan))
+    x[at], y[at] = res["x"], res["y"]
+    return dist, x, y
+
+
+def set_distance(a, b):
+    """The Euclidean distance of two sets, each a Polytope or a Region: the minimum over all member pairs, from one
+    distance_pairs call.  -> (dist, x[d], y[d], (member_a, member_b)): a closest pair of points, x in `a` and y in `b`, and
+    the members they lie in (indices into list_poly; 0 for a Polytope); the lowest pair index wins ties, pairs counted
+    member_a-major.  (inf, NaN, NaN, (-1, -1)) where no pair has a distance: a set is empty."""
+    la = a.list_poly if isinstance(a, Region) else [a]
+    lb = b.list_poly if isinstance(b, Region) else [b]
+    na, nb = len(la), len(lb)
+    pairs = [(i, na + j) for i in range(na) for j in range(nb)]
+    dist, x, y = distance_pairs(list(la) + list(lb), pairs)
+    d = x.shape[1]
+    if not len(pairs) or not np.any(np.isfinite(dist)):
+        return np.inf, np.full(d, np.nan), np.full(d, np.nan), (-1, -1)
+    t = int(np.argmin(np.where(np.isfinite(dist), dist, np.inf)))
+    return float(dist[t]), x[t].copy(), y[t].copy(), (t // nb, t % nb)
