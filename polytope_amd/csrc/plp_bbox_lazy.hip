@@ -9,13 +9,10 @@
 // step limit): the caller solves the generic LPs for those.
 #include "plp_lp_launch.hpp"
 #include "plp_lazy.hpp"
+#include "plp_reduce_rules.hpp"
 #include "plp_wide.hpp"
 
 namespace plp {
-
-namespace {
-constexpr double BBOX_LAZY_MIN_R = 1e-6;  // (bbox_r_kernel's BBOX_MIN_R)
-}
 
 template <int D, bool WDENSE>
 __global__ __launch_bounds__(64, 3) void bbox_lazy_kernel(long long B, int m_max, const double* __restrict__ A,
@@ -43,15 +40,14 @@ __global__ __launch_bounds__(64, 3) void bbox_lazy_kernel(long long B, int m_max
     const int st = wide::cheby_run<D>(Tv, T16, c, lane, m, sh, m > 64);
     double x[NC];
     wide::cheby_point<D>(c, x);
-    const bool ok = (st == ST_OPT) & (x[D] >= BBOX_LAZY_MIN_R);
+    const bool ok = (st == ST_OPT) & (x[D] >= rule::BBOX_MIN_R);
     bool handed = !ok;
     // ---- my slack at the centre (bbox_r_kernel: s by an fma chain, beta = max(b - s, 0))
     double s = 0.0;
 #pragma unroll
     for (int k = 0; k < D; ++k) s = fma(has ? sA[lane * D + k] : 0.0, ok ? x[k] : 0.0, s);
     const double be0 = (ok & has) ? fmax(bi - s, 0.0) : 0.0;
-    const double qnan = __longlong_as_double(0x7ff8000000000000ll);
-    const double pinf = __longlong_as_double(0x7ff0000000000000ll);
+    using rule::qnan;
     for (int it = 0; it < 2 * D; ++it) {  // lower_0, upper_0, lower_1, upper_1, ...
         const int kx = it >> 1;
         const bool up = it & 1;
@@ -68,10 +64,9 @@ __global__ __launch_bounds__(64, 3) void bbox_lazy_kernel(long long B, int m_max
                                           *reinterpret_cast<wide::WideShared<D>*>(&sh), bo);
             else
                 s2 = lazy::solve<D>(lane, m, sA, (lane == kx) ? (up ? -1.0 : 1.0) : 0.0, be0, has, negz, bo);
-            // zeta = c.x' = -negz ; x_k = xc_k + x'_k ; lower: c = +e_k, upper: c = -e_k
-            if (s2 == ST_OPT) val = up ? (xck + negz) : (xck - negz);
-            else if (s2 == ST_UNBND) val = up ? pinf : -pinf;
-            else handed = true;
+            bool bad;
+            val = rule::box_value(s2, up, rule::box_optimum(up, xck, negz), bad);
+            handed = handed | bad;
         }
         if (lane == 0) (up ? ub : lb)[p * D + kx] = ok ? val : qnan;
     }
@@ -123,7 +118,7 @@ __global__ __launch_bounds__(64 * NW) void bbox_wsplit_kernel(long long B, int m
             for (int j = 0; j < NC; ++j) sx[j] = xf[j];
         }
         if (lane == 0) {
-            sflag[0] = ((st == ST_OPT) & (xr >= BBOX_LAZY_MIN_R)) ? 1u : 0u;
+            sflag[0] = ((st == ST_OPT) & (xr >= rule::BBOX_MIN_R)) ? 1u : 0u;
             sflag[1] = 0u;
         }
     }
@@ -138,8 +133,7 @@ __global__ __launch_bounds__(64 * NW) void bbox_wsplit_kernel(long long B, int m
 #pragma unroll
     for (int k = 0; k < D; ++k) s = fma(has ? sA[lane * D + k] : 0.0, ok ? x[k] : 0.0, s);
     const double be0 = (ok & has) ? fmax(bi - s, 0.0) : 0.0;
-    const double qnan = __longlong_as_double(0x7ff8000000000000ll);
-    const double pinf = __longlong_as_double(0x7ff0000000000000ll);
+    using rule::qnan;
     bool handed = false;
     for (int it = w; it < 2 * D; it += NW) {  // lower_0, upper_0, lower_1, upper_1, ...: wavefront w every NW-th
         const int kx = it >> 1;
@@ -157,9 +151,9 @@ __global__ __launch_bounds__(64 * NW) void bbox_wsplit_kernel(long long B, int m
                                           *reinterpret_cast<wide::WideShared<D>*>(&shw[w]), bo);
             else
                 s2 = lazy::solve<D>(lane, m, sA, (lane == kx) ? (up ? -1.0 : 1.0) : 0.0, be0, has, negz, bo);
-            if (s2 == ST_OPT) val = up ? (xck + negz) : (xck - negz);
-            else if (s2 == ST_UNBND) val = up ? pinf : -pinf;
-            else handed = true;
+            bool bad;
+            val = rule::box_value(s2, up, rule::box_optimum(up, xck, negz), bad);
+            handed = handed | bad;
         }
         if (lane == 0) (up ? ub : lb)[p * D + kx] = ok ? val : qnan;
     }

@@ -17,6 +17,7 @@
 #pragma once
 #include "plp_lp_launch.hpp"
 #include "plp_pair_index.hpp"
+#include "plp_reduce_rules.hpp"
 #include "plp_simplex_r.hpp"
 
 namespace plp {
@@ -69,7 +70,7 @@ __global__ __launch_bounds__(RBLK, (D <= 4 ? 3 : 1)) void cheby_r_kernel(long lo
     const int st = cheby_r_solve<D, GS, R>(
         g, valid, m, row0, [&](int rr, int kk) { return A[(p * m_max + rr) * D + kk]; },
         [&](int rr) { return b[p * m_max + rr]; }, x, force_retry);
-    const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+    using rule::qnan;
     if (valid & (g.gl == 0)) {
 #pragma unroll
         for (int j = 0; j < D; ++j) xc[p * D + j] = (st == ST_OPT) ? x[j] : qnan;
@@ -80,11 +81,11 @@ __global__ __launch_bounds__(RBLK, (D <= 4 ? 3 : 1)) void cheby_r_kernel(long lo
 
 // Bounding box (polytope/polytope.py:1314-1411): the reference solves 2d generic LPs per polytope (F3:
 // min +-e_i.x over {Ax <= b}), each from scratch.  Here one lane group solves the Chebyshev LP of its polytope first
-// and, when that yields a centre with r >= BBOX_MIN_R, starts all 2d LPs from the dictionary translated to that
+// and, when that yields a centre with r >= rule::BBOX_MIN_R, starts all 2d LPs from the dictionary translated to that
 // centre (primal feasible, no phase 1; the fused reduce does the same for its box), reading x_i off the optimal
 // value.  status: 0 = lb/ub hold the box (+-inf where an LP is unbounded, :1376/:1398), 1 = not handled here
 // (empty / flat / unbounded-ball polytopes and Bland cases): the caller solves the generic LPs for those.
-constexpr double BBOX_MIN_R = 1e-6;
+// The read-out of an LP is rule::box_optimum / box_value (plp_reduce_rules.hpp), shared with the fused reduce's box.
 
 template <int D, int GS>
 __global__ __launch_bounds__(RBLK, (D <= 4 ? 3 : 1)) void bbox_r_kernel(long long B, int m_max,
@@ -107,7 +108,7 @@ __global__ __launch_bounds__(RBLK, (D <= 4 ? 3 : 1)) void bbox_r_kernel(long lon
     const int st = cheby_r_solve<D, GS, R>(
         g, valid, m, row0, [&](int rr, int kk) { return A[(p * m_max + rr) * D + kk]; },
         [&](int rr) { return b[p * m_max + rr]; }, x, force_retry);
-    const bool ok = valid & (st == ST_OPT) & (x[D] >= BBOX_MIN_R);
+    const bool ok = valid & (st == ST_OPT) & (x[D] >= rule::BBOX_MIN_R);
     bool handed = !ok;
     // my rows and their slacks at the centre
     double T0[R][D], be0[R];
@@ -124,8 +125,7 @@ __global__ __launch_bounds__(RBLK, (D <= 4 ? 3 : 1)) void bbox_r_kernel(long lon
         }
         be0[k] = h ? fmax(b[p * m_max + row0 + k] - s, 0.0) : 0.0;
     }
-    const double qnan = __longlong_as_double(0x7ff8000000000000ll);
-    const double pinf = __longlong_as_double(0x7ff0000000000000ll);
+    using rule::qnan;
     for (int it = 0; it < 2 * D; ++it) {  // lower_0, upper_0, lower_1, upper_1, ...
         const int kx = it >> 1;
         const bool up = it & 1;
@@ -150,11 +150,9 @@ __global__ __launch_bounds__(RBLK, (D <= 4 ? 3 : 1)) void bbox_r_kernel(long lon
 #pragma unroll
             for (int kk = 0; kk < D; ++kk) basis8[((size_t)p * 2 * D + it) * D + kk] = (signed char)(S.cv[kk] < D ? -1 - S.cv[kk] : S.cv[kk] - D);
         }
-        // zeta = c.x' = -negz ; x_k = xc_k + x'_k ; lower: c = +e_k, upper: c = -e_k
-        double val;
-        if (S.status == ST_OPT) val = up ? (xck + S.negz) : (xck - S.negz);
-        else if (S.status == ST_UNBND) val = up ? pinf : -pinf;
-        else { val = qnan; handed = true; }
+        bool bad;
+        const double val = rule::box_value(S.status, up, rule::box_optimum(up, xck, S.negz), bad);
+        handed = handed | bad;
         if (valid & (g.gl == 0)) (up ? ub : lb)[p * D + kx] = ok ? val : qnan;
     }
     if (valid & (g.gl == 0)) status[p] = handed ? 1 : 0;
@@ -189,7 +187,7 @@ __global__ __launch_bounds__(RBLK, (D <= 4 ? 3 : 1)) void bbox_split_kernel(long
     const int st = cheby_r_solve<D, GS, R>(
         g, valid, m, row0, [&](int rr, int kk) { return A[(p * m_max + rr) * D + kk]; },
         [&](int rr) { return b[p * m_max + rr]; }, x, force_retry);
-    const bool ok = valid & (st == ST_OPT) & (x[D] >= BBOX_MIN_R);
+    const bool ok = valid & (st == ST_OPT) & (x[D] >= rule::BBOX_MIN_R);
     bool handed = !ok;
     double T0[R][D], be0[R];
     unsigned has = 0u;
@@ -205,8 +203,7 @@ __global__ __launch_bounds__(RBLK, (D <= 4 ? 3 : 1)) void bbox_split_kernel(long
         }
         be0[k] = h ? fmax(b[p * m_max + row0 + k] - s, 0.0) : 0.0;
     }
-    const double qnan = __longlong_as_double(0x7ff8000000000000ll);
-    const double pinf = __longlong_as_double(0x7ff0000000000000ll);
+    using rule::qnan;
     for (int round = 0; round * NGRP < 2 * D; ++round) {  // group g: LP g, g + NGRP, ...
         const int itq = round * NGRP + grp;
         const bool mine = itq < 2 * D;
@@ -234,10 +231,9 @@ __global__ __launch_bounds__(RBLK, (D <= 4 ? 3 : 1)) void bbox_split_kernel(long
 #pragma unroll
             for (int kk = 0; kk < D; ++kk) basis8[((size_t)p * 2 * D + it) * D + kk] = (signed char)(S.cv[kk] < D ? -1 - S.cv[kk] : S.cv[kk] - D);
         }
-        double val;
-        if (S.status == ST_OPT) val = up ? (xck + S.negz) : (xck - S.negz);
-        else if (S.status == ST_UNBND) val = up ? pinf : -pinf;
-        else { val = qnan; handed = handed | mine; }
+        bool bad;
+        const double val = rule::box_value(S.status, up, rule::box_optimum(up, xck, S.negz), bad);
+        handed = handed | (bad & mine);
         if (valid & mine & (g.gl == 0)) (up ? ub : lb)[p * D + kx] = ok ? val : qnan;
     }
     const bool any_handed = __any(handed);  // (all lanes of the wavefront work on this one polytope)
@@ -384,7 +380,7 @@ __global__ __launch_bounds__(RBLK, (N <= 4 ? 3 : 1)) void lp_r_kernel(long long 
     else if (need_p1) { S.mode = M_DONE; S.status = P1_FAST<N>::value ? ST_RETRY_P1 : ST_RETRY; }
     S.template run_fast<GS, false>(g);
     const bool ok = S.status == ST_OPT;
-    const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+    using rule::qnan;
     double f = 0.0;
 #pragma unroll
     for (int j = 0; j < N; ++j) {
@@ -456,7 +452,7 @@ __global__ __launch_bounds__(RBLK, (R == 2 ? 2 : (N <= 3 ? 2 : 1))) void lp_p1_r
     S.mode = valid ? M_P2 : M_DONE;
     S.template run_two_phase<GS>(g, qi, actb, valid);
     const bool ok = S.status == ST_OPT;
-    const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+    using rule::qnan;
     double f = 0.0;
 #pragma unroll
     for (int j = 0; j < N; ++j) {

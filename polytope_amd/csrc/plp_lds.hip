@@ -15,6 +15,7 @@
 #include <stdlib.h>
 
 #include "plp_lp_launch.hpp"
+#include "plp_reduce_rules.hpp"
 #include "plp_wave.hpp"
 #include "plp_simplex.hpp"  // mode names
 
@@ -309,7 +310,7 @@ __global__ __launch_bounds__(64) void lp_lds_kernel(long long B, int m_max, int 
     const int lane = threadIdx.x;
     const int nc = n + 1;  // + phase-1 artificial
     const int ld = nc | 1;
-    const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+    using rule::qnan;
     for (long long lp = blockIdx.x; lp < B; lp += gridDim.x) {
         const int m = mrows ? mrows[lp] : m_max;
         const LdsDict D = lds_carve(smem_raw, m_max, ld);
@@ -442,7 +443,7 @@ __global__ __launch_bounds__(64) void cheby_lds_kernel(long long B, int m_max, i
     const int lane = threadIdx.x;
     const int nc = d + 1;
     const int ld = nc | 1;
-    const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+    using rule::qnan;
     for (long long p = blockIdx.x; p < B; p += gridDim.x) {
         const int m = mrows ? mrows[p] : m_max;
         const LdsDict D = lds_carve(smem_raw, m_max, ld);
@@ -489,10 +490,10 @@ __global__ __launch_bounds__(64) void cheby_gather_lds_kernel(long long nlp, int
 // reduce_lds_kernel -- fused reduce() (polytope/polytope.py:1053-1163) of polytopes with MORE THAN 64 ROWS: the stacks
 // Polytope.intersect builds (m1 + m2 rows, :268-275) and the leaves of region_diff (:2276) have no row limit in the
 // reference.  One polytope per wavefront; its rows (A, b, s = A xc, a state word per row) stay in LDS next to the
-// dictionary of the LP being solved; lane l owns rows l, l + 64, ...  The pipeline and every reference step are those
-// of reduce_r_tile (plp_reduce_r_impl.hpp): F1 -> parallel-row dedupe -> 2d F3 LPs + prefilter (rows > 3d) -> the F2
-// presolve (same two witness points) -> one F2 LP per row it leaves, each on lds_step (the general engine: Bland's rule
-// in the loop, no hand-over pass).  keep is W = ceil(m_max / 64) words per polytope.
+// dictionary of the LP being solved; lane l owns rows l, l + 64, ...  The pipeline is reduce_r_tile's (plp_reduce_r_impl.hpp),
+// the rules of its steps plp_reduce_rules.hpp's: F1 -> parallel-row dedupe -> 2d F3 LPs + prefilter -> the F2 presolve (same
+// two witness points) -> one F2 LP per row it leaves, each on lds_step (the general engine: Bland's rule in the loop, no
+// hand-over pass).  keep is W = ceil(m_max / 64) words per polytope.
 namespace {
 
 // ROW_SETTLED: live and settled as "keep" by the presolve.  ROW_DROPPED: found redundant by its F2 LP -- still a row of
@@ -551,8 +552,7 @@ __global__ __launch_bounds__(64) void reduce_lds_kernel(long long B, int m_max, 
     const int lane = threadIdx.x;
     const int nc1 = d + 1;
     const int ld = nc1 | 1;
-    const double qnan = __longlong_as_double(0x7ff8000000000000ll);
-    const double pinf = __longlong_as_double(0x7ff0000000000000ll);
+    using rule::qnan;
     RedRows R;
     R.A = reinterpret_cast<double*>(smem_raw + dict_bytes);
     R.b = R.A + (size_t)m_max * d;
@@ -596,7 +596,7 @@ __global__ __launch_bounds__(64) void reduce_lds_kernel(long long B, int m_max, 
         }
         const double rr = lds_x_of(D, m, d, lane);
         if (lane < d) R.xc[lane] = xcl;
-        bool ball = (S.status == ST_OPT) & (rr >= 0.0);  // cheby_ball: status 0 and r >= 0 (:1289-1293)
+        bool ball = rule::ball_ok(S.status, rr);
         __syncthreads();
         {   // a centre that violates a row (centre_off, plp_common.hpp) is no centre: RF_F1OPEN
             double xs = 1.0;
@@ -609,8 +609,8 @@ __global__ __launch_bounds__(64) void reduce_lds_kernel(long long B, int m_max, 
             }
             if (ball & (__ballot(off) != 0)) { ball = false; S.status = ST_NUM; }
         }
-        const bool fulldim = ball & (rr > abs_tol);
-        int flags = fulldim ? 0 : (RF_EMPTY | (((S.status != ST_OPT) & (S.status != ST_INFEAS)) ? RF_F1OPEN : 0));
+        const bool fulldim = rule::full_dim(ball, rr, abs_tol);
+        int flags = fulldim ? 0 : rule::empty_flags(rule::f1_open(S.status));
         int nlp = 1;
         int stage = 0;  // 0 done, 1 needs the box, 2 needs the redundancy LPs
         int neq = 0;
@@ -626,8 +626,8 @@ __global__ __launch_bounds__(64) void reduce_lds_kernel(long long B, int m_max, 
                     double dot = 0.0;
                     for (int k = 0; k < d; ++k) dot = dot + (R.A[i * d + k] * an_i) * (R.A[j * d + k] * an_j);
                     const double bjn = R.b[j] * an_j;
-                    const bool par = (j != i) & (dot > 1.0 - abs_tol);
-                    removed = removed | (par & ((i < j) ? !(bin_ < bjn) : (bjn < bin_)));
+                    const bool par = (j != i) & rule::same_plane(dot, abs_tol);
+                    removed = removed | (par & rule::row_goes(i, j, bin_, bjn));
                 }
                 if (removed) R.state[i] = ROW_DEAD;
             }
@@ -648,8 +648,8 @@ __global__ __launch_bounds__(64) void reduce_lds_kernel(long long B, int m_max, 
             }
             neq = wave_sum_i(cnt);
             __syncthreads();
-            if (neq <= d + 1) flags = RF_EARLY;
-            else stage = (neq > 3 * d) ? 1 : 2;
+            if (rule::few_rows(neq, d)) flags = RF_EARLY;
+            else stage = rule::box_first(neq, d) ? 1 : 2;
         }
         // ---------------------------------------------------------------- F3: bounding box (:1367-1409) + prefilter (:1118-1134)
         if (stage == 1) {
@@ -662,26 +662,20 @@ __global__ __launch_bounds__(64) void reduce_lds_kernel(long long B, int m_max, 
                 red_setup_lp(S, D, R, m, d, neq, lane, lane == kx ? (up ? -1.0 : 1.0) : 0.0);
                 while (S.mode != M_DONE) lds_step(S, D, lane);
                 const double xck = R.xc[kx];
-                double val;
-                if (S.status == ST_OPT) val = up ? (xck + S.negz) : (xck - S.negz);
-                else if (S.status == ST_UNBND) val = up ? pinf : -pinf;
-                else { val = qnan; lpfail = true; }
+                bool bad;
+                const double val = rule::box_value(S.status, up, rule::box_optimum(up, xck, S.negz), bad);
+                lpfail = lpfail | bad;
                 if (!up) {
                     lbk = val;
                 } else {
-                    for (int i = lane; i < m; i += 64) {
-                        const double aik = R.A[i * d + kx];
-                        const double pa = (aik > 0.0 ? 1.0 : 0.0) * aik;
-                        R.w1[i] = R.w1[i] + pa * (val - lbk);
-                        R.w2[i] = R.w2[i] + aik * lbk;
-                    }
+                    for (int i = lane; i < m; i += 64) rule::prefilter_add(R.A[i * d + kx], lbk, val, R.w1[i], R.w2[i]);
                 }
                 __syncthreads();
             }
             int cnt = 0;
             for (int i = lane; i < m; i += 64) {
                 const bool alive = R.state[i] != ROW_DEAD;
-                const bool out = alive & ((R.w1[i] - (R.b[i] - R.w2[i])) < -1e-4);
+                const bool out = alive & rule::prefilter_drops(R.w1[i], R.w2[i], R.b[i]);
                 if (out) {
                     R.state[i] = ROW_DEAD;
                     for (int k = 0; k < d; ++k) R.A[i * d + k] = 0.0;
@@ -693,30 +687,28 @@ __global__ __launch_bounds__(64) void reduce_lds_kernel(long long B, int m_max, 
             neq = wave_sum_i(cnt);
             nlp += 2 * d;
             if (lpfail) flags |= RF_LPFAIL;
-            if (neq <= d + 1) { flags |= RF_EARLY; stage = 0; }
+            if (rule::few_rows(neq, d)) { flags |= RF_EARLY; stage = 0; }
             else stage = 2;
             __syncthreads();
         }
         // ---------------------------------------------------------------- F2: presolve, then one LP per row it leaves (:1142-1160)
         if (stage == 2) {
             nlp += neq;
-            const bool presolve = abs_tol < 0.04;
+            const bool presolve = abs_tol < 0.04;   // (this kernel's alone: the other presolves have rule::presolve_reach only)
             for (int k = lane; presolve && k < m; k += 64) {   // (see f2_presolve in plp_reduce_r_impl.hpp: same witnesses)
                 if (R.state[k] == ROW_DEAD) continue;
                 double gkk = 0.0;
                 for (int c = 0; c < d; ++c) gkk = fma(R.A[k * d + c], R.A[k * d + c], gkk);
                 const double bk = R.b[k];
-                const double sk = fmax(bk - R.s[k], 0.0);
-                const double tau = abs_tol + 1e-9 * (1.0 + fabs(bk) + sk);
-                const double skt = sk + tau;
-                if (!((gkk > 0.0) & (tau < 0.05))) continue;
+                double skt;
+                if (!rule::presolve_reach(bk, fmax(bk - R.s[k], 0.0), abs_tol, gkk, skt)) continue;
                 bool ok = true;
                 int jb = 0;
                 for (int i = 0; i < m; ++i) {
                     double gik = 0.0;
                     for (int c = 0; c < d; ++c) gik = fma(R.A[i * d + c], R.A[k * d + c], gik);
                     const double si = fmax(R.b[i] - R.s[i], 0.0);
-                    const bool fine = (i == k) | (skt * gik <= si * gkk);
+                    const bool fine = (i == k) | rule::presolve_clear(skt, gik, si, gkk);
                     ok = ok & fine;
                     jb = fine ? jb : i;
                 }
@@ -727,12 +719,8 @@ __global__ __launch_bounds__(64) void reduce_lds_kernel(long long B, int m_max, 
                         gjj = fma(R.A[jb * d + c], R.A[jb * d + c], gjj);
                     }
                     const double sj = fmax(R.b[jb] - R.s[jb], 0.0);
-                    const double rho = gjk / gjj;
-                    const double t1 = (sj / gjk) * (1.0 - 0x1p-40);
-                    const double akd = fma(-rho, gjk, gkk);
-                    const double t2 = fma(-t1, gkk, skt) / akd;
-                    const double c1 = t1 + t2, c2 = t2 * rho;
-                    ok = (gjk > 0.0) & (akd > 1e-12 * gkk) & (t2 >= 0.0) & (t2 < 1e300);
+                    double c1, c2;
+                    ok = rule::presolve_second(sj, gjk, gjj, gkk, skt, c1, c2);
                     for (int i = 0; ok && i < m; ++i) {
                         double gik = 0.0, gij = 0.0;
                         for (int c = 0; c < d; ++c) {
@@ -740,8 +728,7 @@ __global__ __launch_bounds__(64) void reduce_lds_kernel(long long B, int m_max, 
                             gij = fma(R.A[i * d + c], R.A[jb * d + c], gij);
                         }
                         const double si = fmax(R.b[i] - R.s[i], 0.0);
-                        const double lhs = fma(-c2, gij, c1 * gik);
-                        ok = ok & ((i == k) | (lhs <= si));
+                        ok = ok & ((i == k) | rule::presolve_clear2(c1, c2, gik, gij, si));
                     }
                 }
                 if (ok) R.state[k] = ROW_SETTLED;
@@ -749,23 +736,23 @@ __global__ __launch_bounds__(64) void reduce_lds_kernel(long long B, int m_max, 
             __syncthreads();
             // settled rows: the reference's in-place round trip of h[k] right away (see f2_presolve)
             for (int k = lane; k < m; k += 64)
-                if (R.state[k] == ROW_SETTLED) R.b[k] = (R.b[k] + 0.1) - 0.1;
+                if (R.state[k] == ROW_SETTLED) R.b[k] = rule::rhs_round_trip(R.b[k]);
             __syncthreads();
             for (int kr = 0; kr < m; ++kr) {
                 if (R.state[kr] != ROW_LIVE) continue;   // (wave-uniform: an LDS word)
                 double cxc = 0.0;
                 for (int c = 0; c < d; ++c) cxc = fma(-R.A[kr * d + c], R.xc[c], cxc);
                 __syncthreads();
-                if (lane == 0) R.b[kr] = R.b[kr] + 0.1;  // h[k] += 0.1 in place (:1149)
+                if (lane == 0) R.b[kr] = rule::rhs_relaxed(R.b[kr]);  // in place (:1149)
                 __syncthreads();
                 red_setup_lp(S, D, R, m, d, neq, lane, lane < d ? -R.A[kr * d + (lane < d ? lane : 0)] : 0.0);
                 while (S.mode != M_DONE) lds_step(S, D, lane);
                 const double fun = cxc - S.negz;  // c.xc + zeta, zeta = -negz
-                const double hk = R.b[kr] - 0.1;  // (:1151)
+                const double hk = rule::rhs_restored(R.b[kr]);  // (:1151)
                 __syncthreads();
                 if (lane == 0) R.b[kr] = hk;
-                const double obj = -fun - hk;     // (:1156)
-                const bool keepk = ((S.status == ST_OPT) & (obj > abs_tol)) | (S.status == ST_UNBND);
+                const double obj = rule::f2_objective(fun, hk);
+                const bool keepk = rule::f2_keeps(S.status, obj, abs_tol);
                 if (!keepk && lane == 0) R.state[kr] = ROW_DROPPED;
                 __syncthreads();
             }

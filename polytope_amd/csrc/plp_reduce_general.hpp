@@ -3,13 +3,16 @@
 // (RF_RETRY); its tile, reduce_general_tile, is a device function so that the fast kernels can also redo such polytopes
 // in place instead of leaving them to a second launch.
 //
-// Reference behaviour restated (polytope/polytope.py:1053-1163, `reduce`), per polytope:
-//   1. is_fulldim -> cheby_ball: LP F1, r > abs_tol                      (:1081, :962-985, :1241-1300)
-//   2. pairwise parallel-row dedupe on unit rows                          (:1094-1112)
-//   3. early return when neq <= nx+1                                      (:1114-1116)
-//   4. if neq > 3 nx: bounding box = 2 nx LPs F3, prefilter rows          (:1118-1134, :1367-1409)
-//   5. early return when neq <= nx+1                                      (:1136-1138)
-//   6. one redundancy LP F2 per remaining row k (h[k] += 0.1 ... -= 0.1)  (:1142-1160)
+// Reference behaviour restated (polytope/polytope.py:1053-1163, `reduce`), per polytope; the thresholds and comparisons
+// of every step are plp_reduce_rules.hpp's (namespace rule), stated there once for this and the fast kernels:
+//   1. is_fulldim -> cheby_ball: LP F1        (:1081, :962-985, :1241-1300)   ball_ok, full_dim, f1_open, empty_flags
+//   2. pairwise parallel-row dedupe           (:1094-1112)                    same_plane, row_goes / pair_loser
+//   3. early return                           (:1114-1116)                    few_rows
+//   4. bounding box = 2 nx LPs F3, prefilter  (:1118-1134, :1367-1409)        box_first, box_optimum / _value, prefilter_add / _drops
+//   5. early return                           (:1136-1138)                    few_rows
+//   6. one redundancy LP F2 per remaining row (:1142-1160)                    f2_rhs, f2_objective, f2_keeps
+// (written out here, each under a comment naming its function: empty_flags, step 3, step 4's read-out and prefilter.  The
+// rule for this file: a call may replace them when the lane kernels, whose redo path this tile is, keep their scratch figure.)
 // Output: 64-bit keep mask over the INPUT rows, flags, Chebyshev ball, number of LPs solved.
 //
 // Mapping: a 256-thread workgroup takes a tile of NG = 256/GS polytopes (GS lanes per group,
@@ -30,6 +33,7 @@
 // (NT / gs) * gs * (D + 1) doubles.  `mine`: my lane group's polytope takes part (others are left untouched).
 #pragma once
 #include "plp_kernels.hpp"
+#include "plp_reduce_rules.hpp"
 #include "plp_simplex.hpp"
 
 namespace plp {
@@ -49,8 +53,8 @@ __device__ __forceinline__ void reduce_general_tile(unsigned char* smem_raw, con
     double* sb = sA + (size_t)NG * gs * D;               // [NG][gs]
     const double* myA = sA + (size_t)gib * gs * D;       // rows of my polytope
     const double* myb = sb + (size_t)gib * gs;
-    const double qnan = __longlong_as_double(0x7ff8000000000000ll);
-    const double pinf = __longlong_as_double(0x7ff0000000000000ll);
+    using rule::qnan;
+    using rule::pinf;
     // ---------------------------------------------------------------- stage rows in LDS
     __syncthreads();  // the previous tile's readers are done
     {
@@ -86,12 +90,11 @@ __device__ __forceinline__ void reduce_general_tile(unsigned char* smem_raw, con
     {
         double x1[D + 1];
         const int st1 = cheby_lp<D>(g, valid, has_row, m, gs, a, bi, x1, an_i);
-        const bool ok = st1 == ST_OPT;
-        f1open = valid && !ok && st1 != ST_INFEAS;   // (RF_F1OPEN, plp_common.hpp)
+        f1open = valid && rule::f1_open(st1);
 #pragma unroll
         for (int j = 0; j < D; ++j) xc[j] = x1[j];
         rr = x1[D];
-        ball = ok && rr >= 0.0;        // cheby_ball: status 0 and r >= 0 (:1289-1293)
+        ball = rule::ball_ok(st1, rr);
         {   // a centre that violates a row (centre_off, plp_common.hpp) is no centre: RF_F1OPEN
             double sk = 0.0;
 #pragma unroll
@@ -100,11 +103,9 @@ __device__ __forceinline__ void reduce_general_tile(unsigned char* smem_raw, con
                 ball = false; f1open = true;
             }
         }
-        fulldim = ball && rr > abs_tol;
+        fulldim = rule::full_dim(ball, rr, abs_tol);
     }
     // ---------------------------------------------------------------- dedupe (:1094-1110)
-    // unit rows with dot > 1 - abs_tol are the same hyperplane; of a pair (p<q) the one with the
-    // larger normalised offset goes, ties drop p.
     uint64_t live;
     {
         bool removed = false;
@@ -119,17 +120,17 @@ __device__ __forceinline__ void reduce_general_tile(unsigned char* smem_raw, con
 #pragma unroll
             for (int k = 0; k < D; ++k) dot = dot + ni[k] * (myA[j * D + k] * an_j);
             const double bjn = myb[j] * an_j;
-            const bool par = has_row && jrow && j != i && (dot > 1.0 - abs_tol);
-            removed = removed || (par && ((i < j) ? !(bin_ < bjn) : (bjn < bin_)));
+            const bool par = has_row && jrow && j != i && rule::same_plane(dot, abs_tol);
+            removed = removed || (par && rule::row_goes(i, j, bin_, bjn));
         }
         live = grp_ballot(has_row && !removed, g);
     }
-    int flags = fulldim ? 0 : (RF_EMPTY | (f1open ? RF_F1OPEN : 0));
+    int flags = fulldim ? 0 : (RF_EMPTY | (f1open ? RF_F1OPEN : 0));   // rule::empty_flags WRITTEN OUT (see the top)
     int nlp = 1;
     uint64_t keep = 0ull;
     int stage = 0;  // 0 done, 1 needs the box, 2 needs the redundancy LPs
     if (fulldim) {
-        const int neq = __popcll(live);
+        const int neq = __popcll(live);   // rule::few_rows / rule::box_first WRITTEN OUT
         if (neq <= D + 1) { flags = RF_EARLY; keep = live; }
         else stage = (neq > 3 * D) ? 1 : 2;
     }
@@ -162,7 +163,7 @@ __device__ __forceinline__ void reduce_general_tile(unsigned char* smem_raw, con
             S.rowact = lrow;
             S.mode = go ? M_P2 : M_DONE;
             S.run(g);
-            // zeta = c.x' = -negz ; x_k = xc_k + x'_k ; lower: c = +e_k, upper: c = -e_k
+            // rule::box_optimum / box_value, prefilter_add / prefilter_drops WRITTEN OUT (the lane kernels' redo path, as above)
             double val;
             if (S.status == ST_OPT) val = up ? (xck + S.negz) : (xck - S.negz);
             else if (S.status == ST_UNBND) val = up ? pinf : -pinf;
@@ -181,17 +182,13 @@ __device__ __forceinline__ void reduce_general_tile(unsigned char* smem_raw, con
             live = live & ~outb;
             nlp += 2 * D;
             if (lpfail) flags |= RF_LPFAIL;
-            if (__popcll(live) <= D + 1) { flags |= RF_EARLY; keep = live; stage = 0; }
+            if (rule::few_rows(__popcll(live), D)) { flags |= RF_EARLY; keep = live; stage = 0; }
             else stage = 2;
         }
     }
     // ---------------------------------------------------------------- F2: redundancy LPs (:1142-1160)
     if (__any(stage == 2)) {
         const bool lrow = (live >> i) & 1ull;
-        // h[k] += 0.1 for LP k; rows k' < k carry the (+0.1, -0.1) round trip (:1149-1151)
-        const double bup = bi + 0.1;
-        const double brt = bup - 0.1;
-        const double sh_plain = bi - s, sh_up = bup - s, sh_rt = brt - s;
         uint64_t todo = (stage == 2) ? live : 0ull;
         if (stage == 2) nlp += __popcll(live);
         while (__any(todo != 0ull)) {
@@ -208,16 +205,14 @@ __device__ __forceinline__ void reduce_general_tile(unsigned char* smem_raw, con
                 S.cost[kk] = ck;
                 cxc = fma(ck, xc[kk], cxc);
             }
-            const double bsh = (i < k) ? sh_rt : ((i == k) ? sh_up : sh_plain);
+            const double bsh = rule::f2_rhs(i < k, i == k, bi) - s;   // rows before k carry the round trip
             S.beta = (lrow && bsh > 0.0) ? bsh : 0.0;
             S.rowact = lrow;
             S.mode = go ? M_P2 : M_DONE;
             S.run(g);
             const double fun = cxc - S.negz;        // c.xc + zeta, zeta = -negz
-            const double bk = myb[k];
-            const double hk = (bk + 0.1) - 0.1;
-            const double obj = -fun - hk;           // (:1156)
-            const bool keepk = go && ((S.status == ST_OPT && obj > abs_tol) || S.status == ST_UNBND);
+            const double obj = rule::f2_objective(fun, rule::rhs_round_trip(myb[k]));
+            const bool keepk = go && rule::f2_keeps(S.status, obj, abs_tol);
             keep |= keepk ? (1ull << k) : 0ull;
         }
         if (stage == 2) flags |= RF_MINREP;

@@ -12,9 +12,9 @@
 //     F3: the 96 box LPs of a tile = two rounds (4 LPs per polytope, then 2),
 //     F2: the ~34 LPs the presolve leaves in a tile = one round (lane t takes the t-th LP of the tile's list).
 // F1 (the Chebyshev LP, d + 1 columns), the dedupe, the prefilter arithmetic and the presolve are those of the lane-group
-// kernel, instruction for instruction: r, xc and every verdict that does not come out of an F3 / F2 LP are bit for bit
-// the same; the LP optima agree to rounding (tests/test_lane_lp_host.py: 1e-12 against the oracle's simplex), so keep
-// masks, flags and LP counts are the oracle's (tests/test_gpu_parity.py, bench.py's full-batch check).
+// kernel, instruction for instruction (every step's rules: plp_reduce_rules.hpp): r, xc and every verdict that does not come
+// out of an F3 / F2 LP are bit for bit the same; the LP optima agree to rounding (tests/test_lane_lp_host.py: 1e-12 against the
+// oracle's simplex), so keep masks, flags and LP counts are the oracle's (tests/test_gpu_parity.py, bench.py's full-batch check).
 //
 // LDS layout: POLYTOPE-INTERLEAVED -- element (row i, column k) of the tile's polytope p at sA[(i * D + k) * 16 + p],
 // b and the per-row scalar likewise at [i * 16 + p].  Sixteen lanes that read the same element of sixteen different
@@ -99,8 +99,8 @@ __device__ __forceinline__ void reduce_lane_tile(
 #define OA(k, kk) rA[((k) * D + (kk)) * LS]
 #define OB(k) rS[OFF_B + (k) * LS]
 #define ON(k) rS[OFF_N + (k) * LS]
-    const double qnan = __longlong_as_double(0x7ff8000000000000ll);
-    const double pinf = __longlong_as_double(0x7ff0000000000000ll);
+    using rule::qnan;
+    using rule::pinf;
     const int ntile = (B - tile) < NG ? (int)(B - tile) : NG;
     __syncthreads();
     {
@@ -200,8 +200,9 @@ __device__ __forceinline__ void reduce_lane_tile(
         S.template run_fast<GS, true>(g, qi, actb);
 #endif
         retry = retry | (valid & (S.status == ST_RETRY));
+        // rule::f1_open and rule::ball_ok WRITTEN OUT (they share one compare of the status: ISA of two instances)
         const bool ok = S.status == ST_OPT;
-        f1open = valid & !ok & (S.status != ST_INFEAS);   // (RF_F1OPEN, plp_common.hpp)
+        f1open = valid & !ok & (S.status != ST_INFEAS);
 #pragma unroll
         for (int j = 0; j <= D; ++j) {
             bool found;
@@ -211,9 +212,9 @@ __device__ __forceinline__ void reduce_lane_tile(
             const double xj = ob ? v : 0.0;
             if (j < D) xc[j < D ? j : 0] = xj; else rr = xj;
         }
-        ball = ok & (rr >= 0.0);  // cheby_ball: status 0 and r >= 0 (:1289-1293)
-        fulldim = ball & (rr > abs_tol);
-        if constexpr (BBOX) fulldim = ball & (rr >= 1e-6);   // (BBOX_MIN_R of bbox_r_kernel: a centre worth starting from)
+        ball = ok & (rr >= 0.0);
+        fulldim = rule::full_dim(ball, rr, abs_tol);
+        if constexpr (BBOX) fulldim = ball & (rr >= rule::BBOX_MIN_R);   // (a centre worth starting from)
     }
     if (!BBOX && (valid & (g.gl == 0))) {
         (r_out + tile)[gib] = ball ? rr : 0.0;
@@ -254,12 +255,12 @@ __device__ __forceinline__ void reduce_lane_tile(
 #pragma unroll
                 for (int kk = 0; kk < D; ++kk) dot = dot + ni[k][kk] * (LA(j, kk) * an_j);
                 const double bjn = LB(j) * an_j;
-                const bool par = valid & (m <= rows) & (i < m) & (j < m) & (dot > 1.0 - abs_tol);
-                // the reference's rule for the pair (lo, hi), lo < hi (:1104-1109): b_lo < b_hi removes hi, else lo
+                const bool par = valid & (m <= rows) & (i < m) & (j < m) & rule::same_plane(dot, abs_tol);
+                // the pair as (lo, hi), lo < hi: one evaluation names the row that goes
                 const bool i_lo = i < j;
                 const double blo = i_lo ? bin_[k] : bjn, bhi = i_lo ? bjn : bin_[k];
                 const int lo = i_lo ? i : j, hi = i_lo ? j : i;
-                const int gone = (blo < bhi) ? hi : lo;
+                const int gone = rule::pair_loser(lo, hi, blo, bhi);
                 remmask |= par ? (1u << gone) : 0u;
             }
         }
@@ -327,12 +328,12 @@ __device__ __forceinline__ void reduce_lane_tile(
         }
     };
     zero_dead(((unsigned)(live >> row0) & RMASK));
-    int flags = fulldim ? 0 : (RF_EMPTY | (f1open ? RF_F1OPEN : 0));
+    int flags = fulldim ? 0 : rule::empty_flags(f1open);
     int nlp = 1, presolved = 0;
     uint64_t keep = 0ull;
     int stage = 0;  // 0 done, 1 needs the box, 2 needs the redundancy LPs
     if (fulldim) {
-        const int neq = __popcll(live);
+        const int neq = __popcll(live);   // rule::few_rows / rule::box_first WRITTEN OUT
         if (neq <= D + 1) { flags = RF_EARLY; keep = live; }
         else stage = (neq > 3 * D) ? 1 : 2;
         if constexpr (BBOX) stage = 1;   // every polytope with a usable centre gets its 2 d LPs
@@ -450,6 +451,7 @@ __device__ __forceinline__ void reduce_lane_tile(
 #pragma unroll
             for (int kk = 0; kk < D; ++kk) xck = (kk == kx) ? xc[kk] : xck;
             const double xk = x_of_lp(S, kx);
+            // rule::box_value WRITTEN OUT (the optimum, the walk's own point, is formed under its status branch: DESIGN.md 4.24)
             double v;
             if (S.status == ST_OPT) v = xck + xk;
             else if (S.status == ST_UNBND) v = up ? pinf : -pinf;
@@ -489,17 +491,12 @@ __device__ __forceinline__ void reduce_lane_tile(
             const double lo = bcast(val[f3_round_of(itl)], g.gbase + f3_lane_of(itl));
             const double hi = bcast(val[f3_round_of(ith)], g.gbase + f3_lane_of(ith));
 #pragma unroll
-            for (int k = 0; k < R; ++k) {
-                const double aik = OA(k, kx);
-                const double pa = (aik > 0.0 ? 1.0 : 0.0) * aik;
-                s1[k] = s1[k] + pa * (hi - lo);
-                s2[k] = s2[k] + aik * lo;
-            }
+            for (int k = 0; k < R; ++k) rule::prefilter_add(OA(k, kx), lo, hi, s1[k], s2[k]);
         }
         uint64_t outb = 0ull;
 #pragma unroll
         for (int k = 0; k < R; ++k) {
-            const bool out = go & (((lloc >> k) & 1u) != 0u) & ((s1[k] - (OB(k) - s2[k])) < -1e-4);
+            const bool out = go & (((lloc >> k) & 1u) != 0u) & rule::prefilter_drops(s1[k], s2[k], OB(k));
             outb |= spread_rows<R, GS>(grp_ballot(out, g)) << k;
         }
         __syncthreads();   // every lane's LPs have read the rows: the owners may zero the ones the prefilter removes
@@ -508,7 +505,7 @@ __device__ __forceinline__ void reduce_lane_tile(
             zero_dead(((unsigned)(live >> row0) & RMASK));
             nlp += 2 * D;
             if (lpfail) flags |= RF_LPFAIL;
-            if (__popcll(live) <= D + 1) { flags |= RF_EARLY; keep = live; stage = 0; }
+            if (rule::few_rows(__popcll(live), D)) { flags |= RF_EARLY; keep = live; stage = 0; }
             else stage = 2;
         }
         __syncthreads();
@@ -598,8 +595,8 @@ __device__ __forceinline__ void reduce_lane_tile(
             // after its round trip (:1149-1151):  hk - a_k.xc = beta_k up to the rounding of that round trip (1e-17)
             double akx = -lane::dot3(c[0], c[1], c[2], S.x0, S.x1, S.x2);
             if constexpr (D == 4) akx = -lane::dot4(c[0], c[1], c[2], c[3], S.x0, S.x1, S.x2, S.x3);
-            const double obj = akx - pan[kr * LS];
-            const bool keepk = mine & (((S.status == ST_OPT) & (obj > abs_tol)) | (S.status == ST_UNBND));
+            const double obj = akx - pan[kr * LS];   // (rule::f2_objective in centre-relative form, see above)
+            const bool keepk = mine & rule::f2_keeps(S.status, obj, abs_tol);
             const uint64_t all = __ballot(keepk);   // bit (t - rb) * nparts: the LP at list position t says "keep"
             const uint64_t rt = __ballot(mine & (S.status == ST_RETRY));
             if (rt != 0ull) {   // rare

@@ -1,17 +1,18 @@
 // plp_reduce_r_impl.hpp -- reduce_r_kernel<D,GS,R> and the other lane-group and one-polytope-per-wavefront kernels
 // (launched by plp_reduce_launch.hpp, as plp_reduce_plan.hpp decides): fused reduce() (polytope/polytope.py:1053-1163) with R = 4 rows per lane.
 //
-// Same pipeline and the same reference steps as plp_reduce.hip (F1 -> dedupe -> 2d F3 -> prefilter
-// -> one F2 per surviving row, all LPs of a polytope solved by one lane group out of registers),
-// but built on SimplexR (plp_simplex_r.hpp): a polytope with up to 16 / 32 / 64 rows occupies a
-// group of 4 / 8 / 16 lanes, lane l holding rows 4l..4l+3.  A wavefront therefore advances 16 / 8 / 4
-// polytopes per instruction instead of 4 / 2 / 1, and the per-pivot reductions are DPP quad steps.
+// Same pipeline and the same reference steps as plp_reduce_general.hpp (F1 -> dedupe -> 2d F3 -> prefilter -> one F2 per
+// surviving row, all LPs of a polytope solved by one lane group out of registers; every step's thresholds and comparisons
+// are plp_reduce_rules.hpp's), but built on SimplexR (plp_simplex_r.hpp): a polytope with up to 16 / 32 / 64 rows occupies
+// a group of 4 / 8 / 16 lanes, lane l holding rows 4l..4l+3.  A wavefront therefore advances 16 / 8 / 4 polytopes per
+// instruction instead of 4 / 2 / 1, and the per-pivot reductions are DPP quad steps.
 // A workgroup (RBLOCK threads) takes NG = RBLOCK/GS polytopes per tile; their rows are read from HBM once,
 // coalesced, into LDS (rows of F2's objective and the dedupe partners are read back from there).
 #pragma once
 #include <stdlib.h>
 
 #include "plp_kernels.hpp"
+#include "plp_reduce_rules.hpp"
 #include "plp_simplex_r.hpp"
 #include "plp_lazy.hpp"
 #include "plp_reduce_plan.hpp"
@@ -86,8 +87,8 @@ __device__ __forceinline__ void ctr_add(unsigned long long* ctr, int v, bool lea
 // unbounded LP is "keep" as well, so boundedness does not matter).  The witness: from the Chebyshev centre xc (strictly
 // inside, slack s_i = b_i - a_i.xc > 0) along a_k to the point  x* = xc + t a_k,  t = (s_k + tau) / |a_k|^2,  i.e. tau
 // beyond row k's own plane.  x* is feasible iff  t (a_i.a_k) <= s_i  for every other live row i, and
-// tau <= 0.1 keeps it inside the relaxed row k.  Division-free:  (s_k + tau) (a_i.a_k) <= s_i |a_k|^2.
-// tau = abs_tol + 1e-9 (1 + |b_k| + s_k): nine orders of magnitude above the rounding of either side.
+// tau below the relaxation keeps it inside the relaxed row k.  Division-free:  (s_k + tau) (a_i.a_k) <= s_i |a_k|^2.
+// The arithmetic of both witnesses is plp_reduce_rules.hpp's (presolve_reach: tau, nine orders above the rounding; ..._second).
 // Measured on random H-polytopes: 61 % of the F2 LPs at (16,3), 63 % at (32,6), 68 % at (64,8), 77 % at (64,16) are
 // settled here, for ~7 VALU instructions per pair of rows; the other rows (redundant ones, and facets whose foot point
 // lies outside the facet) run the simplex as before.  `nlp` still counts every LP the reference issues.
@@ -117,11 +118,9 @@ __device__ __forceinline__ unsigned f2_presolve(const double* myA, double* myb, 
         }
         const double bk = myb[(row0 + k) * LS];
         const double sk = BETA ? myan[(row0 + k) * LS] : fmax(bk - myan[(row0 + k) * LS], 0.0);
-        const double tau = abs_tol + 1e-9 * (1.0 + fabs(bk) + sk);
-        skt[k] = sk + tau;
         gkk[k] = g;
         jb[k] = 0;
-        if (!((g > 0.0) & (tau < 0.05))) { ok &= ~(1u << k); cand &= ~(1u << k); }  // (NaN-safe: such a row is never settled)
+        if (!rule::presolve_reach(bk, sk, abs_tol, g, skt[k])) { ok &= ~(1u << k); cand &= ~(1u << k); }
     }
     for (int i = 0; i < m_loop; ++i) {
         double ai[D];
@@ -133,7 +132,7 @@ __device__ __forceinline__ unsigned f2_presolve(const double* myA, double* myb, 
             double gik = 0.0;
 #pragma unroll
             for (int kk = 0; kk < D; ++kk) gik = fma(ai[kk], ak[k][kk], gik);
-            const bool fine = (i == row0 + k) | (skt[k] * gik <= si * gkk[k]);
+            const bool fine = (i == row0 + k) | rule::presolve_clear(skt[k], gik, si, gkk[k]);
             ok = fine ? ok : (ok & ~(1u << k));
             jb[k] = fine ? jb[k] : i;
         }
@@ -184,14 +183,7 @@ __device__ __forceinline__ unsigned f2_presolve(const double* myA, double* myb, 
                     gjj = fma(aj[q][kk], aj[q][kk], gjj);
                 }
                 const double sj = BETA ? myan[(j) * LS] : fmax(myb[(j) * LS] - myan[(j) * LS], 0.0);
-                const double rho = gjk / gjj;
-                const double t1 = (sj / gjk) * (1.0 - 0x1p-40);
-                const double akd = fma(-rho, gjk, gk);        // a_k.d = |a_k|^2 - (a_j.a_k)^2 / |a_j|^2 >= 0
-                const double t2 = fma(-t1, gk, sk_t) / akd;   // (s_k + tau - t1 |a_k|^2) / a_k.d
-                c1[q] = t1 + t2;
-                c2[q] = t2 * rho;
-                // (a blocked ray has a_j.a_k > 0 and t1 |a_k|^2 < s_k + tau; anything else -- parallel rows, NaN -- is left to the simplex)
-                if (!((gjk > 0.0) & (akd > 1e-12 * gk) & (t2 >= 0.0) & (t2 < 1e300))) ok2 &= ~(1u << k);
+                if (!rule::presolve_second(sj, gjk, gjj, gk, sk_t, c1[q], c2[q])) ok2 &= ~(1u << k);
             }
             for (int i = 0; i < m_loop; ++i) {
                 double ai[D];
@@ -206,8 +198,7 @@ __device__ __forceinline__ unsigned f2_presolve(const double* myA, double* myb, 
                         gik = fma(ai[kk], bk_[q][kk], gik);
                         gij = fma(ai[kk], aj[q][kk], gij);
                     }
-                    const double lhs = fma(-c2[q], gij, c1[q] * gik);
-                    const bool fine = (i == rowk[q]) | (lhs <= si);
+                    const bool fine = (i == rowk[q]) | rule::presolve_clear2(c1[q], c2[q], gik, gij, si);
                     ok2 = fine ? ok2 : (ok2 & ~(1u << kq[q]));
                 }
             }
@@ -216,7 +207,7 @@ __device__ __forceinline__ unsigned f2_presolve(const double* myA, double* myb, 
     ok |= ok2;
 #pragma unroll
     for (int k = 0; k < R; ++k)
-        if ((ok >> k) & 1u) myb[(row0 + k) * LS] = (myb[(row0 + k) * LS] + 0.1) - 0.1;  // (:1149-1151), see above
+        if ((ok >> k) & 1u) myb[(row0 + k) * LS] = rule::rhs_round_trip(myb[(row0 + k) * LS]);  // (:1149-1151), see above
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     return ok;
 }
@@ -265,8 +256,7 @@ __device__ __forceinline__ void reduce_r_tile(
     double* sval = san + (size_t)NG * rows;
     unsigned long long* skeep = reinterpret_cast<unsigned long long*>(sval + 2 * D);
     unsigned* sflag = reinterpret_cast<unsigned*>(skeep + 1);
-    const double qnan = __longlong_as_double(0x7ff8000000000000ll);
-    const double pinf = __longlong_as_double(0x7ff0000000000000ll);
+    using rule::qnan;
 
     {  // one tile per workgroup (no values kept live across a tile loop)
         const int ntile = (B - tile) < NG ? (int)(B - tile) : NG;
@@ -321,9 +311,9 @@ __device__ __forceinline__ void reduce_r_tile(
 #pragma unroll
             for (int j = 0; j < D; ++j) xc[j] = x1[j];
             rr = x1[D];
-            ball = (st1 == ST_OPT) & (rr >= 0.0);  // cheby_ball: status 0 and r >= 0 (:1289-1293)
-            fulldim = ball & (rr > abs_tol);
-            f1open = valid & (st1 != ST_OPT) & (st1 != ST_INFEAS);   // (RF_F1OPEN, plp_common.hpp)
+            ball = rule::ball_ok(st1, rr);
+            fulldim = rule::full_dim(ball, rr, abs_tol);
+            f1open = valid & rule::f1_open(st1);
         } else
         {
             // cheby_r_lp (plp_simplex_r.hpp) on the rows in LDS; 1 / ||a|| of every row goes there too, for the dedupe
@@ -340,13 +330,12 @@ __device__ __forceinline__ void reduce_r_tile(
                 if (valid & (g.gl == 0)) { PLP_STAT_ADD(2, it1); PLP_STAT_ADD(11, 1); }
             }
 #endif
-            const bool ok = st1 == ST_OPT;
-            f1open = valid & !ok & (st1 != ST_INFEAS);   // (RF_F1OPEN, plp_common.hpp)
+            f1open = valid & rule::f1_open(st1);
 #pragma unroll
             for (int j = 0; j < D; ++j) xc[j] = x1[j];
             rr = x1[D];
-            ball = ok & (rr >= 0.0);  // cheby_ball: status 0 and r >= 0 (:1289-1293)
-            fulldim = ball & (rr > abs_tol);
+            ball = rule::ball_ok(st1, rr);
+            fulldim = rule::full_dim(ball, rr, abs_tol);
         }
         // the Chebyshev ball is final: r and xc go out now (eight registers less to carry through the LP stages)
         if (valid & (g.gl == 0) & (!SPLIT || grp == 0)) {
@@ -384,12 +373,12 @@ __device__ __forceinline__ void reduce_r_tile(
 #pragma unroll
                     for (int kk = 0; kk < D; ++kk) dot = dot + ni[k][kk] * (myA[j * D + kk] * an_j);
                     const double bjn = myb[j] * an_j;
-                    const bool par = valid & (m <= rows) & (i < m) & (j < m) & (dot > 1.0 - abs_tol);
-                    // the reference's rule for the pair (lo, hi), lo < hi (:1104-1109): b_lo < b_hi removes hi, else lo
+                    const bool par = valid & (m <= rows) & (i < m) & (j < m) & rule::same_plane(dot, abs_tol);
+                    // the pair as (lo, hi), lo < hi: one evaluation names the row that goes
                     const bool i_lo = i < j;
                     const double blo = i_lo ? bin_[k] : bjn, bhi = i_lo ? bjn : bin_[k];
                     const int lo = i_lo ? i : j, hi = i_lo ? j : i;
-                    const int gone = (blo < bhi) ? hi : lo;
+                    const int gone = rule::pair_loser(lo, hi, blo, bhi);
                     remmask |= par ? (1u << gone) : 0u;
                 }
             }
@@ -422,8 +411,8 @@ __device__ __forceinline__ void reduce_r_tile(
 #pragma unroll
                     for (int kk = 0; kk < D; ++kk) dot = dot + ni[k][kk] * nj[kk];
                     const int i = row0 + k;
-                    const bool par = (((has >> k) & 1u) != 0u) & jrow & (j != i) & (dot > 1.0 - abs_tol);
-                    const bool rem = par & ((i < j) ? !(bin_[k] < bjn) : (bjn < bin_[k]));
+                    const bool par = (((has >> k) & 1u) != 0u) & jrow & (j != i) & rule::same_plane(dot, abs_tol);
+                    const bool rem = par & rule::row_goes(i, j, bin_[k], bjn);
                     removed |= rem ? (1u << k) : 0u;
                 }
             }
@@ -469,12 +458,12 @@ __device__ __forceinline__ void reduce_r_tile(
             }
         };
         zero_dead(((unsigned)(live >> row0) & RMASK));
-        int flags = fulldim ? 0 : (RF_EMPTY | (f1open ? RF_F1OPEN : 0));
+        int flags = fulldim ? 0 : rule::empty_flags(f1open);
         int nlp = 1;
         uint64_t keep = 0ull;
         int stage = 0;  // 0 done, 1 needs the box, 2 needs the redundancy LPs
         if (fulldim) {
-            const int neq = __popcll(live);
+            const int neq = __popcll(live);   // rule::few_rows / rule::box_first WRITTEN OUT
             if (neq <= D + 1) { flags = RF_EARLY; keep = live; }
             else stage = (neq > 3 * D) ? 1 : 2;
         }
@@ -523,11 +512,9 @@ __device__ __forceinline__ void reduce_r_tile(
                     S.ract = lloc;
                     S.mode = mine ? M_P2 : M_DONE;
                     S.template run_fast<GS>(g);
-                    double val;
-                    unsigned fl = 0u;
-                    if (S.status == ST_OPT) val = up ? (xck + S.negz) : (xck - S.negz);
-                    else if (S.status == ST_UNBND) val = up ? pinf : -pinf;
-                    else { val = qnan; fl = 1u; }
+                    bool bad;
+                    const double val = rule::box_value(S.status, up, rule::box_optimum(up, xck, S.negz), bad);
+                    unsigned fl = bad ? 1u : 0u;
                     if (S.status == ST_RETRY) fl |= 2u;
                     if (mine & (g.gl == 0)) {
                         sval[it] = val;
@@ -538,12 +525,7 @@ __device__ __forceinline__ void reduce_r_tile(
                 for (int kx = 0; kx < D; ++kx) {  // prefilter sums, accumulated in k order (:1131-1134)
                     const double lo = sval[2 * kx], hi = sval[2 * kx + 1];
 #pragma unroll
-                    for (int k = 0; k < R; ++k) {
-                        const double aik = myA[(row0 + k) * D + kx];
-                        const double pa = (aik > 0.0 ? 1.0 : 0.0) * aik;
-                        s1[k] = s1[k] + pa * (hi - lo);
-                        s2[k] = s2[k] + aik * lo;
-                    }
+                    for (int k = 0; k < R; ++k) rule::prefilter_add(myA[(row0 + k) * D + kx], lo, hi, s1[k], s2[k]);
                 }
                 const unsigned fl = *sflag;
                 lpfail = go & ((fl & 1u) != 0u);
@@ -595,11 +577,9 @@ __device__ __forceinline__ void reduce_r_tile(
                 S.status = S_.status;
                 S.negz = S_.negz;
                 }
-                // zeta = c.x' = -negz ; x_k = xc_k + x'_k ; lower: c = +e_k, upper: c = -e_k
-                double val;
-                if (S.status == ST_OPT) val = up ? (xck + S.negz) : (xck - S.negz);
-                else if (S.status == ST_UNBND) val = up ? pinf : -pinf;
-                else { val = qnan; lpfail = lpfail | go; }
+                bool bad;
+                const double val = rule::box_value(S.status, up, rule::box_optimum(up, xck, S.negz), bad);
+                lpfail = lpfail | (bad & go);
                 if (!up) {
                     lbk = val;
                 } else if constexpr (BOX_IN_LANES) {
@@ -612,12 +592,7 @@ __device__ __forceinline__ void reduce_r_tile(
                     }
                 } else {  // prefilter sums, accumulated in k order (:1131-1134)
 #pragma unroll
-                    for (int k = 0; k < R; ++k) {
-                        const double aik = myA[(row0 + k) * D + kx];
-                        const double pa = (aik > 0.0 ? 1.0 : 0.0) * aik;
-                        s1[k] = s1[k] + pa * (val - lbk);
-                        s2[k] = s2[k] + aik * lbk;
-                    }
+                    for (int k = 0; k < R; ++k) rule::prefilter_add(myA[(row0 + k) * D + kx], lbk, val, s1[k], s2[k]);
                 }
             }
             if constexpr (BOX_IN_LANES) {
@@ -626,18 +601,13 @@ __device__ __forceinline__ void reduce_r_tile(
                     const double lo = bcast(blo[kx / GS], g.gbase + kx % GS);
                     const double hi = bcast(bhi[kx / GS], g.gbase + kx % GS);
 #pragma unroll
-                    for (int k = 0; k < R; ++k) {
-                        const double aik = myA[(row0 + k) * D + kx];
-                        const double pa = (aik > 0.0 ? 1.0 : 0.0) * aik;
-                        s1[k] = s1[k] + pa * (hi - lo);
-                        s2[k] = s2[k] + aik * lo;
-                    }
+                    for (int k = 0; k < R; ++k) rule::prefilter_add(myA[(row0 + k) * D + kx], lo, hi, s1[k], s2[k]);
                 }
             }
             uint64_t outb = 0ull;
 #pragma unroll
             for (int k = 0; k < R; ++k) {
-                const bool out = go & (((lloc >> k) & 1u) != 0u) & ((s1[k] - (myb[row0 + k] - s2[k])) < -1e-4);
+                const bool out = go & (((lloc >> k) & 1u) != 0u) & rule::prefilter_drops(s1[k], s2[k], myb[row0 + k]);
                 outb |= spread_rows<R, GS>(grp_ballot(out, g)) << k;
             }
             if (go) {
@@ -645,7 +615,7 @@ __device__ __forceinline__ void reduce_r_tile(
                 zero_dead(((unsigned)(live >> row0) & RMASK));
                 nlp += 2 * D;
                 if (lpfail) flags |= RF_LPFAIL;
-                if (__popcll(live) <= D + 1) { flags |= RF_EARLY; keep = live; stage = 0; }
+                if (rule::few_rows(__popcll(live), D)) { flags |= RF_EARLY; keep = live; stage = 0; }
                 else stage = 2;
             }
         }
@@ -678,19 +648,16 @@ __device__ __forceinline__ void reduce_r_tile(
                         for (int kk = 0; kk < D; ++kk) S.T[k][kk] = myA[(row0 + k) * D + kk];
                         // h as the reference holds it when row kr has its turn (:1149-1151): rows before it carry the round trip
                         const int rw = row0 + k;
-                        const double h0 = myb[rw];
-                        const double hp = h0 + 0.1;
                         const bool lv = ((lloc >> k) & 1u) != 0u;
-                        const double hh = (lv & (rw < kr)) ? hp - 0.1 : ((lv & (rw == kr)) ? hp : h0);
+                        const double hh = rule::f2_rhs(lv & (rw < kr), lv & (rw == kr), myb[rw]);
                         S.beta[k] = fmax(hh - myan[rw], 0.0);  // 0 for the zeroed rows
                     }
                     S.ract = lloc;
                     S.mode = mine ? M_P2 : M_DONE;
                     S.template run_fast<GS>(g);
                     const double fun = cxc - S.negz;  // c.xc + zeta, zeta = -negz
-                    const double hk = (myb[kr] + 0.1) - 0.1;
-                    const double obj = -fun - hk;  // (:1156)
-                    const bool keepk = mine & (((S.status == ST_OPT) & (obj > abs_tol)) | (S.status == ST_UNBND));
+                    const double obj = rule::f2_objective(fun, rule::rhs_round_trip(myb[kr]));
+                    const bool keepk = mine & rule::f2_keeps(S.status, obj, abs_tol);
                     if (g.gl == 0) {
                         if (keepk) atomicOr(skeep, 1ull << kr);
                         if (mine & (S.status == ST_RETRY)) atomicOr(sflag, 2u);
@@ -724,7 +691,7 @@ __device__ __forceinline__ void reduce_r_tile(
                     const double ck = g.lane < D ? -myA[kr * D + (g.lane < D ? g.lane : 0)] : 0.0;  // f = -A[k,:]  (:1145)
                     const double cxc = -myan[kr];
                     const bool owner = kr == row0;
-                    if (owner) myb[kr] = myb[kr] + 0.1;  // h[k] += 0.1 in place (:1149), undone below (:1151)
+                    if (owner) myb[kr] = rule::rhs_relaxed(myb[kr]);  // in place (:1149), undone below (:1151)
                     double negz2 = 0.0;
                     int st2;
                     if constexpr (WDENSE)
@@ -736,11 +703,9 @@ __device__ __forceinline__ void reduce_r_tile(
                     retry = retry | (st2 == ST_RETRY);
                     const double fun = cxc - negz2;  // c.xc + zeta, zeta = -negz
                     double hk_own = 0.0;
-                    if (owner) { hk_own = myb[kr] - 0.1; myb[kr] = hk_own; }
-                    const double hk = bcast(hk_own, kr);
-                    const double obj = -fun - hk;  // (:1156)
-                    const bool keepk = ((st2 == ST_OPT) & (obj > abs_tol)) | (st2 == ST_UNBND);
-                    keep |= keepk ? (1ull << kr) : 0ull;
+                    if (owner) { hk_own = rule::rhs_restored(myb[kr]); myb[kr] = hk_own; }
+                    const double obj = rule::f2_objective(fun, bcast(hk_own, kr));
+                    keep |= rule::f2_keeps(st2, obj, abs_tol) ? (1ull << kr) : 0ull;
                 }
                 flags |= RF_MINREP;
             }
@@ -835,10 +800,8 @@ __device__ __forceinline__ void reduce_r_tile(
                             if (fin) {
                                 pool_retry = pool_retry | (S.status == ST_RETRY);
                                 const double fun = cxc - S.negz;               // c.xc + zeta, zeta = -negz
-                                const double hk = (sb[cur_p * rows + kr] + 0.1) - 0.1;   // h[k] after its round trip (:1149-1151)
-                                const double obj = -fun - hk;                  // (:1156)
-                                const bool keepk = ((S.status == ST_OPT) & (obj > abs_tol)) | (S.status == ST_UNBND);
-                                res |= keepk ? (1ull << (cur_t - rb)) : 0ull;
+                                const double obj = rule::f2_objective(fun, rule::rhs_round_trip(sb[cur_p * rows + kr]));
+                                res |= rule::f2_keeps(S.status, obj, abs_tol) ? (1ull << (cur_t - rb)) : 0ull;
                                 busy = false;
                             }
                             if (start) {
@@ -858,10 +821,8 @@ __device__ __forceinline__ void reduce_r_tile(
 #pragma unroll
                                     for (int kk = 0; kk < D; ++kk) S.T[k][kk] = pA[(row0 + k) * D + kk];
                                     const int rw = row0 + k;
-                                    const double h0 = pb[rw];
-                                    const double hp = h0 + 0.1;
                                     const bool un = ((unsettled >> k) & 1u) != 0u;
-                                    const double hh = (un & (rw < kr)) ? hp - 0.1 : ((rw == kr) ? hp : h0);
+                                    const double hh = rule::f2_rhs(un & (rw < kr), rw == kr, pb[rw]);
                                     S.beta[k] = fmax(hh - pan[rw], 0.0);  // 0 for the zeroed rows
                                 }
                                 S.ract = (lv >> row0) & RMASK;
@@ -921,11 +882,9 @@ __device__ __forceinline__ void reduce_r_tile(
                         // other lanes would need a fence for the compiler, which otherwise keeps an earlier load)
                         const bool owner = (kr >> RSH) == g.gl;
                         double hk_own = 0.0;
-                        if (owner) { hk_own = myb[kr] - 0.1; myb[kr] = hk_own; }
-                        const double hk = bcast(hk_own, g.gbase + (kr >> RSH));
-                        const double obj = -fun - hk;  // (:1156)
-                        const bool keepk = ((S.status == ST_OPT) & (obj > abs_tol)) | (S.status == ST_UNBND);
-                        keep |= keepk ? (1ull << kr) : 0ull;
+                        if (owner) { hk_own = rule::rhs_restored(myb[kr]); myb[kr] = hk_own; }
+                        const double obj = rule::f2_objective(fun, bcast(hk_own, g.gbase + (kr >> RSH)));
+                        keep |= rule::f2_keeps(S.status, obj, abs_tol) ? (1ull << kr) : 0ull;
                         busy = false;
                     }
                     if (start) {
@@ -935,7 +894,7 @@ __device__ __forceinline__ void reduce_r_tile(
 #pragma unroll
                         for (int kk = 0; kk < D; ++kk) S.cost[kk] = -myA[kr * D + kk];  // f = -A[k,:]  (:1145)
                         cxc = -myan[kr];   // c.xc = -(a_k.xc): the mirror image of the FMA chain that made s_k
-                        if ((kr >> RSH) == g.gl) myb[kr] = myb[kr] + 0.1;  // h[k] += 0.1 in place (:1149)
+                        if ((kr >> RSH) == g.gl) myb[kr] = rule::rhs_relaxed(myb[kr]);  // in place (:1149)
 #pragma unroll
                         for (int k = 0; k < R; ++k) {
 #pragma unroll
@@ -1025,9 +984,8 @@ __device__ __forceinline__ bool f2_presolve_ws(const double* myA, const double* 
     }
     const double bk = myb[lane];
     const double sk = fmax(bk - myan[lane], 0.0);
-    const double tau = abs_tol + 1e-9 * (1.0 + fabs(bk) + sk);
-    const double skt = sk + tau;
-    if (!((g > 0.0) & (tau < 0.05))) cand = false;  // (NaN-safe: such a row is never settled)
+    double skt;
+    if (!rule::presolve_reach(bk, sk, abs_tol, g, skt)) cand = false;
     const int iw = (m_loop + NW - 1) / NW;
     const int i0 = w * iw;
     const int i1 = i0 + iw < m_loop ? i0 + iw : m_loop;
@@ -1041,7 +999,7 @@ __device__ __forceinline__ bool f2_presolve_ws(const double* myA, const double* 
         double gik = 0.0;
 #pragma unroll
         for (int kk = 0; kk < D; ++kk) gik = fma(ai[kk], ak[kk], gik);
-        const bool fine = (i == lane) | (skt * gik <= si * g);
+        const bool fine = (i == lane) | rule::presolve_clear(skt, gik, si, g);
         ok = ok & fine;
         jb = fine ? jb : i;
     }
@@ -1070,13 +1028,8 @@ __device__ __forceinline__ bool f2_presolve_ws(const double* myA, const double* 
             gjj = fma(aj[kk], aj[kk], gjj);
         }
         const double sj = fmax(myb[j] - myan[j], 0.0);
-        const double rho = gjk / gjj;
-        const double t1 = (sj / gjk) * (1.0 - 0x1p-40);
-        const double akd = fma(-rho, gjk, g);
-        const double t2 = fma(-t1, g, skt) / akd;
-        const double c1 = t1 + t2;
-        const double c2 = t2 * rho;
-        if (!((gjk > 0.0) & (akd > 1e-12 * g) & (t2 >= 0.0) & (t2 < 1e300))) ok2 = false;
+        double c1, c2;
+        if (!rule::presolve_second(sj, gjk, gjj, g, skt, c1, c2)) ok2 = false;
         for (int i = i0; i < i1; ++i) {
             double ai[D];
 #pragma unroll
@@ -1088,8 +1041,7 @@ __device__ __forceinline__ bool f2_presolve_ws(const double* myA, const double* 
                 gik = fma(ai[kk], ak[kk], gik);
                 gij = fma(ai[kk], aj[kk], gij);
             }
-            const double lhs = fma(-c2, gij, c1 * gik);
-            const bool fine = (i == lane) | (lhs <= si);
+            const bool fine = (i == lane) | rule::presolve_clear2(c1, c2, gik, gij, si);
             ok2 = ok2 & fine;
         }
         const uint64_t m2 = __ballot(ok2);
@@ -1144,8 +1096,7 @@ __global__ __launch_bounds__(64 * NW, PLP_REDUCE_WSPLIT_WAVES(D)) void reduce_ws
     unsigned long long* smask = reinterpret_cast<unsigned long long*>(reinterpret_cast<unsigned char*>(slist + 64) +
                                                                       (size_t)NW * wsplit_block_bytes<D>());  // [2 NW]
     int* sjb = reinterpret_cast<int*>(smask + 2 * NW);                                                        // [NW][64]
-    const double qnan = __longlong_as_double(0x7ff8000000000000ll);
-    const double pinf = __longlong_as_double(0x7ff0000000000000ll);
+    using rule::qnan;
     {
         const int rowsz = m_max * D;
         const double* src = Ag + pg * rowsz;
@@ -1176,8 +1127,8 @@ __global__ __launch_bounds__(64 * NW, PLP_REDUCE_WSPLIT_WAVES(D)) void reduce_ws
 #pragma unroll
         for (int j = 0; j < D; ++j) xc1[j] = x1[j];
         const double rr1 = x1[D];
-        bool ball1 = (st1 == ST_OPT) & (rr1 >= 0.0);  // cheby_ball: status 0 and r >= 0 (:1289-1293)
-        bool full1 = ball1 & (rr1 > abs_tol);
+        bool ball1 = rule::ball_ok(st1, rr1);
+        bool full1 = rule::full_dim(ball1, rr1, abs_tol);
         {   // a centre that violates a row (centre_off, plp_common.hpp) is no centre: RF_F1OPEN
             double sk = 0.0;
 #pragma unroll
@@ -1192,7 +1143,7 @@ __global__ __launch_bounds__(64 * NW, PLP_REDUCE_WSPLIT_WAVES(D)) void reduce_ws
 #pragma unroll
             for (int k = 0; k < D; ++k) { xc_out[pg * D + k] = ball1 ? xc1[k] : qnan; sxc[k] = xc1[k]; }
             sxc[D] = rr1;
-            s32[3] = (ball1 ? 1u : 0u) | (full1 ? 2u : 0u) | (((st1 != ST_OPT) & (st1 != ST_INFEAS)) ? 4u : 0u);   // bit 2: RF_F1OPEN
+            s32[3] = (ball1 ? 1u : 0u) | (full1 ? 2u : 0u) | (rule::f1_open(st1) ? 4u : 0u);   // bit 2: RF_F1OPEN
         }
     } else {
         // ------------------------------------------------------------ dedupe (:1094-1110): the partners j in NW - 1 ranges
@@ -1211,8 +1162,8 @@ __global__ __launch_bounds__(64 * NW, PLP_REDUCE_WSPLIT_WAVES(D)) void reduce_ws
 #pragma unroll
             for (int kk = 0; kk < D; ++kk) dot = dot + ni[kk] * (myA[j * D + kk] * an_j);
             const double bjn = myb[j] * an_j;
-            const bool par = has & jrow & (j != lane) & (dot > 1.0 - abs_tol);
-            const bool rem = par & ((lane < j) ? !(bin_ < bjn) : (bjn < bin_));
+            const bool par = has & jrow & (j != lane) & rule::same_plane(dot, abs_tol);
+            const bool rem = par & rule::row_goes(lane, j, bin_, bjn);
             removed = removed | rem;
         }
         const uint64_t rb = __ballot(removed);
@@ -1239,14 +1190,14 @@ __global__ __launch_bounds__(64 * NW, PLP_REDUCE_WSPLIT_WAVES(D)) void reduce_ws
         myan[lane] = sk;
         zero_dead(((live >> lane) & 1ull) != 0ull);
     }
-    int flags = fulldim ? 0 : (RF_EMPTY | ((s32[3] & 4u) ? RF_F1OPEN : 0));
+    int flags = fulldim ? 0 : rule::empty_flags((s32[3] & 4u) != 0u);
     int nlp = 1;
     uint64_t keep = 0ull;
     int stage = 0;
     if (fulldim) {
         const int neq = __popcll(live);
-        if (neq <= D + 1) { flags = RF_EARLY; keep = live; }
-        else stage = (neq > 3 * D) ? 1 : 2;
+        if (rule::few_rows(neq, D)) { flags = RF_EARLY; keep = live; }
+        else stage = rule::box_first(neq, D) ? 1 : 2;
     }
     __syncthreads();
     wide::WideShared<D>& shd = *reinterpret_cast<wide::WideShared<D>*>(shb);
@@ -1268,11 +1219,9 @@ __global__ __launch_bounds__(64 * NW, PLP_REDUCE_WSPLIT_WAVES(D)) void reduce_ws
             else   // (d beyond PLP_REDUCE_WDENSE_MAXD: the LPs without a stored dictionary, plp_lazy.hpp)
                 st = lazy::solve<D>(lane, nlive, myA, (lane == kx) ? (up ? -1.0 : 1.0) : 0.0,
                                     fmax(myb[lane] - myan[lane], 0.0), act, negz);
-            double val;
-            unsigned fl = 0u;
-            if (st == ST_OPT) val = up ? (xck + negz) : (xck - negz);
-            else if (st == ST_UNBND) val = up ? pinf : -pinf;
-            else { val = qnan; fl = 1u; }
+            bool bad;
+            const double val = rule::box_value(st, up, rule::box_optimum(up, xck, negz), bad);
+            unsigned fl = bad ? 1u : 0u;
             if (st == ST_RETRY) fl |= 2u;
             if (lane == 0) {
                 sval[it] = val;
@@ -1283,13 +1232,9 @@ __global__ __launch_bounds__(64 * NW, PLP_REDUCE_WSPLIT_WAVES(D)) void reduce_ws
         if (w == 0) {   // prefilter sums, accumulated in k order (:1131-1134)
             double s1 = 0.0, s2 = 0.0;
             for (int kx = 0; kx < D; ++kx) {
-                const double lo = sval[2 * kx], hi = sval[2 * kx + 1];
-                const double aik = myA[lane * D + kx];
-                const double pa = (aik > 0.0 ? 1.0 : 0.0) * aik;
-                s1 = s1 + pa * (hi - lo);
-                s2 = s2 + aik * lo;
+                rule::prefilter_add(myA[lane * D + kx], sval[2 * kx], sval[2 * kx + 1], s1, s2);
             }
-            const bool out = act & ((s1 - (myb[lane] - s2)) < -1e-4);
+            const bool out = act & rule::prefilter_drops(s1, s2, myb[lane]);
             const uint64_t l2 = live & ~__ballot(out);
             zero_dead(((l2 >> lane) & 1ull) != 0ull);
             if (lane == 0) s64[3] = l2;
@@ -1300,7 +1245,7 @@ __global__ __launch_bounds__(64 * NW, PLP_REDUCE_WSPLIT_WAVES(D)) void reduce_ws
         retry = retry | ((fl & 2u) != 0u);
         nlp += 2 * D;
         if (fl & 1u) flags |= RF_LPFAIL;
-        if (__popcll(live) <= D + 1) { flags |= RF_EARLY; keep = live; stage = 0; }
+        if (rule::few_rows(__popcll(live), D)) { flags |= RF_EARLY; keep = live; stage = 0; }
         else stage = 2;
     }
     // ---------------------------------------------------------------- F2: redundancy LPs (:1142-1160)
@@ -1316,7 +1261,7 @@ __global__ __launch_bounds__(64 * NW, PLP_REDUCE_WSPLIT_WAVES(D)) void reduce_ws
         if (w == 0) {
             ctr_add(ctr, -__popcll(cert), lane == 0);
             if ((lane == 0) & (cert != 0ull)) atomicOr(&s64[1], (unsigned long long)cert);
-            if (settled) myb[lane] = (myb[lane] + 0.1) - 0.1;  // (:1149-1151), as f2_presolve leaves the settled rows
+            if (settled) myb[lane] = rule::rhs_round_trip(myb[lane]);  // (:1149-1151), as f2_presolve leaves the settled rows
         }
         if ((w == 0) && ((todo >> lane) & 1ull)) slist[__popcll(todo & ((1ull << lane) - 1ull))] = lane;
         __syncthreads();
@@ -1329,16 +1274,14 @@ __global__ __launch_bounds__(64 * NW, PLP_REDUCE_WSPLIT_WAVES(D)) void reduce_ws
             const double ck = lane < D ? -myA[kr * D + (lane < D ? lane : 0)] : 0.0;  // f = -A[k,:]  (:1145)
             const double cxc = -myan[kr];
             // h as the reference holds it when row kr has its turn (:1149-1151)
-            const double hp = h0 + 0.1;
-            const double hh = (mytodo & (lane < kr)) ? hp - 0.1 : ((lane == kr) ? hp : h0);
+            const double hh = rule::f2_rhs(mytodo & (lane < kr), lane == kr, h0);
             double negz2 = 0.0;
             int st2;
             if constexpr (WDENSE) st2 = wide::solve_dense<D>(lane, nlive, myA, ck, fmax(hh - sl, 0.0), act, negz2, shd);
             else st2 = lazy::solve<D>(lane, nlive, myA, ck, fmax(hh - sl, 0.0), act, negz2);
             const double fun = cxc - negz2;  // c.xc + zeta, zeta = -negz
-            const double hk = (myb[kr] + 0.1) - 0.1;
-            const double obj = -fun - hk;    // (:1156)
-            const bool keepk = ((st2 == ST_OPT) & (obj > abs_tol)) | (st2 == ST_UNBND);
+            const double obj = rule::f2_objective(fun, rule::rhs_round_trip(myb[kr]));
+            const bool keepk = rule::f2_keeps(st2, obj, abs_tol);
             if (lane == 0) {
                 if (keepk) atomicOr(&s64[1], 1ull << kr);
                 if (st2 == ST_RETRY) atomicOr(&s32[0], 2u);
